@@ -9,6 +9,11 @@ step     : one pass of the whole hot path over one batch: ElphHashes.build_hash_
            h-1 table hops with fused cardinalities) + ElphHashes.get_subgraph_features(B pairs), i.e. what ELPH does
            per training step (reference runners/train.py:198,204) and what BUDDY does once per edge set.  Nothing is
            cached between steps.  Inputs (edge_index, links) are resident in HBM.
+plain run: `bench.py --gpus N --steps K --warmup W` sets up, runs the step untimed for --settle-seconds and then W warm-up steps,
+           times K steps and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step and the keys that
+           describe the run).  --dump-outputs DIR writes what the last timed step returned (dump_outputs).  Everything below that is
+           not the timed region itself -- ms_per_step_cold, the roofline (HIP events inside the timed region), latency, the sustained
+           run, breakdown, kernels, secondary, cpu_baseline, and at N > 1 the build probe, weak and strong figures -- runs with --full only.
 N > 1    : one process per GPU (torchrun), per-batch feature rows all-gathered over RCCL (async, on RCCL's stream,
            double-buffered, every gather completed inside the timed region).
            --scaling weak (default): every rank owns its own B pairs AND repeats the whole build (table replicated):
@@ -192,6 +197,51 @@ def emit(out):
             line[k] = out[k]
     line.update({k: v for k, v in out.items() if k not in line})
     print(json.dumps(line), flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_TABLE_ROWS = 2048     # rows of every hop's MinHash / HLL table written (the same rows for every hop)
+
+
+def sample_rows(n_rows, row_bytes, max_bytes, seed):
+    """None (every row) when n_rows rows fit in max_bytes, else a fixed, seeded, sorted sample of row indices that fits together with
+    its own float64 index"""
+    if n_rows * row_bytes <= max_bytes:
+        return None
+    k = min(n_rows, max(1, max_bytes // (row_bytes + 8)))
+    return np.sort(np.random.RandomState(seed).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(path, feats, table, cards):
+    """--dump-outputs: what the last timed step handed its caller -- the feature rows of get_subgraph_features, the cardinalities and the
+    per-hop MinHash / HLL tables of build_hash_tables (the reference-shaped int64 / int8 leaves) -- as DIR/<name>.npy in float32, or in
+    float64 for the uint32 MinHash values (exact).  An array above its share of DUMP_MAX_BYTES is a fixed, seeded sample of its rows,
+    whose indices are written beside it as <name>_rows.npy; the inputs of a run are fixed by its arguments, so two builds of the project
+    can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+
+    def put(name, t, dtype, idx):
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+            arrays[f'{name}_rows'] = idx.astype(np.float64)
+        arrays[name] = t.cpu().numpy().astype(dtype)
+
+    put('features', feats, np.float32, sample_rows(feats.shape[0], 4 * feats[0].numel(), 20 << 20, 11))
+    put('cards', cards, np.float32, sample_rows(cards.shape[0], 4 * cards[0].numel(), 12 << 20, 12))
+    n = cards.shape[0]
+    rows = np.sort(np.random.RandomState(13).choice(n, size=DUMP_TABLE_ROWS, replace=False)) if n > DUMP_TABLE_ROWS else None
+    if rows is not None:
+        arrays['table_rows'] = rows.astype(np.float64)
+    sel = torch.from_numpy(rows if rows is not None else np.arange(n))
+    for k in sorted(table):
+        arrays[f'minhash_hop{k}'] = table[k]['minhash'][sel.to(table[k]['minhash'].device)].cpu().numpy().astype(np.float64)
+        arrays[f'hll_hop{k}'] = table[k]['hll'][sel.to(table[k]['hll'].device)].cpu().numpy().astype(np.float32)
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}'
+    for name, x in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), x)
+    print(f'dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MiB -> {path}', file=sys.stderr, flush=True)
 
 
 def resident_label(rf, table_bytes):
@@ -527,12 +577,20 @@ def main():
     ap.add_argument('--no-strong', action='store_true', help='N > 1: skip the strong-scaling figures measured after the timed region')
     ap.add_argument('--no-secondary', action='store_true', help='skip the `secondary` shapes measured after the timed region')
     ap.add_argument('--no-kernel-table', action='store_true', help='skip the per-kernel HIP-event table (extra steps after the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the cold figure, the roofline of the dominant kernel (HIP events inside the timed '
+                         'region), latency, sustained run, breakdown, kernel table, secondary shapes, CPU baselines and the N > 1 build probe, '
+                         'weak and strong figures.  Without it a run sets up, warms up, times --steps steps and prints the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB: arrays larger than their share are a fixed, seeded sample of rows, whose indices go to <name>_rows.npy)')
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     n, e_und, h = cfg['n'], cfg['e_und'], cfg['h']
     batch = a.batch or cfg['batch']
     e_dir = 2 * e_und
 
+    assert a.steps > 0 and a.warmup >= 0, '--steps must be positive and --warmup non-negative'
     if a.time_every is None:
         a.time_every = 1 if a.steps <= 50 else 4
     if a.gpus > 1 and 'RANK' not in os.environ:
@@ -586,7 +644,8 @@ def main():
     pairs_planned = batch * buddy_batches if a.api == 'buddy' else batch
     plan = ssa.dist.BatchPlan(a.scaling, world, rank, pairs_planned)
     ei_np = synthetic_graph(n, e_und, a.graph, a.alpha)
-    hub_e, hub_n = hub_stats(ssa, ei_np, n)  # rows (and their in-edges) the row kernels leave to the hub passes
+    # rows (and their in-edges) the row kernels leave to the hub passes: the byte models of --full only
+    hub_e, hub_n = hub_stats(ssa, ei_np, n) if a.full else (None, None)
     links_np = synthetic_links(n, pairs_planned, plan.links_seed)
     if a.api == 'buddy' and a.buddy_negs > 0:  # every source's pairs listed together
         links_np[:, 0] = np.repeat(links_np[::a.buddy_negs, 0], a.buddy_negs)[:pairs_planned]
@@ -606,6 +665,11 @@ def main():
 
     stream = torch.cuda.current_stream(dev)
     phase_marks = []
+    last = {}  # --dump-outputs: the tables and cardinalities of the latest step (only kept when they are to be written)
+
+    def keep(table, cards):
+        if a.dump_outputs:
+            last['table'], last['cards'] = table, cards
 
     def step_build_query(mark=False):
         if mark:
@@ -619,6 +683,7 @@ def main():
             e2.record(stream)
             phase_marks.append((e0, e1, e2))
         gather(f)
+        keep(table, cards)
         return f
 
     elph_state = {}
@@ -637,6 +702,7 @@ def main():
             cards[:, k - 1] = eh.hll_count(table[k]['hll'])
         f = eh.get_subgraph_features(links, table, cards)
         gather(f)
+        keep(table, cards)
         return f
 
     def step_buddy(mark=False):
@@ -645,6 +711,7 @@ def main():
         table, cards = build_tables()
         f = eh.get_subgraph_features(links, table, cards, batch_size=a.buddy_chunk)
         gather(f)
+        keep(table, cards)
         return f
 
     step = {'build_query': step_build_query, 'elph': step_elph, 'buddy': step_buddy}[a.api]
@@ -682,10 +749,12 @@ def main():
     sharded_build = mode['build'] in ('sharded', 'peer')
 
     # the driver's protocol as a fresh process meets it (its --warmup steps, then its --steps), BEFORE anything has settled: printed
-    # as ms_per_step_cold beside the settled figure (VERDICT r4 #7a)
-    for _ in range(a.warmup):
-        step()
-    ms_per_step_cold = 1e3 * timed_region(a.steps) / a.steps
+    # as ms_per_step_cold beside the settled figure (VERDICT r4 #7a); --full only
+    ms_per_step_cold = None
+    if a.full:
+        for _ in range(a.warmup):
+            step()
+        ms_per_step_cold = 1e3 * timed_region(a.steps) / a.steps
     # steady state: clocks, caches, allocator pools and the hub hint of this shape (disclosed as `settle_seconds`; not timed)
     settle_steps = 0
     if a.settle_seconds > 0:
@@ -711,8 +780,10 @@ def main():
     if a.api == 'buddy':  # the link set dwarfs the build: the query is the dominant kernel (92 % of a citation2-size precompute)
         dom_tag = nat.PROF_PAIRS
     # (every 4th launch of it: a timed launch costs its step ~5 us -- the completion signal its events are filled from --, 1 % of the step)
-    lib.ss_profile_sample(a.time_every)
-    lib.ss_profile_enable(0 if os.environ.get('SS_BENCH_EXP_NO_EVENTS') else 1 << dom_tag)
+    # --full only: a plain run times the steps without them
+    if a.full:
+        lib.ss_profile_sample(a.time_every)
+        lib.ss_profile_enable(0 if os.environ.get('SS_BENCH_EXP_NO_EVENTS') else 1 << dom_tag)
     fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -720,14 +791,45 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     dom_ms, dom_n = c_float(), c_int32()
-    lib.ss_profile_read(dom_tag, byref(dom_ms), byref(dom_n))  # the launches of the timed region only
-    lib.ss_profile_enable(0)
-    lib.ss_profile_sample(1)
+    if a.full:
+        lib.ss_profile_read(dom_tag, byref(dom_ms), byref(dom_n))  # the launches of the timed region only
+        lib.ss_profile_enable(0)
+        lib.ss_profile_sample(1)
     if launched:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     ms_per_step = 1e3 * elapsed / a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, feats, last['table'], last['cards'])
+    config_obj = {'workload': f'ogbl-{a.config}-like synthetic {a.graph} graph' + (' (BASELINE configs[1])' if a.config == 'collab' else '') +
+                              ', BUDDY/ELPH hot path: step = build_hash_tables + get_subgraph_features, nothing cached across steps; '
+                              'tables stay in the packed u32 / u8 layout the query reads -- the reference-shaped int64 [N, P] views of '
+                              'the returned dict are lazy and are NOT materialised inside a step' +
+                              ('' if a.api == 'build_query' else f' [api mode: {a.api}' + (f', {pairs_planned} links per build' + (f' ({a.buddy_negs} per source, listed together)' if a.buddy_negs else ' (uniformly random pairs)') + f', get_subgraph_features in chunks of {a.buddy_chunk} (datasets/elph.py:207-208); link sets >= {ssa.hashing.GROUP_LINKS_MIN} pairs are grouped by their first node unless they already are (hashing.GROUP_LINKS_MIN)' if a.api == 'buddy' else '')
+                               + (', last-hop MinHash rows computed for the queried nodes only (hashing.DEFER_TABLE_HOP; SS_DEFER_TABLE_HOP=0: all N rows)'
+                                  if a.api == 'elph' and ssa.hashing.DEFER_TABLE_HOP else '') + ']'),
+                  'num_nodes': n, 'directed_edges': e_dir, 'max_hash_hops': h, 'minhash_num_perm': P, 'hll_p': HLL_P,
+                  'pairs_per_step_per_gpu': links.size(0), 'global_pairs_per_step': pairs_per_step,
+                  'parallelism': (f'edge batches sharded x{world} ({a.scaling} scaling), all_gather of features; sketch table ' +
+                                  ((f'built row-sharded x{world}, every rank writing its rows into all ranks\' tables (peer-write, no exchange step)' if mode['build'] == 'peer' else f'built row-sharded x{world} with an in-place all_gather per hop and sketch') if sharded_build
+                                   else 'replicated (every rank builds it)')),
+                  'hll_tables': eh.tables_id}
+    # the headline: the same keys, with the same meaning, in a plain run and in a --full one
+    headline = {
+        'metric': 'edge-pairs/sec subgraph-feature extraction (build+query)',
+        'value': pairs_per_step * a.steps / elapsed, 'unit': 'pairs/s', 'n_gpus': world, 'steps': a.steps,
+        'warmup': a.warmup, 'settle_seconds': a.settle_seconds, 'settle_steps': settle_steps, 'ms_per_step': ms_per_step,
+        'higher_is_better': True, 'scaling': a.scaling,
+        'rccl_ranks': (dist.get_world_size() if (launched and backend == 'nccl') else None), 'backend': (backend if launched else None),
+        'build': mode['build'], 'vs_baseline': None, 'dtype': 'u32/u8 sketches, f32 estimator', 'data': 'synthetic', 'config': config_obj}
+    if not a.full:
+        eh.check_errors()  # the deferred bounds report of every launch so far (none expected on the synthetic workload)
+        if rank == 0:
+            emit(headline)
+        if launched:
+            dist.destroy_process_group()
+        return
     # one step at a time: the latency of ONE synchronous build + query (BUDDY builds once; the headline above is a throughput -- the
     # host queues steps ahead of the GPU, so launch overhead of step i + 1 hides under the kernels of step i)
     lat = []
@@ -849,27 +951,8 @@ def main():
     achieved = roof.get('achieved_gbs')
     step_bytes = rf.step_bytes_implemented(n, e_dir, P, HLL_P, h, links.size(0), hub_e, hub_n)
     step_ok = a.api == 'build_query' and not sharded_build
-    out = {
-        'metric': 'edge-pairs/sec subgraph-feature extraction (build+query)',
-        'value': pairs_per_step * a.steps / elapsed, 'unit': 'pairs/s', 'n_gpus': world, 'steps': a.steps,
-        'warmup': a.warmup, 'settle_seconds': a.settle_seconds, 'settle_steps': settle_steps, 'ms_per_step': ms_per_step,
-        'ms_per_step_cold': ms_per_step_cold, 'latency_one_step_ms': latency_one_step_ms, 'higher_is_better': True, 'scaling': a.scaling,
-        'rccl_ranks': (dist.get_world_size() if (launched and backend == 'nccl') else None), 'backend': (backend if launched else None),
-        'build': mode['build'], 'build_probe_ms_per_step': build_probe,
-        'vs_baseline': None, 'dtype': 'u32/u8 sketches, f32 estimator', 'data': 'synthetic',
-        'config': {'workload': f'ogbl-{a.config}-like synthetic {a.graph} graph' + (' (BASELINE configs[1])' if a.config == 'collab' else '') +
-                               ', BUDDY/ELPH hot path: step = build_hash_tables + get_subgraph_features, nothing cached across steps; '
-                               'tables stay in the packed u32 / u8 layout the query reads -- the reference-shaped int64 [N, P] views of '
-                               'the returned dict are lazy and are NOT materialised inside a step' +
-                               ('' if a.api == 'build_query' else f' [api mode: {a.api}' + (f', {pairs_planned} links per build' + (f' ({a.buddy_negs} per source, listed together)' if a.buddy_negs else ' (uniformly random pairs)') + f', get_subgraph_features in chunks of {a.buddy_chunk} (datasets/elph.py:207-208); link sets >= {ssa.hashing.GROUP_LINKS_MIN} pairs are grouped by their first node unless they already are (hashing.GROUP_LINKS_MIN)' if a.api == 'buddy' else '')
-                                + (', last-hop MinHash rows computed for the queried nodes only (hashing.DEFER_TABLE_HOP; SS_DEFER_TABLE_HOP=0: all N rows)'
-                                   if a.api == 'elph' and ssa.hashing.DEFER_TABLE_HOP else '') + ']'),
-                   'num_nodes': n, 'directed_edges': e_dir, 'max_hash_hops': h, 'minhash_num_perm': P, 'hll_p': HLL_P,
-                   'pairs_per_step_per_gpu': links.size(0), 'global_pairs_per_step': pairs_per_step,
-                   'parallelism': (f'edge batches sharded x{world} ({a.scaling} scaling), all_gather of features; sketch table ' +
-                                   ((f'built row-sharded x{world}, every rank writing its rows into all ranks\' tables (peer-write, no exchange step)' if mode['build'] == 'peer' else f'built row-sharded x{world} with an in-place all_gather per hop and sketch') if sharded_build
-                                    else 'replicated (every rank builds it)')),
-                   'hll_tables': eh.tables_id},
+    out = dict(headline, ms_per_step_cold=ms_per_step_cold, latency_one_step_ms=latency_one_step_ms, build_probe_ms_per_step=build_probe)
+    out.update({
         'roofline': {'kernel': roof_kernel + ('' if h > 1 else ' (not launched at h=1)') +
                                (' [elph api mode launches it per sketch: the same kernel and bytes]' if a.api == 'elph' and dom_tag != nat.PROF_FUSED else ''),
                      'bound': 'hbm', 'achieved': achieved, 'peak': rf.HBM_PEAK_GBS, 'unit': 'GB/s',
@@ -889,7 +972,7 @@ def main():
                      'note': 'resident = infinity-cache: the gathered table fits the 256 MiB Infinity Cache, so `achieved` is a fabric + cache '
                              'rate (`gather_probe_gbs`: what random row gathers from a table of this size reach in a micro-benchmark; ~6.3 TB/s '
                              'is what HBM alone streams); mixed: the cache holds at least half of it; hbm: less -- see secondary_summary.citation2_uniform'},
-    }
+    })
     if step_ok:
         out['step_roofline'] = {'bound': 'hbm', 'bytes_per_step': step_bytes, 'ms_per_step': ms_per_step,
                                 'achieved': step_bytes / (ms_per_step * 1e-3) / 1e9, 'peak': rf.HBM_PEAK_GBS, 'unit': 'GB/s',

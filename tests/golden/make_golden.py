@@ -429,6 +429,25 @@ def make_g15():
     print('G15 written:', sorted(k for k in g if k.startswith('sign_')))
 
 
+def make_g16():
+    """G16: what the reference's model and dataset modules take from `src.hashing` -- the names they import from it, the methods they
+    call on their `self.elph_hashes` and the number of arguments of each `ElphHashes(...)` they construct.  Read with ast, nothing
+    imported; test_reference_modules_import_the_shim checks the shipped shim against it without the reference at hand."""
+    import ast
+    src = os.path.dirname(REF)
+    g = {}
+    for key, rel in (('models_elph', os.path.join('models', 'elph.py')), ('datasets_elph', os.path.join('datasets', 'elph.py'))):
+        with open(os.path.join(src, rel)) as fh:
+            nodes = list(ast.walk(ast.parse(fh.read())))
+        g[f'{key}_imports'] = np.asarray(sorted({a.name for n in nodes if isinstance(n, ast.ImportFrom) and n.module == 'src.hashing'
+                                                 for a in n.names}))
+        g[f'{key}_calls'] = np.asarray(sorted({n.func.attr for n in nodes if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute)
+                                               and isinstance(n.func.value, ast.Attribute) and n.func.value.attr == 'elph_hashes'}))
+        g[f'{key}_constructor_arity'] = np.asarray([len(n.args) + len(n.keywords) for n in nodes if isinstance(n, ast.Call)
+                                                    and isinstance(n.func, ast.Name) and n.func.id == 'ElphHashes'], dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, 'g16_reference_hashing_use.npz'), **g)
+
+
 def args(h=2, p=8, P=128, floor_sf=False, use_zero_one=True):
     return Namespace(max_hash_hops=h, hll_p=p, minhash_num_perm=P, floor_sf=floor_sf, use_zero_one=use_zero_one)
 
@@ -657,9 +676,12 @@ if __name__ == '__main__':
         make_g14()
     elif '--only-g15' in sys.argv:
         make_g15()
+    elif '--only-g16' in sys.argv:
+        make_g16()
     else:
         main()
         make_g10()
         make_g12()
         make_g14()
         make_g15()
+        make_g16()

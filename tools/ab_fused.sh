@@ -1,6 +1,6 @@
 #!/bin/bash
 # (GPU box) fused-stage variants: step time + the fused kernel's mean launch time on the bench graph, then citation2 / ppa size
-run() { python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary --sustain-seconds 0 "$@" 2>/dev/null | tail -1 | python -c "
+run() { python "$(dirname "$0")/../bench.py" --full --no-cpu-baseline --no-secondary --sustain-seconds 0 "$@" 2>/dev/null | tail -1 | python -c "
 import sys, json, os
 d = json.loads(sys.stdin.read())
 print('   ', 'wg/cu', os.environ.get('SS_FUSED_WG_PER_CU', 'default'), '$*', 'step', round(d['ms_per_step'], 4), 'fused', round(d['kernels']['fused_first_hop_hll_hop']['mean_launch_ms'] * 1e3, 1), 'us')"; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # (GPU box) query-kernel variants: the bench step's pair kernel span, the BUDDY precompute at collab size (h = 2) and a citation2-size (h = 3) link set
-run() { python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary --sustain-seconds 0 "$@" 2>/dev/null | tail -1 | python -c "
+run() { python "$(dirname "$0")/../bench.py" --full --no-cpu-baseline --no-secondary --sustain-seconds 0 "$@" 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d.get('kernels', {}).get('pair_features', {})

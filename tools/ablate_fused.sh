@@ -18,7 +18,7 @@ if [ "$1" = build ]; then
 fi
 for cfg in collab citation2; do
 for m in $MASKS; do
-  SS_LIB=$PWD/tools/ablate_lib/libss_ab$m.so python bench.py --no-cpu-baseline --no-secondary --sustain-seconds 0 --settle-seconds 0.5 --config $cfg --steps $([ $cfg = collab ] && echo 50 || echo 5) --warmup 3 2>/dev/null | tail -1 | python -c "
+  SS_LIB=$PWD/tools/ablate_lib/libss_ab$m.so python bench.py --full --no-cpu-baseline --no-secondary --sustain-seconds 0 --settle-seconds 0.5 --config $cfg --steps $([ $cfg = collab ] && echo 50 || echo 5) --warmup 3 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels']['fused_first_hop_hll_hop']

@@ -3,7 +3,7 @@
 # HIP-event times (bench.py kernel table): hub units hosted by the row launches (default) against launches of their own
 # (SS_HUB_LAUNCHES=1)
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --graph $3 --alpha $1 --no-secondary --no-cpu-baseline --sustain-seconds 0 2>/dev/null | python -c "
+run() { python bench.py --full --graph $3 --alpha $1 --no-secondary --no-cpu-baseline --sustain-seconds 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 print('$2 $3 alpha=$1', round(d['ms_per_step'],4), {n:round(v['mean_launch_ms']*1e3,1) for n,v in k.items() if isinstance(v,dict)})"; }

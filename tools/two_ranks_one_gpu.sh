@@ -5,4 +5,4 @@
 # host); what it checks is that every collective of the N > 1 path is entered by every rank with matching shapes.
 cd $GRAFT_REPO_ROOT
 SS_BENCH_SINGLE_DEVICE=1 SS_BENCH_BACKEND=gloo python \
-  bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --sustain-seconds 0 "$@"
+  bench.py --gpus 2 --full --steps 5 --warmup 2 --no-cpu-baseline --sustain-seconds 0 "$@"
