@@ -272,6 +272,48 @@ int ss_pair_features_grouped(const int64_t *links, const int32_t *order, int64_t
 int ss_common_neighbour_scores(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
                                int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream);
 
+/* Personalised PageRank of many sources at once -- the fourth link heuristic (reference heuristics.py:74-113: PPR, one
+ * fast_pagerank.pagerank_power(A, p, personalize=e_src, tol) power iteration per distinct source).  With r = row sums of A,
+ * n = N, s_j = n e_src_j and z_u = ((1-p)[r_u != 0] + [r_u == 0]) / n, every source column j iterates
+ *     x <- W x + s_j (z . x),   W[v, u] = (p A[u, v]) (1 / r_u)  (rows with r_u = 0 drop out),   x_0 = s_j
+ * until ||x - x_old||_2 <= tol or max_iter steps, and its result is x / sum(x).  fp64 throughout; bit-identical for a source
+ * whatever S or the column it occupies (every sum runs in an order fixed by the graph).
+ *   ss_ppr_graph: device CSR of A^T (row v lists the u with A[u, v] != 0) with the weights w above, z[N], and the rows
+ *   holding more than SS_PPR_SEGMENT entries ("hubs", ascending) cut into segments of SS_PPR_SEGMENT entries:
+ *   hub_seg[h] .. hub_seg[h + 1] are the segments of hub_rows[h], seg_hub[s] the hub segment s belongs to.
+ *   Workspace (iterates, per-block partials, per-column state): ss_ppr_workspace_bytes(N, S, n_hubs, n_segments) device
+ *   bytes, 0 = unsupported size; S <= SS_PPR_MAX_COLUMNS.  One batch:
+ *     ss_ppr_begin    x_0 of the S sources (device int64[S]); an id outside [0, N) sets err_flag (nullable)
+ *     ss_ppr_iterate  step `iteration` (1, 2, ...) of every column still active; a column that stops keeps its iterate
+ *     ss_ppr_status   iters (device int32[S], nullable) = steps taken, n_active (device int32, nullable) = columns left
+ *     ss_ppr_scores   out[l] = (float)(x_c[dst[l]] / sum x_c), c = link_col[l] -- the reference's ppr[dst]
+ *     ss_ppr_vectors  out [S, N] fp64 = the normalised vectors */
+#define SS_PPR_SEGMENT 256
+#define SS_PPR_MAX_COLUMNS 4096
+typedef struct ss_ppr_graph {
+    const int64_t *rowptr;    /* int64[N + 1] */
+    const int32_t *col;       /* int32[nnz] */
+    const double *w;          /* double[nnz] */
+    const double *z;          /* double[N] */
+    int64_t num_nodes;
+    int64_t nnz;
+    const int32_t *hub_rows;  /* int32[n_hubs] */
+    const int32_t *hub_seg;   /* int32[n_hubs + 1] */
+    const int32_t *seg_hub;   /* int32[n_segments] */
+    int64_t n_hubs;
+    int64_t n_segments;
+} ss_ppr_graph;
+size_t ss_ppr_workspace_bytes(int64_t N, int32_t S, int64_t n_hubs, int64_t n_segments);
+int ss_ppr_begin(const ss_ppr_graph *g, const int64_t *sources, int32_t S, double tol, void *workspace, size_t workspace_bytes,
+                 int32_t *err_flag, void *stream);
+int ss_ppr_iterate(const ss_ppr_graph *g, int32_t S, int32_t iteration, int32_t max_iter, double tol, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int ss_ppr_status(const ss_ppr_graph *g, int32_t S, const void *workspace, size_t workspace_bytes, int32_t *iters, int32_t *n_active,
+                  void *stream);
+int ss_ppr_scores(const ss_ppr_graph *g, int32_t S, const int64_t *dst, const int32_t *link_col, int64_t L, const void *workspace,
+                  size_t workspace_bytes, float *out, int32_t *err_flag, void *stream);
+int ss_ppr_vectors(const ss_ppr_graph *g, int32_t S, const void *workspace, size_t workspace_bytes, double *out, void *stream);
+
 /* out = A * x for a row-grouped CSR with fp32 values -- the node-feature propagation of
  * HashDataset._generate_sign_features (reference datasets/elph.py:87-110: gcn_norm, then torch_sparse.spmm = multiply
  * and scatter-add in edge order).  Every output element is accumulated by one lane in CSR order, product and sum rounded

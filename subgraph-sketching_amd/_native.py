@@ -5,7 +5,7 @@ object has not been built (run `python __graft_entry__.py` or `subgraph-sketchin
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SS_LIB: measurement hook -- tools/ablate_fused.sh loads deliberately incomplete builds of the library to time what is left)
@@ -35,6 +35,13 @@ class CsrGraphStruct(ctypes.Structure):
                 ('mirror_cards', c_void_p * 7), ('hub_report', c_void_p), ('report_hub_count', c_void_p), ('report_mega_count', c_void_p)]
 
 
+class PprGraphStruct(ctypes.Structure):
+    """mirror of `struct ss_ppr_graph`"""
+    _fields_ = [('rowptr', c_void_p), ('col', c_void_p), ('w', c_void_p), ('z', c_void_p), ('num_nodes', c_int64), ('nnz', c_int64),
+                ('hub_rows', c_void_p), ('hub_seg', c_void_p), ('seg_hub', c_void_p), ('n_hubs', c_int64), ('n_segments', c_int64)]
+
+
+PPR_SEGMENT, PPR_MAX_COLUMNS = 256, 4096  # SS_PPR_SEGMENT / SS_PPR_MAX_COLUMNS of include/subgraph_sketch.h
 ABI_VERSION = 129  # ss_version() of the library this module's struct mirrors and signatures describe
 PROF_MINHASH_HOP, PROF_HLL_HOP, PROF_FIRST_HOP_MH, PROF_FIRST_HOP_HLL, PROF_PAIRS, PROF_CSR, PROF_HUB, PROF_FUSED, PROF_MINHASH_ROWS = range(9)  # SS_PROF_* tags
 MEGA_DESC_WORDS = 8  # SS_MEGA_DESC_WORDS
@@ -77,6 +84,13 @@ SIGNATURES = {
                                                   c_void_p, c_void_p]),
     'ss_common_neighbour_scores': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                              c_void_p]),
+    'ss_ppr_workspace_bytes': (c_size_t, [c_int64, c_int32, c_int64, c_int64]),
+    'ss_ppr_begin': (c_int32, [POINTER(PprGraphStruct), c_void_p, c_int32, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'ss_ppr_iterate': (c_int32, [POINTER(PprGraphStruct), c_int32, c_int32, c_int32, c_double, c_void_p, c_size_t, c_void_p]),
+    'ss_ppr_status': (c_int32, [POINTER(PprGraphStruct), c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'ss_ppr_scores': (c_int32, [POINTER(PprGraphStruct), c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                c_void_p]),
+    'ss_ppr_vectors': (c_int32, [POINTER(PprGraphStruct), c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
     'ss_spmm_csr': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'ss_csr_group_ids': (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_csr_sort_workspace_bytes': (c_size_t, [c_int64]),

@@ -56,3 +56,12 @@ REUSE_CSR_BY_CONTENT = os.environ.get('SS_REUSE_CSR', '1') != '0'
 # and batched tail walks it wins there too (3.70 against 3.92 ms), so there is no cap any more.  SS_FUSED_STAGE_MAX_MB:
 # measurement hook
 FUSED_STAGE_MAX_TABLE_BYTES = int(os.environ.get('SS_FUSED_STAGE_MAX_MB', str(1 << 30))) << 20
+
+# source columns per personalised-PageRank batch (heuristics.PPR / personalized_pagerank): the iterate is fp64 [N, S] and every
+# step gathers one S * 8-byte row per in-edge, so S = 64 makes each wavefront load of it a 512-byte row (the MinHash table hop's
+# access pattern); at ogbl-collab size the two iterates (2 x 120 MB) stay in the 256 MiB Infinity Cache.  Lowered automatically
+# when free device memory is short.  Results are bit-identical for every S.
+PPR_COLUMNS = int(os.environ.get('SS_PPR_COLUMNS', '64'))
+# the active-column count is read back (a host synchronisation) every this many iterations: a batch ends at most this many
+# (then empty) launches after its last column stopped instead of at max_iter
+PPR_CHECK_EVERY = int(os.environ.get('SS_PPR_CHECK_EVERY', '4'))
