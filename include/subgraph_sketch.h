@@ -314,6 +314,25 @@ int ss_ppr_scores(const ss_ppr_graph *g, int32_t S, const int64_t *dst, const in
                   size_t workspace_bytes, float *out, int32_t *err_flag, void *stream);
 int ss_ppr_vectors(const ss_ppr_graph *g, int32_t S, const void *workspace, size_t workspace_bytes, double *out, void *stream);
 
+/* One-vs-all link candidates: the set-intersection estimate I[k1, k2] = J * U (reference hashing.py:167-189) of S sources
+ * against every node, as ranking keys for a top-k selection -- the operation the reference's sample_hard_negatives
+ * (src/data.py:262-304) sets out to do and full-ranking evaluation / candidate generation need.
+ *   ss_topk_scan     keys [S, N] int64: keys[s][v] ranks v for sources[s] (device int64[S], torch-style negative ids wrapped;
+ *                    an id outside [-N, N) sets err_flag (nullable) and its row is all sentinels).  mh_src / hll_src: the
+ *                    hop-k1 tables, mh_cand / hll_cand: the hop-k2 tables (packed [N, P] / [N, 2^p]).  The score is
+ *                    bit-identical to ss_pair_features' dbg_inter[(k1, k2)] for the pair (u, v) (-0 becomes +0).
+ *                    Key = (monotone score bits as signed int32) << 32 | (0xFFFFFFFF - v): signed order == (score desc, id
+ *                    asc); v == u holds INT64_MIN, below every real key.  N < 2^32 - 1.
+ *   ss_topk_exclude  INT64_MIN over keys[s][v] for every v in row u of a CSR (rowptr int64[N + 1], col int32) -- the CSR of
+ *                    the exclude list flipped (ss_csr_build lists row i = {j : j -> i}), so row u = {v : u -> v}.
+ * Workspace: the key buffer, ss_topk_workspace_bytes(N, S) device bytes (0 = unsupported size). */
+size_t ss_topk_workspace_bytes(int64_t N, int32_t S);
+int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const uint32_t *mh_src, const uint8_t *hll_src, const uint32_t *mh_cand,
+                 const uint8_t *hll_cand, int32_t P, const ss_hll_params *prm, int64_t *keys, size_t keys_bytes, int32_t *err_flag,
+                 void *stream);
+int ss_topk_exclude(const int64_t *sources, int32_t S, int64_t N, const int64_t *rowptr, const int32_t *col, int64_t *keys,
+                    size_t keys_bytes, void *stream);
+
 /* out = A * x for a row-grouped CSR with fp32 values -- the node-feature propagation of
  * HashDataset._generate_sign_features (reference datasets/elph.py:87-110: gcn_norm, then torch_sparse.spmm = multiply
  * and scatter-add in edge order).  Every output element is accumulated by one lane in CSR order, product and sum rounded

@@ -91,6 +91,10 @@ SIGNATURES = {
     'ss_ppr_scores': (c_int32, [POINTER(PprGraphStruct), c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
                                 c_void_p]),
     'ss_ppr_vectors': (c_int32, [POINTER(PprGraphStruct), c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'ss_topk_workspace_bytes': (c_size_t, [c_int64, c_int32]),
+    'ss_topk_scan': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(HllParams), c_void_p,
+                               c_size_t, c_void_p, c_void_p]),
+    'ss_topk_exclude': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_spmm_csr': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'ss_csr_group_ids': (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_csr_sort_workspace_bytes': (c_size_t, [c_int64]),

@@ -16,7 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "ss_common.hpp"
+#include "ss_pair_math.hpp"
 
 namespace ss {
 
@@ -26,64 +26,6 @@ struct PairTables {
     const uint32_t *mh[SS_MAX_HOPS];
     const uint8_t *hll[SS_MAX_HOPS];
 };
-
-// (measured and rejected in round 3: counting equal dwords as 4 - sum(min(a ^ b, 1)) instead of v_cmp_eq_u32 + v_addc_co_u32 -- hipcc
-// puts an `s_nop 1` behind each of the 72 compares of a pair at h = 3, gfx950 wanting two wait states between a VALU write of VCC
-// and its VALU read -- removes 59 of 102 s_nops but adds 47 VALU instructions: level on cache-resident tables, 3.5 % SLOWER on
-// citation2-size tables (3 713 against 3 580 us for 4 M pairs): other wavefronts fill the wait states, nobody fills extra instructions)
-__device__ __forceinline__ int eq4(u32x4 a, u32x4 b)
-{
-    return (int)(a.x == b.x) + (int)(a.y == b.y) + (int)(a.z == b.z) + (int)(a.w == b.w);
-}
-
-// generic path: union of two 16-register chunks -> non-zero count and harmonic sum
-__device__ __forceinline__ void union_stats(u32x4 a, u32x4 b, int &nonzero, float &hsum)
-{
-    const u32x4 m = bytemax16(a, b);
-    hll_dword_stats(m.x, nonzero, hsum);
-    hll_dword_stats(m.y, nonzero, hsum);
-    hll_dword_stats(m.z, nonzero, hsum);
-    hll_dword_stats(m.w, nonzero, hsum);
-}
-
-// fast path: a 16-register HLL chunk pre-digested once per row so that each of the h^2 unions costs
-// 4 instructions per dword: bf16 patterns of 2^-r (even / odd registers; max of registers == unsigned min of
-// patterns) and a 16-bit "register is zero" mask (union register zero <=> zero in both rows).
-struct HllChunk {
-    uint32_t pe[4], po[4];
-    uint32_t zero_mask;
-};
-
-__device__ __forceinline__ HllChunk digest_chunk(u32x4 x)
-{
-    HllChunk c;
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    uint32_t nzbits = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        c.pe[d] = regs_even_to_bf16(w[d]);
-        c.po[d] = regs_odd_to_bf16(w[d]);
-        nzbits |= nonzero_byte_flags(w[d]) >> (7 - d);  // flags live in bits 7,15,23,31 -> bits d, 8+d, 16+d, 24+d
-    }
-    c.zero_mask = ~nzbits & 0x0F0F0F0Fu;
-    return c;
-}
-
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    u16x2 x = __builtin_bit_cast(u16x2, a), y = __builtin_bit_cast(u16x2, b);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(x, y));
-}
-
-__device__ __forceinline__ void union_stats_digested(const HllChunk &a, const HllChunk &b, int &zeros, float &hsum)
-{
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        hsum = dot2_ones(pk_min_u16(a.pe[d], b.pe[d]), hsum);
-        hsum = dot2_ones(pk_min_u16(a.po[d], b.po[d]), hsum);
-    }
-    zeros += __builtin_popcount(a.zero_mask & b.zero_mask);
-}
 
 // feature algebra of get_subgraph_features (hashing.py:276-320); I is indexed [k1-1][k2-1].
 template <int H>
@@ -287,10 +229,7 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
     }
     float my_I = 0.0f;
     const int my_match = (int)((uint32_t)my_mz >> 20), my_zeros = my_mz & 0xFFFFF;  // P <= 2048: the packed word uses all 32 bits
-    if (l < NC) {
-        const float jac = (float)my_match / (float)P;
-        my_I = jac * hll_estimate(est, my_zeros, my_hs);
-    }
+    if (l < NC) my_I = intersection_estimate(est, my_match, my_zeros, my_hs, P);
     const int row_base = (threadIdx.x & (kWave - 1)) & ~(kRow - 1);
     float I[H][H];
 #pragma unroll
@@ -479,10 +418,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
                 my_hs = (l == c) ? hs[c] : my_hs;
             }
             float my_I = 0.0f;
-            if (l < NC) {
-                const float jac = (float)(int)((uint32_t)my_mz >> 20) / (float)TP;
-                my_I = jac * hll_estimate(est, my_mz & 0xFFFFF, my_hs);
-            }
+            if (l < NC) my_I = intersection_estimate(est, (int)((uint32_t)my_mz >> 20), my_mz & 0xFFFFF, my_hs, TP);
             float I[H][H];
 #pragma unroll
             for (int c = 0; c < NC; ++c) I[c / H][c % H] = __shfl(my_I, row_base + c);

@@ -22,6 +22,31 @@ LABEL_LOOKUP = {1: {0: (1, 1), 1: (0, 1), 2: (1, 0)},
                     9: (0, 1), 10: (1, 0), 11: (0, 2), 12: (2, 0), 13: (0, 3), 14: (3, 0)}}
 
 
+# ---- one-vs-all link candidates (ElphHashes.topk_candidates, csrc/ss_topk.hip) -----------------------------------------------------
+TOPK_SENTINEL = -(1 << 63)  # the key of an ineligible candidate (v == u, excluded, out-of-range source): below every real key
+_TOPK_KEY_BYTES = 1 << 31   # bound on one block's key buffer [sources, N] int64 (rows do not depend on it; not a user knob)
+
+
+def _decode_topk_keys(keys):
+    """(ids int64, scores float32) of ss_topk_scan keys, on keys.device: high word = monotone bits of the score as a signed int32,
+    low word = 0xFFFFFFFF - id; the sentinel decodes to (-1, -inf)"""
+    hi, lo = keys >> 32, keys & 0xFFFFFFFF
+    m = hi + (1 << 31)                                              # the score's monotone bits as an unsigned word
+    bits = torch.where(m >= (1 << 31), m - (1 << 31), 0xFFFFFFFF - m)  # its IEEE bits
+    bits = bits - ((bits >> 31) << 32)                              # as a signed int32 value
+    scores = bits.to(torch.int32).view(torch.float32)
+    pad = keys == TOPK_SENTINEL
+    return (0xFFFFFFFF - lo).masked_fill(pad, -1), scores.masked_fill(pad, float('-inf'))
+
+
+def _table_shape(hash_table, hop):
+    """(N, P) of a hop's MinHash table without touching a device"""
+    entry = hash_table[hop]
+    t = entry.mh_u32 if isinstance(entry, HopSketch) else entry['minhash']
+    if t.dim() != 2:
+        raise ValueError(f'hop {hop} MinHash table must be 2-D, got {tuple(t.shape)}')
+    return int(t.shape[0]), int(t.shape[1])
+
 class ElphHashes(object):
     """class to store hashes and retrieve subgraph features (mirror of reference hashing.py:48-323)"""
     HUB_HINT_SHAPES = 256  # graph shapes that get a hub hint word (one pinned int32 each, kept for the engine's lifetime)
@@ -507,6 +532,85 @@ class ElphHashes(object):
         inter = dbg['inter'].to(edge_list.device)
         return {(k1, k2): inter[:, k1 - 1, k2 - 1].contiguous()
                 for k1 in range(1, self.max_hops + 1) for k2 in range(1, self.max_hops + 1)}
+
+    def topk_candidates(self, sources, hash_table, k, hops=(1, 1), exclude=None):
+        """the k best link partners of every source by the engine's set-intersection estimate -- what the reference's
+        sample_hard_negatives (src/data.py:262-304, unfinished) ranks by, and what full-ranking evaluation and candidate generation
+        need.  The score of candidate v for source u is I[k1, k2] = J * U of u's hop-k1 and v's hop-k2 sketches (hashing.py:167-189),
+        bit-identical to _get_intersections([(u, v)])[(k1, k2)] (-0.0 comes back as +0.0).
+        @param sources: int64 [S] node ids (torch-style negative ids allowed), CPU or device
+        @param hash_table: anything get_subgraph_features accepts
+        @param k: 1 <= k <= N;  @param hops: (k1, k2), 1 <= k1, k2 <= max_hash_hops
+        @param exclude: optional int64 [2, E] edge_index: every v with an edge u -> v in it is no candidate of u (nor is u itself)
+        @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows
+                 with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only."""
+        try:
+            k1, k2 = (int(x) for x in hops)
+        except (TypeError, ValueError):
+            raise ValueError(f'hops must be a pair (k1, k2), got {hops!r}')
+        if not (1 <= k1 <= self.max_hops and 1 <= k2 <= self.max_hops):
+            raise ValueError(f'hops must lie in [1, {self.max_hops}], got {(k1, k2)}')
+        src = torch.as_tensor(sources)
+        if src.dim() != 1 or src.dtype.is_floating_point or src.dtype == torch.bool:
+            raise ValueError(f'sources must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
+        N, P = _table_shape(hash_table, 1)
+        _check_sizes(P, self.p)
+        k = int(k)
+        if not 1 <= k <= N:
+            raise ValueError(f'k must lie in [1, {N}], got {k}')
+        ex = None
+        if exclude is not None:
+            ex = torch.as_tensor(exclude)
+            if ex.dim() != 2 or ex.size(0) != 2 or ex.dtype.is_floating_point or ex.dtype == torch.bool:
+                raise ValueError(f'exclude must be an integer [2, E] edge_index, got {ex.dtype} {tuple(ex.shape)}')
+        # CPU ids are checked here, as the reference's CPU indexing would; device ids are reported late (strict_bounds)
+        if not src.is_cuda and src.numel() and (int(src.min()) < -N or int(src.max()) >= N):
+            raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
+        if ex is not None and not ex.is_cuda and ex.numel() and (int(ex.min()) < -N or int(ex.max()) >= N):
+            raise IndexError(f'exclude refers to nodes outside [-{N}, {N})')
+        home = src.device
+        S = src.numel()
+        first = hash_table.get(1) if hasattr(hash_table, 'get') else None
+        device = _compute_device(src, first.mh_u32 if isinstance(first, HopSketch) else None)
+        mh, hll, N, P = self._resolve_tables(hash_table, device)
+        params = self._params(device)
+        lk = src.to(device=device, dtype=torch.int64).contiguous()
+        strict, err = self._bounds(device, f'topk_candidates({S} sources, num_nodes={N})')
+        csr = None
+        if ex is not None:
+            ex = ex.to(device=device, dtype=torch.int64)
+            ex = torch.where(ex < 0, ex + N, ex)  # (ids below -N stay negative: out of range)
+            csr = build_csr(ex.flip(0), N, device, check=strict, err_flag=None if strict else err)  # row u = {v : u -> v}
+        if strict:
+            err = _error_flag(device)
+        ids = torch.empty((S, k), dtype=torch.int64, device=device)
+        scores = torch.empty((S, k), dtype=torch.float32, device=device)
+        blk = max(1, min(S, _TOPK_KEY_BYTES // (8 * N)))
+        lib = _native.lib()
+        if S:
+            keys = torch.empty((blk, N), dtype=torch.int64, device=device)
+            nbytes = keys.numel() * 8
+        for b0 in range(0, S, blk):
+            nb = min(blk, S - b0)
+            sb = c_void_p(lk.data_ptr() + 8 * b0)
+            with _Span('topk_scan', device):
+                _native.check(lib.ss_topk_scan(sb, nb, N, _ptr(mh[k1 - 1]), _ptr(hll[k1 - 1]), _ptr(mh[k2 - 1]), _ptr(hll[k2 - 1]), P,
+                                               byref(params.struct), _ptr(keys), nbytes, _ptr(err), _stream(device)), 'ss_topk_scan')
+            if csr is not None:
+                with _Span('topk_exclude', device):
+                    _native.check(lib.ss_topk_exclude(sb, nb, N, _ptr(csr.rowptr), _ptr(csr.col), _ptr(keys), nbytes, _stream(device)),
+                                  'ss_topk_exclude')
+            with _Span('topk_select', device):
+                top = torch.topk(keys[:nb], k, dim=1, largest=True, sorted=True).values  # unique keys: no ties, deterministic
+                ids[b0:b0 + nb], scores[b0:b0 + nb] = _decode_topk_keys(top)
+        if strict and S and _take_error(device):
+            raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
+        if home == device:
+            return ids, scores
+        ids, scores = ids.to(home), scores.to(home)
+        if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
+            self._deferred.raise_if_set()
+        return ids, scores
 
     def get_hashval(self, x):
         return x.hashvals
