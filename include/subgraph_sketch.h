@@ -264,13 +264,20 @@ int ss_pair_features_grouped(const int64_t *links, const int32_t *order, int64_t
 /* Weighted common-neighbour scores of node pairs -- the other per-link precompute of HashDataset.__init__ (SURVEY 8(f)
  * row N4; reference datasets/elph.py:76-77,314 calling heuristics.py:51-70 RA; CN heuristics.py:10-27 and AA :30-48
  * are the same sum with another multiplier):
- *     out[q] = (float) sum_w A[u, w] * (A[v, w] * mult[w]),   (u, v) = links[q], fp64 inside like scipy.
+ *     out[q] = (float) sum_w A[u, w] * (A[v, w] * mult[w]),   (u, v) = links[q],
+ *   in fp64 (what scipy does for int, bool and float64 matrices): products and sum in fp64, one float32 rounding.
  *   rowptr / col / val: device CSR of A (int64[N+1], int32[nnz] SORTED and duplicate-free inside a row -- what
  *   scipy.sparse.csr_matrix((w, (row, col))) holds after sum_duplicates/sort_indices --, double[nnz] or NULL = all 1);
  *   mult: device double[N] or NULL (= 1: common neighbours).  links: device int64[B, 2]; out: device fp32[B].
  *   err_flag (nullable): set to 1 when a link refers to a node outside [0, N) (its score is written as 0). */
 int ss_common_neighbour_scores(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
                                int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream);
+/* The same scores in scipy's float32 arithmetic (float32 matrices): val and mult hold float32 values (exact in double); each
+ * term is f32(a_u * a_v) (mult NULL) or f32(a_u * f32(a_v * mult[w])), terms equal to 0 are dropped, and the m terms of a pair,
+ * in ascending column order, are added as t[0] + pairwise(t[1:]) in numpy's float32 pairwise order (CSR row sum through
+ * np.add.reduceat): bit-identical to the reference on float32 matrices.  Arguments and errors as above. */
+int ss_common_neighbour_scores_f32(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
+                                   int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream);
 
 /* Personalised PageRank of many sources at once -- the fourth link heuristic (reference heuristics.py:74-113: PPR, one
  * fast_pagerank.pagerank_power(A, p, personalize=e_src, tol) power iteration per distinct source).  With r = row sums of A,

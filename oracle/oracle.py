@@ -204,7 +204,8 @@ def append_degree_normalised(x, links, degrees):
 
 
 def common_neighbour_scores(A, links, kind):
-    """heuristics.py:10-70: kind in {'CN', 'AA', 'RA'}; A scipy sparse (any format), links [L, 2] -> float32 [L]"""
+    """heuristics.py:10-70: kind in {'CN', 'AA', 'RA'}; A scipy sparse (any format), links [L, 2] -> float32 [L].  A float32
+    matrix is scored in scipy's float32 arithmetic and summation order, every other dtype in fp64 (so_common_neighbour_scores*)"""
     A = A.tocsr().copy()
     A.sum_duplicates()
     rowptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
@@ -220,8 +221,8 @@ def common_neighbour_scores(A, links, kind):
         mult = np.ascontiguousarray(mult)
     links = np.ascontiguousarray(np.asarray(links, dtype=np.int64).reshape(-1, 2))
     out = np.empty(links.shape[0], dtype=np.float32)
-    lib().so_common_neighbour_scores(_p(rowptr), _p(col), _p(val), _p(mult), c_int64(A.shape[0]), _p(links), c_int64(links.shape[0]),
-                                     _p(out))
+    fn = lib().so_common_neighbour_scores_f32 if A.dtype == np.float32 else lib().so_common_neighbour_scores
+    fn(_p(rowptr), _p(col), _p(val), _p(mult), c_int64(A.shape[0]), _p(links), c_int64(links.shape[0]), _p(out))
     return out
 
 

@@ -377,6 +377,62 @@ void so_common_neighbour_scores(const int64_t *rowptr, const int32_t *col, const
     }
 }
 
+/* numpy's float32 pairwise sum (the add loop of np.add.reduce / reduceat): fewer than 8 terms in order from -0.0; up to 128
+ * in 8 strided accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the rest in order; above 128 split at n/2
+ * rounded down to a multiple of 8. */
+static float pairwise_sum_f32(const float *a, int64_t n)
+{
+    if (n < 8) {
+        float res = -0.0f;
+        for (int64_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        float r[8];
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        int64_t i;
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+        float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return pairwise_sum_f32(a, n2) + pairwise_sum_f32(a + n2, n - n2);
+}
+
+/* The same scores in scipy's float32 arithmetic (float32 matrices: A.multiply, the element-wise product and the CSR row sum all
+ * stay float32): val / mult hold float32 values; term = f32(a_src * a_dst) or f32(a_src * f32(a_dst * mult[w])), zero terms
+ * dropped (scipy does not store them), score = t[0] + pairwise(t[1:]) over the terms in ascending column order -- the row sum
+ * np.add.reduceat(data, indptr) starts from the row's first element and adds the pairwise sum of the rest. */
+void so_common_neighbour_scores_f32(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult, int64_t N,
+                                    const int64_t *links, int64_t B, float *out)
+{
+    int64_t cap = 0;
+    for (int64_t r = 0; r < N; ++r) cap = rowptr[r + 1] - rowptr[r] > cap ? rowptr[r + 1] - rowptr[r] : cap;
+    float *t = (float *)malloc((size_t)(cap > 0 ? cap : 1) * sizeof(float));
+    for (int64_t q = 0; q < B; ++q) {
+        const int64_t u = wrap_index(links[2 * q], N), v = wrap_index(links[2 * q + 1], N);
+        int64_t i = rowptr[u], j = rowptr[v], m = 0;
+        const int64_t ie = rowptr[u + 1], je = rowptr[v + 1];
+        while (i < ie && j < je) {
+            if (col[i] < col[j]) ++i;
+            else if (col[i] > col[j]) ++j;
+            else {
+                const float a_src = val ? (float)val[i] : 1.0f, a_dst = val ? (float)val[j] : 1.0f;
+                const float scaled = mult ? a_dst * (float)mult[col[i]] : a_dst;
+                const float term = a_src * scaled;
+                if (term != 0.0f) t[m++] = term;
+                ++i;
+                ++j;
+            }
+        }
+        out[q] = m == 0 ? 0.0f : t[0] + pairwise_sum_f32(t + 1, m - 1);
+    }
+    free(t);
+}
+
 /* torch_sparse.spmm as used by datasets/elph.py:87-110: out[row[e]] += val[e] * x[col[e]] for
  * e = 0..E-1 in edge order, fp32 product and fp32 add rounded separately (sequential CPU scatter_add). */
 void so_spmm_coo(const int64_t *row, const int64_t *col, const float *val, int64_t E, int64_t N, const float *x, int32_t F, float *out)

@@ -84,6 +84,8 @@ SIGNATURES = {
                                                   c_void_p, c_void_p]),
     'ss_common_neighbour_scores': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                              c_void_p]),
+    'ss_common_neighbour_scores_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                                 c_void_p, c_void_p]),
     'ss_ppr_workspace_bytes': (c_size_t, [c_int64, c_int32, c_int64, c_int64]),
     'ss_ppr_begin': (c_int32, [POINTER(PprGraphStruct), c_void_p, c_int32, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
     'ss_ppr_iterate': (c_int32, [POINTER(PprGraphStruct), c_int32, c_int32, c_int32, c_double, c_void_p, c_size_t, c_void_p]),

@@ -3,8 +3,11 @@ row N4: `RA` is the other per-link precompute of HashDataset.__init__ (datasets/
 
 Same call surface as the reference: `RA(A, edge_index, batch_size)` with A a scipy sparse adjacency matrix and
 `edge_index` an int tensor of links [L, 2]; returns `(float32 scores [L], edge_index)`.  The three scores are one kernel
-(ss_common_neighbour_scores) with a different column multiplier; the multiplier itself is computed on the host with the
-reference's own numpy expression, so its fp64 values are identical.  No CPU fallback: the kernels need a HIP device.
+with a different column multiplier; the multiplier itself is computed on the host with the reference's own numpy expression,
+so its values are identical.  The kernel follows scipy's arithmetic for the matrix's dtype: fp64 products and sum for int, bool
+and float64 matrices (ss_common_neighbour_scores: CN of integer weights is exact, the rest within one float32 ulp), float32
+products and numpy's float32 pairwise summation order for float32 matrices (ss_common_neighbour_scores_f32: bit-identical).
+No CPU fallback: the kernels need a HIP device.
 
 `PPR(A, edge_index)` keeps the reference's own return convention, which differs from the other three: the scores come in the
 order of `torch.sort(edge_index[:, 0])` and the second value is that sorted link list as a [2, L] tensor.  The personalised
@@ -27,7 +30,8 @@ logger = logging.getLogger(__name__)
 
 class DeviceAdjacency(object):
     """scipy sparse matrix -> device CSR with sorted, duplicate-free rows (the canonical form scipy itself computes with)
-    plus fp64 values; built once per matrix object and reused by CN / AA / RA"""
+    plus the values widened to fp64 (exact); built once per matrix object and reused by CN / AA / RA.  `dtype` (A's) picks
+    the arithmetic of the scores: float32 matrices are scored in float32, as scipy does"""
 
     def __init__(self, A, device):
         A = A.tocsr()
@@ -185,12 +189,12 @@ def _scores(kind, A, edge_index, batch_size):
     out = torch.empty(L, dtype=torch.float32, device=device)
     err = _error_flag(device)
     lib = _native.lib()
+    fn = lib.ss_common_neighbour_scores_f32 if adj.dtype == np.float32 else lib.ss_common_neighbour_scores
     step = max(int(batch_size), 1)
     for lo in range(0, L, step):  # the reference's DataLoader chunks (heuristics.py:18,41,62); results do not depend on it
         hi = min(lo + step, L)
-        _native.check(lib.ss_common_neighbour_scores(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes,
-                                                     _ptr(lk[lo:hi]), hi - lo, _ptr(out[lo:hi]), _ptr(err), _stream(device)),
-                      'ss_common_neighbour_scores')
+        _native.check(fn(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes, _ptr(lk[lo:hi]), hi - lo,
+                         _ptr(out[lo:hi]), _ptr(err), _stream(device)), 'ss_common_neighbour_scores')
     if _take_error(device):
         raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
     return out.to(home), edge_index

@@ -73,6 +73,10 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.ss_minhash_hop_rows(None, None, None, 128, None, 0, None) == -1                                                 # no graph
     assert lib.ss_first_hop(None, None, None, 128, None, 8, None, None, 0, None, None) == -1
     assert lib.ss_propagate(None, None, None, 128, None, None, 256, None, 0, None, None) == -1
+    for cn in (lib.ss_common_neighbour_scores, lib.ss_common_neighbour_scores_f32):
+        assert cn(None, None, None, None, 4, None, 3, None, None, None) == -1       # null CSR / links / out
+        assert cn(None, None, None, None, 4, None, -1, None, None, None) == -1
+        assert cn(None, None, None, None, 4, None, 0, None, None, None) == 0        # no links: nothing to do
     g = ssa._native.CsrGraphStruct(rowptr=8, col=8, num_nodes=4, n_self_loops=0, n_self_loops_dev=None, hub_threshold=512, reserved=0,
                                    hub_rows=None, hub_count=None, mega_rows=None, mega_count=None, mega_scratch=None, row_begin=0, row_end=0)
     from ctypes import byref, c_void_p

@@ -160,3 +160,94 @@ def test_errors_empty_and_devices():
     fresh = DeviceAdjacency(A.tocoo(), torch.device('cuda:0'))
     for fn in (CN, AA, RA):
         assert torch.equal(fn(adj, ei)[0], fn(fresh, ei)[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# inputs at the edges: matrix dtypes, damping, tolerance, step limits, degenerate graphs, the check interval
+# ---------------------------------------------------------------------------------------------------------------------------
+def _weighted(dtype, seed=5):
+    """_small_graph's pattern with float32 / float64 weights (duplicates summed in that dtype) or as a bool matrix"""
+    A = _small_graph(seed).tocoo()
+    rng = np.random.RandomState(seed + 100)
+    if dtype == 'bool':
+        return sp.csr_matrix((np.ones(A.nnz, dtype=bool), (A.row, A.col)), shape=A.shape)
+    return sp.csr_matrix((rng.uniform(0.05, 3.0, size=A.nnz).astype(dtype), (A.row, A.col)), shape=A.shape)
+
+
+def _dangling_and_isolated(A):
+    deg = np.diff(A.indptr)
+    return [int(np.nonzero(deg == 0)[0][0]), A.shape[0] - 1]
+
+
+@pytest.mark.parametrize('dtype', ['float32', 'float64', 'bool'])
+def test_matrix_dtypes_match_the_restatement(dtype):
+    A = _weighted(dtype)
+    assert A.dtype == np.dtype(dtype)
+    for p in (0.5, 0.85):
+        _check_against_restatement(A, [0, 3, 17] + _dangling_and_isolated(A), p)
+
+
+@pytest.mark.parametrize('p', [0.0, 0.15, 0.99])
+@pytest.mark.parametrize('tol', [0.0, 1e-12, 1e-3])
+def test_damping_and_tolerance_edges(p, tol):
+    """tol = 0 stops only on a residual of exactly 0, i.e. once the iterate reaches its fixed point to the last bit -- a step
+    that depends on rounding, not on the method (p = 0 gets there after one step); 12 steps stay well above that floor"""
+    A = _weighted('float64', seed=6)
+    _, iters, _ = _check_against_restatement(A, [1, 2, 40] + _dangling_and_isolated(A), p, tol=tol, max_iter=12 if tol == 0 else 40)
+    if tol == 0 and p > 0:
+        assert (iters[:3] == 12).all()
+
+
+@pytest.mark.parametrize('max_iter', [0, 1, 2])
+def test_step_limits(max_iter):
+    A = _small_graph(7)
+    _, iters, ref_iters = _check_against_restatement(A, [0, 5, 9] + _dangling_and_isolated(A), 0.85, max_iter=max_iter)
+    assert np.array_equal(iters, ref_iters)
+    assert (iters[:3] == max(max_iter, 1)).all()  # the reference steps once before it checks max_iter
+    assert (iters[3:] == 1).all()  # a dangling or isolated source is its own fixed point: the second residual is 0
+
+
+def test_duplicate_sources_and_self_loops():
+    A = _small_graph(8).tolil()
+    for u in (3, 5, 11):
+        A[u, u] = 2
+    A = A.tocsr()
+    assert A.diagonal()[[3, 5, 11]].all()
+    vec, _, _ = _check_against_restatement(A, [3, 3, 5, 3, 11, 5], 0.85)
+    assert np.array_equal(vec[0], vec[1]) and np.array_equal(vec[0], vec[3]) and np.array_equal(vec[2], vec[5])
+    from subgraph_sketching_amd.heuristics import PPR
+    links = torch.tensor([[3, 3], [3, 5], [5, 5], [3, 11], [3, 3]])
+    scores, back = PPR(A, links)
+    src = back[0].numpy()
+    assert scores.numpy()[src == 3].size == 4 and len(set(scores.numpy()[(src == 3) & (back[1].numpy() == 3)].tolist())) == 1
+
+
+@pytest.mark.parametrize('n,edges', [(1, []), (1, [(0, 0)]), (2, []), (2, [(0, 1)]), (2, [(0, 1), (1, 0), (1, 1)])])
+def test_one_and_two_node_graphs(n, edges):
+    e = np.array(edges, dtype=np.int64).reshape(-1, 2)
+    A = sp.csr_matrix((np.ones(len(e)), (e[:, 0], e[:, 1])), shape=(n, n))
+    sources = [0] if n == 1 else [0, 1, 0]
+    vec, _, _ = _check_against_restatement(A, sources, 0.85)
+    assert np.allclose(vec.sum(axis=1), 1.0, rtol=1e-12)
+    from subgraph_sketching_amd.heuristics import PPR
+    links = torch.tensor([[0, 0]] if n == 1 else [[1, 0], [0, 1], [0, 0]])
+    scores, back = PPR(A, links)
+    for (u, v), s in zip(back.T.tolist(), scores.tolist()):
+        assert s == np.float32(vec[sources.index(u), v])
+
+
+@pytest.mark.parametrize('every', [1, 3, 1000])
+def test_check_interval_does_not_change_results(every, monkeypatch):
+    """knobs.PPR_CHECK_EVERY only says how often the host asks whether any column is still running"""
+    import subgraph_sketching_amd as ssa
+    from subgraph_sketching_amd.heuristics import personalized_pagerank
+    A = _small_graph(9)
+    sources = torch.tensor([0, 4, 8, 15, 23] + _dangling_and_isolated(A))
+    for p, tol, max_iter in ((0.85, 1e-7, 100), (0.99, 1e-12, 37), (0.5, 0.0, 5)):
+        base = personalized_pagerank(A, sources, p=p, tol=tol, max_iter=max_iter)
+        monkeypatch.setattr(ssa.knobs, 'PPR_CHECK_EVERY', every)
+        got = personalized_pagerank(A, sources, p=p, tol=tol, max_iter=max_iter)
+        monkeypatch.undo()
+        assert torch.equal(got[1], base[1]), (p, tol, max_iter)
+        assert torch.equal(got[0].view(torch.int64), base[0].view(torch.int64)), (p, tol, max_iter)
+        _check_against_restatement(A, sources.tolist(), p, tol=tol, max_iter=max_iter)

@@ -238,3 +238,73 @@ def test_scores_pin_the_oracle(ssa, dev, regenerated_tables):
             _, dbg = oracle.pair_features(links, tabs, cards.cpu().numpy(), 2, prm, debug=True)
             np.testing.assert_allclose(scores[u][valid].numpy(), dbg['inter'][:, hops[0] - 1, hops[1] - 1], rtol=1e-5, atol=0)
             assert int(valid.sum()) == N - 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# one-hop tables, awkward exclude lists, source counts around the 32-source staging block, an oracle pin at a generic shape
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_one_hop_tables(ssa, dev):
+    N, ei = _graph('uniform3000')
+    eh = _eh(ssa, h=1)
+    table, _ = eh.build_hash_tables(N, torch.from_numpy(ei).to(dev))
+    sources = _sources(N, 40, seed=21)
+    src = torch.from_numpy(sources).to(dev)
+    for excl in (None, ei):
+        for k in (1, 17):
+            want = _brute(eh, table, sources, k, (1, 1), N, excl)
+            _assert_same(eh.topk_candidates(src, table, k, exclude=None if excl is None else torch.from_numpy(excl).to(dev)), want)
+    with pytest.raises(ValueError):
+        eh.topk_candidates(src, table, 3, hops=(1, 2))
+
+
+def test_exclude_lists_with_negative_ids_duplicates_and_self_edges(ssa, dev):
+    N, ei = _graph('uniform3000')
+    eh = _eh(ssa, h=2)
+    table, _ = eh.build_hash_tables(N, torch.from_numpy(ei).to(dev))
+    sources = _sources(N, 30, seed=22)
+    rng = np.random.RandomState(23)
+    u = np.concatenate([np.repeat(sources, 8), sources])
+    v = np.concatenate([rng.randint(0, N, size=8 * len(sources)), sources])       # ... and every source's self edge
+    neg = rng.rand(len(u)) < 0.5
+    ex = np.stack([np.where(neg, u - N, u), np.where(rng.rand(len(u)) < 0.5, v - N, v)])  # ids as negative as positive
+    ex = np.where(ex < -N, ex + N, ex)
+    ex = np.concatenate([ex, ex[:, ::3], ei[:, :500]], axis=1)                    # duplicate edges
+    want = _brute(eh, table, sources, 25, (1, 2), N, ex)
+    got = eh.topk_candidates(torch.from_numpy(sources).to(dev), table, 25, hops=(1, 2), exclude=torch.from_numpy(ex).to(dev))
+    _assert_same(got, want)
+    # the excluded partners are really gone: every pair of the list with a source in it is absent from that source's row
+    ids = got[0].cpu().numpy()
+    exw = np.where(ex < 0, ex + N, ex)
+    for r, s in enumerate(np.where(sources < 0, sources + N, sources)):
+        assert not np.isin(ids[r], exw[1][exw[0] == s]).any()
+
+
+@pytest.mark.parametrize('S', [31, 32, 33])
+def test_source_counts_around_the_staging_block(ssa, dev, S):
+    N, ei = _graph('uniform3000')
+    eh = _eh(ssa, h=2)
+    table, _ = eh.build_hash_tables(N, torch.from_numpy(ei).to(dev))
+    sources = np.random.RandomState(S).randint(-N, N, size=S).astype(np.int64)
+    for hops in ((1, 1), (2, 1)):
+        want = _brute(eh, table, sources, 12, hops, N, ei)
+        _assert_same(eh.topk_candidates(torch.from_numpy(sources).to(dev), table, 12, hops=hops, exclude=torch.from_numpy(ei).to(dev)),
+                     want)
+
+
+def test_scores_pin_the_oracle_at_a_generic_shape(ssa, dev, regenerated_tables):
+    """p = 6, P = 192, three hops: every score of a full ranking against the oracle's intersection estimate"""
+    from oracle import oracle
+    g = load_golden('g3_g4_ba40.npz')
+    N, ei = int(g['num_nodes']), g['edge_index'].astype(np.int64)
+    eh = _eh(ssa, h=3, p=6, P=192)
+    table, cards = eh.build_hash_tables(N, torch.from_numpy(ei).to(dev))
+    tabs = {k: {'minhash': table[k].mh_u32.cpu().numpy().view(np.uint32), 'hll': table[k].hll_u8.cpu().numpy()} for k in range(4)}
+    prm = oracle_params(regenerated_tables[6])
+    for hops in ((3, 3), (1, 3), (2, 1)):
+        ids, scores = eh.topk_candidates(torch.arange(N), table, N, hops=hops)
+        for u in range(N):
+            valid = ids[u] >= 0
+            assert int(valid.sum()) == N - 1
+            links = np.stack([np.full(N - 1, u), ids[u][valid].numpy()], 1)
+            _, dbg = oracle.pair_features(links, tabs, cards.cpu().numpy(), 3, prm, debug=True)
+            np.testing.assert_allclose(scores[u][valid].numpy(), dbg['inter'][:, hops[0] - 1, hops[1] - 1], rtol=1e-5, atol=0)
