@@ -340,6 +340,32 @@ int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const uint32_t *m
 int ss_topk_exclude(const int64_t *sources, int32_t S, int64_t N, const int64_t *rowptr, const int32_t *col, int64_t *keys,
                     size_t keys_bytes, void *stream);
 
+/* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
+ * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
+ * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,
+ * hashing.py:148) -- is B_0(x) = {x}, B_k(x) = U_{(j -> x) in G'} B_{k-1}(j).  For a pair (u, v) and 1 <= k1, k2, k <= h:
+ *   I[k1][k2] = |B_k1(u) & B_k2(v)|   (what the intersection estimate J * U of hashing.py:167-189 approximates)
+ *   balls     = |B_k(u)| then |B_k(v)| (what the HLL++ cards of hashing.py:150-163 approximate)
+ *   feats     = the feature algebra of hashing.py:276-320 (flags: SS_FLAG_USE_ZERO_ONE / SS_FLAG_FLOOR_SF) on float(I), float(balls):
+ *               exact integers in fp32 for N < 2^20.
+ * links: device int64 [B, 2] (torch-style negative ids wrapped; a pair with an id outside [-N, N) gets NaN features and zero counts
+ * and sets err_flag, nullable).  I int32 [B, h, h] and balls int32 [B, 2, h] are nullable, feats fp32 [B, h(h+2)] is not.
+ *   ss_exact_pairs  the on-chip tier: one workgroup per pair, both BFSs in one LDS hash table.  A pair whose union of balls has more
+ *                   than lds_max_nodes nodes (at most the table's own bound; 0 = every pair) is left to the large tier: its index
+ *                   goes to the overflow list of the workspace (ss_exact_workspace_bytes(B) device bytes; the call clears its counters).
+ *   ss_exact_large  the large tier over that list, on the same stream after ss_exact_pairs with the same arguments: `slots`
+ *                   persistent workgroups, each owning ss_exact_slot_bytes(N) bytes of `arena` (dense distance bytes + visit lists),
+ *                   which must be all zero at the first call and are left all zero by every call.
+ * Both return SS_ERR_UNSUPPORTED for h outside [1, 3], SS_ERR_INVALID_ARG for negative sizes or null pointers, SS_OK for B == 0
+ * (before any launch), and need N < 2^31 and graph->num_nodes == N. */
+size_t ss_exact_workspace_bytes(int64_t B);
+size_t ss_exact_slot_bytes(int64_t N);
+int ss_exact_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags, int32_t lds_max_nodes,
+                   int32_t *I, int32_t *balls, float *feats, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
+int ss_exact_large(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags, int32_t *I,
+                   int32_t *balls, float *feats, void *workspace, size_t workspace_bytes, int32_t slots, void *arena, size_t arena_bytes,
+                   void *stream);
+
 /* out = A * x for a row-grouped CSR with fp32 values -- the node-feature propagation of
  * HashDataset._generate_sign_features (reference datasets/elph.py:87-110: gcn_norm, then torch_sparse.spmm = multiply
  * and scatter-add in edge order).  Every output element is accumulated by one lane in CSR order, product and sum rounded

@@ -8,7 +8,7 @@ from ctypes import byref, c_float, c_void_p
 import numpy as np
 import torch
 
-from . import _native, hll_tables, knobs
+from . import _native, exact, hll_tables, knobs
 from ._runtime import (CsrProtocolFault, raise_csr_protocol_faults, _DeferredErrors, _DeviceParams, _Span, _check_sizes, _compute_device, _error_flag, _ptr, _stream, _take_error,
                        linear_counting_table, logger)
 from .containers import (HopSketch, LazyMinhash, SketchTable, _packed_hll_of, _packed_minhash_of, _stamp_tables, _tag, unpack_minhash)
@@ -611,6 +611,18 @@ class ElphHashes(object):
         if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
             self._deferred.raise_if_set()
         return ids, scores
+
+    def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False):
+        """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph
+        build_hash_tables(num_nodes, edge_index) propagates over (its edges, flow source -> target, plus a self loop at every node
+        below max(edge_index) + 1), I[k1][k2] = |B_k1(u) & B_k2(v)| replaces J * U and |B_k(u)|, |B_k(v)| replace cards[u], cards[v]
+        in the same feature algebra (LABEL_LOOKUP order, use_zero_one / floor_sf as set now).  Counted by BFS on the GPU
+        (exact.py, csrc/ss_exact.hip).
+        @param links: int tensor [L, 2] (or [2]), torch-style negative ids wrapped; CPU or device
+        @param num_nodes, edge_index: as given to build_hash_tables; edge_index CPU or device
+        @param batch_size: pairs per launch (results do not depend on it)
+        @return: float32 [L, h(h+2)] on links.device; with return_counts also int32 I [L, h, h] and int32 balls [L, 2, h] (u, v)"""
+        return exact.exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=batch_size, return_counts=return_counts)
 
     def get_hashval(self, x):
         return x.hashvals

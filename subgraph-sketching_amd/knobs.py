@@ -65,3 +65,11 @@ PPR_COLUMNS = int(os.environ.get('SS_PPR_COLUMNS', '64'))
 # the active-column count is read back (a host synchronisation) every this many iterations: a batch ends at most this many
 # (then empty) launches after its last column stopped instead of at max_iter
 PPR_CHECK_EVERY = int(os.environ.get('SS_PPR_CHECK_EVERY', '4'))
+
+# exact_subgraph_features (csrc/ss_exact.hip): a pair whose union of k-hop balls has at most this many nodes is counted in the on-chip
+# tier (one workgroup, one LDS hash table; the table bounds it to 2048), every other pair in the large tier (dense per-slot distance
+# arrays in device memory).  0 sends every pair to the large tier (tests compare the two tiers that way).  Results do not depend on it.
+EXACT_LDS_MAX_NODES = int(os.environ.get('SS_EXACT_LDS_NODES', '2048'))
+# persistent workgroups ("slots") of the large tier, each owning N distance bytes + 2N int32 of visit lists (26 MB at ogbl-citation2
+# size); fewer when a quarter of the free device memory does not hold them.  The arena is allocated zeroed once per (device, stream, N)
+EXACT_LARGE_SLOTS = int(os.environ.get('SS_EXACT_SLOTS', '256'))
