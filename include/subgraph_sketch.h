@@ -411,6 +411,35 @@ int ss_table_digest(const void *data, int64_t bytes, uint64_t *out, void *stream
 int ss_pack_minhash(const int64_t *in, uint32_t *out, int64_t count, void *stream);
 int ss_unpack_minhash(const uint32_t *in, int64_t *out, int64_t count, void *stream);
 
+/* Incremental update of the tables of build_hash_tables after a few edges were added or removed.  The reference has no such
+ * operation: build_hash_tables (hashing.py:139-165) recomputes every row of every hop, and get_hashed_train_val_test_datasets
+ * (src/data.py:173-176 with datasets/elph.py) does so once per split for graphs that differ by a few per cent of their edges.  A hop-k
+ * row depends only on the closed in-neighbourhood of its node, so with `graph` the CSR of the edge list AFTER the change:
+ *   seed    = targets of the added / removed edges + rows whose implicit self loop (i < n_self) appeared or disappeared, read off the
+ *             old hop-1 cardinalities: (i < n_self) != (cards_old[i * cards_stride] > 0)
+ *   dirty_1 = seed;  dirty_k = seed + { i : an in-neighbour of i is in dirty_{k-1}, or i < n_self and i is in dirty_{k-1} }
+ * and hop k of the update recomputes exactly the rows of dirty_k -- from scratch, so removals need nothing of their own.
+ *   ss_update_mark  dirty_1 .. dirty_h as byte maps, int32 row lists and device-side counts, all in `workspace`
+ *                   (ss_update_workspace_bytes(N, h) device bytes, 0 = unsupported size; the call clears what it needs).
+ *                   added_dst / removed_dst: device int64[n_added] / [n_removed] target ids (either may be empty); an id outside
+ *                   [0, N) sets bit 0 of *err_flag (nullable) and is dropped.  One pull pass over `col` per hop beyond the first.
+ *   ss_update_hop   rows dirty_hop of the hop's MinHash table, HLL table and cardinalities (cards_out[i * cards_stride]) from the
+ *                   UPDATED tables of hop - 1 (mh_in / hll_in); every other row and cardinality is left untouched.  mh_in == NULL:
+ *                   MinHash rows from node ids (hop 1 only; a / b as ss_first_hop, P % 64 == 0, P <= 256); hll_in == NULL: HLL rows
+ *                   from node ids (hop 1 only, p == 8); SS_ERR_UNSUPPORTED otherwise.  To be called for hop = 1 .. h in order, on the
+ *                   stream of ss_update_mark with the same graph and workspace.  Launches are sized by N; the row counts are read
+ *                   on the device, so nothing between the first and the last launch of an update waits for the host.
+ * After the calls the first words of the workspace hold, as int32: [0] = |seed|, [4k] = |dirty_k|, [4k + 1] / [4k + 2] = how many of
+ * them were listed as regular / hub rows (more in-edges than graph->hub_threshold: one 16-wavefront workgroup each), k = 1 .. h.
+ * The hub lists of the graph itself are not used: a hub row that is not dirty is not recomputed. */
+size_t ss_update_workspace_bytes(int64_t N, int32_t h);
+int ss_update_mark(const ss_csr_graph *graph, const int64_t *added_dst, int64_t n_added, const int64_t *removed_dst, int64_t n_removed,
+                   const float *cards_old, int64_t cards_stride, int32_t h, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int ss_update_hop(const ss_csr_graph *graph, int32_t hop, int32_t h, const uint64_t *a, const uint64_t *b, const uint32_t *mh_in,
+                  uint32_t *mh_out, int32_t P, const uint8_t *hll_in, uint8_t *hll_out, int32_t p, float *cards_out, int64_t cards_stride,
+                  const ss_hll_params *prm, const void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement-only entry points (launch-duration probes used by bench.py and tools/) are declared in
  * subgraph_sketch_debug.h; they are not part of the drop-in boundary. */
 

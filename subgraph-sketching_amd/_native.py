@@ -103,6 +103,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_exact_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
+    'ss_update_workspace_bytes': (c_size_t, [c_int64, c_int32]),
+    'ss_update_mark': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    'ss_update_hop': (c_int32, [POINTER(CsrGraphStruct), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                c_int32, c_void_p, c_int64, POINTER(HllParams), c_void_p, c_size_t, c_void_p]),
     'ss_spmm_csr': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'ss_csr_group_ids': (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_csr_sort_workspace_bytes': (c_size_t, [c_int64]),

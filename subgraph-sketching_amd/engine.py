@@ -624,6 +624,26 @@ class ElphHashes(object):
         @return: float32 [L, h(h+2)] on links.device; with return_counts also int32 I [L, h, h] and int32 balls [L, 2, h] (u, v)"""
         return exact.exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=batch_size, return_counts=return_counts)
 
+    def update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
+        """the tables of build_hash_tables(num_nodes, old_edge_index) brought up to date with a changed edge list WITHOUT a rebuild: a
+        hop-k row depends only on the closed in-neighbourhood of its node, so hop k recomputes exactly the rows within k hops downstream
+        of the targets of the changed edges (plus the rows whose implicit self loop came or went because max(edge_index) moved) and
+        writes nothing else (update.py, csrc/ss_update.hip).  The reference rebuilds: build_hash_tables once per split
+        (src/data.py:173-176: the test split is the training graph plus the validation edges).
+        @param hash_table, cards: what build_hash_tables returned for the OLD graph (or load_sketches of a packed cache of it), on the
+               compute device; hops 0 .. max_hash_hops, cards float32 [num_nodes, max_hash_hops]
+        @param edge_index: int64 [2, E], the graph AFTER the change -- what a rebuild would be given
+        @param added, removed: int64 [2, A] / [2, R] directed edges by which the new edge list differs from the old one (both directions
+               of an undirected change); only their targets (row 1) are used; at least one must be given.  Ids outside [0, num_nodes)
+               are reported as build_hash_tables reports them (strict_bounds)
+        @param copy: False updates the given objects in place; True clones the tables first and leaves the inputs untouched
+        @param return_info: also return {'seed_rows': int, 'dirty_rows': {k: rows recomputed at hop k}} (one host read, after the
+               last launch)
+        @return: (table, cards[, info]): every hop table bit-identical to build_hash_tables(num_nodes, edge_index)"""
+        from . import update
+        return update.update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=added, removed=removed, copy=copy,
+                                         return_info=return_info)
+
     def get_hashval(self, x):
         return x.hashvals
 

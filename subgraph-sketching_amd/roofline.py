@@ -161,3 +161,27 @@ def gathered_table_bytes(N, family, P=128, p=8, h=2):
     """bytes of the table(s) a kernel family gathers rows from"""
     M = 1 << p
     return {'minhash_hop': N * 4 * P, 'hll_hop': N * M, 'fused_first_hop_hll_hop': N * M, 'pair_features': h * N * (4 * P + M)}[family]
+
+
+def update_bytes(N, E, dirty_rows, dirty_edges, P=128, p=8, hop=2, first_hop_from_ids=True):
+    """algorithmic bytes of the two kernel families of ElphHashes.update_hash_tables (csrc/ss_update.hip) at one hop.
+    dirty_rows / dirty_edges: |dirty_hop| and the in-edges of those rows.
+      'mark'  one pull pass over the in-edge CSR: col (4E, an upper bound: a row stops at its first dirty in-neighbour) + rowptr
+              (8(N+1)) + one flag byte read per walked in-edge (L2 hits: the map is N bytes) + the seed and previous-hop flags of
+              the row itself (2N) + this hop's map written (N) + the list (4 dirty_rows).  Hop 1 reads no edges: the seed map (N),
+              cards_old[:, 0] (4N), rowptr (8(N+1)), the map written back (N), the list.
+      'rows'  the listed rows recomputed from scratch: list entry + two rowptr words (20) + col (4 per in-edge) per row; a table hop
+              gathers one R-byte row per in-edge and per implicit self loop and writes R + 4 bytes (the row + its cardinality); the
+              first hop from node ids reads no table."""
+    M = 1 << p
+    R = 4 * P + M
+    if hop == 1:
+        mark = N + 4 * N + 8 * (N + 1) + N + 4 * dirty_rows
+    else:
+        mark = 4 * E + E + 8 * (N + 1) + 2 * N + N + 4 * dirty_rows
+    graph = 20 * dirty_rows + 4 * dirty_edges
+    if hop == 1 and first_hop_from_ids:
+        rows = graph + dirty_rows * (R + 4)
+    else:
+        rows = graph + (dirty_edges + dirty_rows) * R + dirty_rows * (R + 4)
+    return {'mark': mark, 'rows': rows}
