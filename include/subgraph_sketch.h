@@ -40,6 +40,8 @@ extern "C" {
 /* flags of ss_pair_features (hashing.py:56,67) */
 #define SS_FLAG_USE_ZERO_ONE 1u
 #define SS_FLAG_FLOOR_SF 2u
+/* ss_exact_pairs / ss_exact_large only: the balls of (u, v) are those of the graph without the edges u -> v and v -> u */
+#define SS_FLAG_MASK_TARGET 4u
 
 /* HyperLogLog++ estimator constants -- everything ElphHashes.__init__ takes from datasketch
  * (hashing.py:69-80) plus two host-derived helpers.  All fp32 values are rounded on the host exactly
@@ -357,7 +359,10 @@ int ss_topk_exclude(const int64_t *sources, int32_t S, int64_t N, const int64_t 
  *                   persistent workgroups, each owning ss_exact_slot_bytes(N) bytes of `arena` (dense distance bytes + visit lists),
  *                   which must be all zero at the first call and are left all zero by every call.
  * Both return SS_ERR_UNSUPPORTED for h outside [1, 3], SS_ERR_INVALID_ARG for negative sizes or null pointers, SS_OK for B == 0
- * (before any launch), and need N < 2^31 and graph->num_nodes == N. */
+ * (before any launch), and need N < 2^31 and graph->num_nodes == N.
+ * flags & SS_FLAG_MASK_TARGET (both calls alike): every pair is counted in the graph without every copy of u -> v and of v -> u -- the
+ * target-link removal of the reference's SEAL path (src/datasets/seal.py:338), the exact counterpart of ss_masked_pair_features; n_self
+ * and the self loops stay as they are.  The BFS leaves the partner out when it expands the root, nothing else changes. */
 size_t ss_exact_workspace_bytes(int64_t B);
 size_t ss_exact_slot_bytes(int64_t N);
 int ss_exact_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags, int32_t lds_max_nodes,
@@ -439,6 +444,32 @@ int ss_update_mark(const ss_csr_graph *graph, const int64_t *added_dst, int64_t 
 int ss_update_hop(const ss_csr_graph *graph, int32_t hop, int32_t h, const uint64_t *a, const uint64_t *b, const uint32_t *mh_in,
                   uint32_t *mh_out, int32_t P, const uint8_t *hll_in, uint8_t *hll_out, int32_t p, float *cards_out, int64_t cards_stride,
                   const ss_hll_params *prm, const void *workspace, size_t workspace_bytes, void *stream);
+
+/* Target-link masking: ss_pair_features for links that may be edges of the graph the tables were built on, each scored as if its own
+ * edge were absent.  The reference does this on its SEAL path only (src/datasets/seal.py:338 removes the target link from every
+ * enclosing subgraph); its sketch path (hashing.py:139-165 build, :258-323 query) cannot, a table row being a min / max fold.  For a link
+ * (u, v) let G_uv be the graph of `graph` (its edges, flow source -> target, plus the implicit self loops below n_self) without every copy
+ * of u -> v and of v -> u; n_self is that of the full graph.  Row q of `out` is what ss_pair_features returns for link q from tables and
+ * cards built on G_uv: MinHash match counts and HLL zero counts exactly, features to fp32 rounding.  A link with u == v, with neither
+ * direction present, or with an id out of range keeps the row (and err_flag report) of ss_pair_features bit for bit.
+ *   graph    the CSR the tables were built on (ss_csr_build of the same edge list; n_self_loops / n_self_loops_dev as in the build;
+ *            whole graph: no row range), graph->num_nodes == N < 2^31.  Nothing checks that the tables belong to it.
+ *   a, b     the permutation parameters of ss_minhash_init (device uint64[P]): hop 0 is recomputed from node ids
+ *   mh, hll, cards, prm, flags, out, dbg_match, dbg_zero, err_flag: as ss_pair_features (cards: those of the FULL graph; the masked
+ *            rows' cardinalities are computed from the masked rows)
+ *   dbg_row_zeros (device int32[B, 2, h], nullable): zero registers of the hop-k row of u, then of v, as used for the link
+ *   dbg_masked    (device uint8[B], nullable): 1 where the link was found in the graph and rebuilt
+ *   workspace     ss_masked_workspace_bytes(B) device bytes (0 = unsupported size; B < 2^31); after the call its first int32 holds
+ *                 the number of links rebuilt
+ * Launches: the plain query, one classify pass over rows u and v of the CSR, one pass over the links found (their count never leaves
+ * the device).  Cost per edge link: the in-degrees of u and v at h <= 2, their 2-hop in-walk counts at h = 3.  Returns
+ * SS_ERR_UNSUPPORTED when a sketch row has more than 256 16-byte chunks (P / 4 + 2^p / 16 > 256). */
+size_t ss_masked_workspace_bytes(int64_t B);
+int ss_masked_pair_features(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, const uint64_t *a,
+                            const uint64_t *b, const uint32_t *const *mh, int32_t P, const uint8_t *const *hll, const float *cards,
+                            int64_t cards_stride, const ss_hll_params *prm, uint32_t flags, float *out, int32_t *dbg_match,
+                            int32_t *dbg_zero, int32_t *dbg_row_zeros, uint8_t *dbg_masked, int32_t *err_flag, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* Measurement-only entry points (launch-duration probes used by bench.py and tools/) are declared in
  * subgraph_sketch_debug.h; they are not part of the drop-in boundary. */

@@ -15,6 +15,7 @@ SS_MAX_HOPS = 3
 SS_MAX_TABLE = 512
 SS_FLAG_USE_ZERO_ONE = 1
 SS_FLAG_FLOOR_SF = 2
+SS_FLAG_MASK_TARGET = 4  # ss_exact_pairs / ss_exact_large: balls of the graph without the link's own edge
 SS_CSR_ERR_BOUNDS, SS_CSR_ERR_PROTOCOL = 1, 2  # bits of a CSR build's err_flag
 
 
@@ -108,6 +109,10 @@ SIGNATURES = {
                                  c_size_t, c_void_p]),
     'ss_update_hop': (c_int32, [POINTER(CsrGraphStruct), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                 c_int32, c_void_p, c_int64, POINTER(HllParams), c_void_p, c_size_t, c_void_p]),
+    'ss_masked_workspace_bytes': (c_size_t, [c_int64]),
+    'ss_masked_pair_features': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, POINTER(c_void_p),
+                                          c_int32, POINTER(c_void_p), c_void_p, c_int64, POINTER(HllParams), c_uint32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_spmm_csr': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'ss_csr_group_ids': (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_csr_sort_workspace_bytes': (c_size_t, [c_int64]),

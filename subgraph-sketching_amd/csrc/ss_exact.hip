@@ -53,6 +53,11 @@ __device__ __forceinline__ int64_t exact_n_self(const ss_csr_graph &g)
     return g.n_self_loops_dev ? *g.n_self_loops_dev : g.n_self_loops;
 }
 
+// SS_FLAG_MASK_TARGET: the balls are those of the graph without the edges u -> v and v -> u.  Level 1 expands the root alone, so the
+// root's expansion leaves the partner out (-1: nothing is left out -- no node id is negative); when the partner is reached another
+// way and expanded, it finds the root visited already, so its own removed in-edge needs nothing.
+__device__ __forceinline__ int32_t exact_skip(uint32_t flags, int64_t partner) { return (flags & SS_FLAG_MASK_TARGET) ? (int32_t)partner : -1; }
+
 // (d_u, d_v) bucket of a node from its two side bytes: the lowest level bit, H + 1 when unreached
 template <int H>
 __device__ __forceinline__ int exact_bucket(uint32_t b)
@@ -215,6 +220,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
         bool ovf = limit <= 0;
         for (int side = 0; side < 2 && !ovf; ++side) {
             const int64_t root = side ? v : u;
+            const int32_t skip = exact_skip(flags, side ? u : v);
             if (root < n_self && t == 0) lds_visit(s, (uint32_t)root, side, 0, limit);
             __syncthreads();
             int lo = 0, hi = s.cnt[side];
@@ -226,7 +232,9 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
                     const int64_t e1 = g.rowptr[y + 1];
                     for (int64_t e = g.rowptr[y] + lane; e < e1; e += kRow) {
                         if (s.ovf) break;
-                        lds_visit(s, (uint32_t)g.col[e], side, d, limit);  // (the self loop of y: y is in the list already)
+                        const int32_t x = g.col[e];
+                        if (d == 1 && x == skip) continue;  // SS_FLAG_MASK_TARGET: the root's expansion leaves the partner out
+                        lds_visit(s, (uint32_t)x, side, d, limit);  // (the self loop of y: y is in the list already)
                     }
                 }
                 __syncthreads();
@@ -324,6 +332,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
         }
         for (int side = 0; side < 2; ++side) {
             const int64_t root = side ? v : u;
+            const int32_t skip = exact_skip(flags, side ? u : v);
             if (root < n_self && t == 0 && slot_reach(sl, (int32_t)root, side, 0)) sl.list[side][cnt[side]++] = (int32_t)root;
             __syncthreads();
             int64_t lo = 0, hi = cnt[side];
@@ -343,6 +352,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
                     }
                     for (int64_t e = e0 + lane; e < e1; e += kRow) {
                         const int32_t x = g.col[e];
+                        if (d == 1 && x == skip) continue;
                         if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
                     }
                 }
@@ -353,6 +363,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
                     const int64_t e1 = g.rowptr[y + 1];
                     for (int64_t e = g.rowptr[y] + t; e < e1; e += kExactThreads) {
                         const int32_t x = g.col[e];
+                        if (d == 1 && x == skip) continue;
                         if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
                     }
                 }

@@ -612,7 +612,7 @@ class ElphHashes(object):
             self._deferred.raise_if_set()
         return ids, scores
 
-    def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False):
+    def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, mask_target=False):
         """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph
         build_hash_tables(num_nodes, edge_index) propagates over (its edges, flow source -> target, plus a self loop at every node
         below max(edge_index) + 1), I[k1][k2] = |B_k1(u) & B_k2(v)| replaces J * U and |B_k(u)|, |B_k(v)| replace cards[u], cards[v]
@@ -621,8 +621,11 @@ class ElphHashes(object):
         @param links: int tensor [L, 2] (or [2]), torch-style negative ids wrapped; CPU or device
         @param num_nodes, edge_index: as given to build_hash_tables; edge_index CPU or device
         @param batch_size: pairs per launch (results do not depend on it)
+        @param mask_target: True counts every link in the graph without its own edge (every copy of u -> v and of v -> u; self loops and
+               max(edge_index) + 1 stay): the exact counterpart of get_subgraph_features(mask_target=edge_index)
         @return: float32 [L, h(h+2)] on links.device; with return_counts also int32 I [L, h, h] and int32 balls [L, 2, h] (u, v)"""
-        return exact.exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=batch_size, return_counts=return_counts)
+        return exact.exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=batch_size, return_counts=return_counts,
+                                             mask_target=mask_target)
 
     def update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
         """the tables of build_hash_tables(num_nodes, old_edge_index) brought up to date with a changed edge list WITHOUT a rebuild: a
@@ -708,7 +711,8 @@ class ElphHashes(object):
             raise ValueError('source and destination hash value shapes must be the same')
         return torch.count_nonzero(src == dst, dim=-1) / self.num_perm
 
-    def get_subgraph_features(self, links, hash_table, cards, batch_size=11000000, degrees=None, lazy=False, out=None):
+    def get_subgraph_features(self, links, hash_table, cards, batch_size=11000000, degrees=None, lazy=False, out=None, mask_target=None,
+                              return_debug=False):
         """structural features of node pairs: approximations of the number of nodes at distance (d_u, d_v)
         from (u, v), for the (d_u, d_v) listed in LABEL_LOOKUP[max_hops] (reference :258-323).
         @param links: int tensor [n_edges, 2] (or [2])
@@ -723,7 +727,23 @@ class ElphHashes(object):
         @param out: extension: a contiguous float32 [n_edges, F] tensor ON THE COMPUTE DEVICE the rows are written into (and which
                is returned): a slice of a larger result -- dist.sharded_precompute lets every launch store straight into the block
                of the output the collective then sends from
+        @param mask_target: extension (masked.py, csrc/ss_masked.hip): the edge_index [2, E] (CPU or device) that
+               `hash_table` and `cards` WERE BUILT ON -- nothing can check that cheaply.  Every link is then scored as if its own edge
+               were absent: link (u, v) gets the features of tables built on the graph without every copy of u -> v and of v -> u
+               (self loops and max(edge_index) + 1 as in the full graph), the target-link removal of the reference's SEAL path
+               (src/datasets/seal.py:338).  MinHash match counts and HLL zero counts are exact, features within the engine's fp32 bar;
+               a link with u == v or with neither direction present keeps the plain query's row bit for bit.  Not combinable with
+               degrees, lazy or out (ValueError).  None (default): the plain query
+        @param return_debug: with mask_target only: also return {'match' int32 [L, h, h], 'zeros' int32 [L, h, h], 'row_zeros' int32
+               [L, 2, h], 'masked' bool [L]} -- the integers behind every row and which links were found in the graph
         @return: float32 [n_edges, max_hops * (max_hops + 2)] on links.device"""
+        if mask_target is not None:
+            from . import masked
+            masked.check_arguments(self, links, mask_target, batch_size, degrees=degrees, lazy=lazy, out=out)
+            return masked.masked_subgraph_features(self, links, hash_table, cards, mask_target, batch_size=batch_size,
+                                                   return_debug=return_debug)
+        if return_debug:
+            raise ValueError('return_debug belongs to the masked query: give mask_target')
         if self.max_hops not in (1, 2, 3):
             raise NotImplementedError("Only 1, 2 and 3 hop hashes are implemented")
         if links.dim() == 1:

@@ -79,10 +79,12 @@ def check_arguments(h, links, num_nodes, edge_index, batch_size):
     return lk, ei, N, batch_size
 
 
-def exact_subgraph_features(eh, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, stats=None):
+def exact_subgraph_features(eh, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, stats=None, mask_target=False):
     """see ElphHashes.exact_subgraph_features.  stats (measurement hook, tools/probe_exact.py): a dict that receives the overflow
     count and the milliseconds of each tier, summed over batches (the call then synchronises after every launch)"""
     h = eh.max_hops
+    if not isinstance(mask_target, bool):
+        raise ValueError(f'mask_target of the exact query is a bool (the links are masked in the edge_index given), got {type(mask_target).__name__}')
     lk, ei, N, batch_size = check_arguments(h, links, num_nodes, edge_index, batch_size)
     home, L, nf = lk.device, lk.size(0), h * (h + 2)
     if L == 0:
@@ -99,6 +101,7 @@ def exact_subgraph_features(eh, links, num_nodes, edge_index, batch_size=1100000
     I = torch.empty((L, h, h), dtype=torch.int32, device=device) if return_counts else None
     balls = torch.empty((L, 2, h), dtype=torch.int32, device=device) if return_counts else None
     flags = (_native.SS_FLAG_USE_ZERO_ONE if eh.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if eh.floor_sf else 0)
+    flags |= _native.SS_FLAG_MASK_TARGET if mask_target else 0
     lib = _native.lib()
     bmax = min(batch_size, L)
     ws_bytes = int(lib.ss_exact_workspace_bytes(bmax))

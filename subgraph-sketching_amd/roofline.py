@@ -185,3 +185,24 @@ def update_bytes(N, E, dirty_rows, dirty_edges, P=128, p=8, hop=2, first_hop_fro
     else:
         rows = graph + (dirty_edges + dirty_rows) * R + dirty_rows * (R + 4)
     return {'mark': mark, 'rows': rows}
+
+
+def masked_query_bytes(links, edge_links, mean_in_degree, P=128, p=8, h=2, two_hop_walks=0.0):
+    """algorithmic bytes of ElphHashes.get_subgraph_features(mask_target=...) over `links` links of which `edge_links` are edges of the
+    graph (csrc/ss_masked.hip).  mean_in_degree: mean in-degree of the endpoints of the edge links; two_hop_walks: mean
+    number of 2-hop in-walks (sum of the in-degrees of the in-neighbours) of such an endpoint, read at h = 3 only.
+      plain query   pair_bytes per link -- every row is written by it
+      classify      the two ids (16) + two rowptr pairs (32) + the col entries of rows u and v (4 each) per link
+      masked rows   per edge link: list entry + ids + rowptr (4 + 16 + 32), col of both rows once per hop walked; hop 1 reads no table
+                    (node ids are hashed); hop 2 gathers one R-byte hop-1 row per in-neighbour of u and of v; hop 3 one per 2-hop
+                    in-walk and per in-neighbour (+ their col entries and rowptr words); the output row is written again"""
+    R = 4 * P + (1 << p)
+    d = float(mean_in_degree)
+    plain = links * pair_bytes(P, p, h)
+    classify = links * (48 + 8 * d)
+    per_edge = 52 + 8 * d + 4 * h * (h + 2)
+    if h >= 2:
+        per_edge += 2 * d * (R + 4)
+    if h >= 3:
+        per_edge += 2 * (two_hop_walks + d) * (R + 4) + 2 * d * 16
+    return int(plain + classify + edge_links * per_edge)
