@@ -32,12 +32,32 @@ __device__ __forceinline__ uint64_t hash_u64(uint64_t x)
     return x;
 }
 
+// the hop-0 HLL row of a node with hash hv has ONE non-zero register (hashing.py:126-137): register hv & (m - 1) holds the rank
+// (64 - p) - bit_length(hv >> p) + 1, always in [1, 64 - p + 1]
+__device__ __forceinline__ uint32_t hll_rank_of(uint64_t hv, int p)
+{
+    const uint64_t bits = hv >> p;
+    const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
+    return (uint32_t)((64 - p) - bl + 1);
+}
+__device__ __forceinline__ uint32_t hll_register_of(uint64_t hv, int M) { return (uint32_t)hv & (uint32_t)(M - 1); }
+
 // x mod (2^61 - 1) for any 64-bit x
 __device__ __forceinline__ uint64_t mod_mersenne61(uint64_t x)
 {
     const uint64_t M = (1ULL << 61) - 1;
     uint64_t r = (x & M) + (x >> 61);
     return r >= M ? r - M : r;
+}
+
+// the two node ids of a query link: torch-style negative indexing, then the bounds; false: an id outside [-N, N)
+__device__ __forceinline__ bool link_ids(const int64_t *links, int64_t q, int64_t N, int64_t &u, int64_t &v)
+{
+    u = links[2 * q];
+    v = links[2 * q + 1];
+    u = u < 0 ? u + N : u;
+    v = v < 0 ? v + N : v;
+    return (uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N;
 }
 
 // ---- byte-parallel helpers on HLL registers (4 registers per dword) --------------------------------
@@ -113,6 +133,22 @@ __device__ __forceinline__ void hll_dword_stats(uint32_t w, int &nonzero, float 
     sum = dot2_ones(regs_odd_to_bf16(w), sum);
     nonzero += __builtin_popcount(nonzero_byte_flags(w));
 }
+// ... of the 16 registers of one chunk, dword after dword (the float sum is order-sensitive: this order is part of the tables' bits)
+__device__ __forceinline__ void hll_chunk_stats(u32x4 x, int &nonzero, float &sum)
+{
+    hll_dword_stats(x.x, nonzero, sum);
+    hll_dword_stats(x.y, nonzero, sum);
+    hll_dword_stats(x.z, nonzero, sum);
+    hll_dword_stats(x.w, nonzero, sum);
+}
+// the lanes' partial statistics summed over the wavefront (butterfly from distance 1 up: every lane ends with the totals)
+__device__ __forceinline__ void wave_sum_stats(int &nonzero, float &sum)
+{
+    for (int off = 1; off < kWave; off <<= 1) {
+        nonzero += __shfl_xor(nonzero, off);
+        sum += __shfl_xor(sum, off);
+    }
+}
 
 // ---- DPP reductions inside a 16-lane row: every lane ends with the row total ----------------------
 template <int CTRL>
@@ -140,6 +176,17 @@ __device__ __forceinline__ float row16_sum_f(float v)
     v += __int_as_float(dpp_i<kDppHalfMirror>(__float_as_int(v)));
     v += __int_as_float(dpp_i<kDppMirror>(__float_as_int(v)));
     return v;
+}
+
+// the statistics of a finished HLL row of CH chunks (global memory or LDS) by one 16-lane group: lane l takes chunks l, l + 16, ...,
+// every lane ends with the row's totals
+__device__ __forceinline__ void hll_row16_stats(const u32x4 *row, int CH, int l, int &nonzero, float &hsum)
+{
+    nonzero = 0;
+    hsum = 0.0f;
+    for (int c = l; c < CH; c += kRow) hll_chunk_stats(row[c], nonzero, hsum);
+    nonzero = row16_sum_i(nonzero);
+    hsum = row16_sum_f(hsum);
 }
 
 // ---- HLL++ estimator (reference hashing.py:194-232) ------------------------------------------------

@@ -31,12 +31,7 @@ __global__ __launch_bounds__(256) void hll_count_kernel(const uint8_t *__restric
         for (int r = 0; r < kCountRows; ++r)
             x[r] = row0 + r < n ? *reinterpret_cast<const u32x4 *>(regs + (row0 + r) * M + 16 * c) : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int r = 0; r < kCountRows; ++r) {
-            hll_dword_stats(x[r].x, nonzero[r], hsum[r]);
-            hll_dword_stats(x[r].y, nonzero[r], hsum[r]);
-            hll_dword_stats(x[r].z, nonzero[r], hsum[r]);
-            hll_dword_stats(x[r].w, nonzero[r], hsum[r]);
-        }
+        for (int r = 0; r < kCountRows; ++r) hll_chunk_stats(x[r], nonzero[r], hsum[r]);
     }
 #pragma unroll
     for (int r = 0; r < kCountRows; ++r) {

@@ -132,15 +132,6 @@ __device__ void exact_bad(int64_t q, const ExactOut &o)
     if (o.err) *o.err = 1;
 }
 
-__device__ __forceinline__ bool exact_ids(const int64_t *links, int64_t q, int64_t N, int64_t &u, int64_t &v)
-{
-    u = links[2 * q];
-    v = links[2 * q + 1];
-    u = u < 0 ? u + N : u;  // torch-style negative indexing, as the sketch query
-    v = v < 0 ? v + N : v;
-    return (uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N;
-}
-
 // ---- on-chip tier ---------------------------------------------------------------------------------------------------------------
 // the value of slot i is the 16-bit half (i & 1) of val[i >> 1] (two side bytes; only ds_or_b32 exists, so halves share a word)
 struct ExactLds {
@@ -203,7 +194,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
     }
     for (int64_t q = blockIdx.x; q < B; q += gridDim.x) {
         int64_t u, v;
-        const bool ok = exact_ids(links, q, N, u, v);  // (workgroup-uniform)
+        const bool ok = link_ids(links, q, N, u, v);  // (workgroup-uniform)
         if (t < 25) s.hist[t] = 0;
         if (t == 0) {
             s.n_nodes = 0;
@@ -326,7 +317,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
         const int64_t q = next_q;
         if (q < 0) break;
         int64_t u, v;
-        if (!exact_ids(links, q, N, u, v)) {  // (the LDS tier has written this pair already: never listed)
+        if (!link_ids(links, q, N, u, v)) {  // (the LDS tier has written this pair already: never listed)
             __syncthreads();
             continue;
         }

@@ -65,21 +65,16 @@ __global__ __launch_bounds__(256) void first_hop_kernel(GraphArgs g, const uint6
     const int total = deg + (i < n_self ? 1 : 0);
     if (DO_MH && !DO_HLL && !kForceExactFirstHop) {
         // MinHash alone: two-phase walk (one multiply per neighbour and permutation); the rare ambiguous row is redone exactly
-        const bool amb = total > 0 && first_hop_minhash_fast<PPL>(g.col + rb, deg, total, i, a, b, acc, lane);
-        if (__any(amb)) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-            first_hop_walk<PPL, true, false>(g.col + rb, deg, total, i, 0, 1, p, a, b, acc, my_row, lane);
-        }
+        first_hop_minhash_row<PPL>(g.col + rb, deg, total, i, p, a, b, acc, lane, true);
     } else {
         first_hop_walk<PPL, DO_MH, DO_HLL>(g.col + rb, deg, total, i, 0, 1, p, a, b, acc, my_row, lane);
-    }
-
-    if (DO_MH) {
-        if (total == 0) {
+        if (DO_MH && total == 0) {
 #pragma unroll
             for (int q = 0; q < PPL; ++q) acc[q] = 0u;  // no in-edge, no self loop: all-zero row (PyG default)
         }
+    }
+
+    if (DO_MH) {
 #pragma unroll
         for (int q = 0; q < PPL; ++q) {
             mh_out[i * P + lane + kWave * q] = acc[q];
@@ -97,10 +92,7 @@ __global__ __launch_bounds__(256) void first_hop_kernel(GraphArgs g, const uint6
         int nonzero = 0;
         float hsum = 0.0f;
         hll_dword_stats(regs, nonzero, hsum);
-        for (int off = 1; off < kWave; off <<= 1) {
-            nonzero += __shfl_xor(nonzero, off);
-            hsum += __shfl_xor(hsum, off);
-        }
+        wave_sum_stats(nonzero, hsum);
         if (lane == 0) {
             const float card = hll_estimate(est, 256 - nonzero, hsum);
             cards_out[i * cards_stride] = card;
@@ -218,57 +210,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void h
         const int deg = degs[r];
         const bool hub = skip_hubs && deg > g.hub_threshold;
         const int total = hub ? 0 : deg + (i < n_self ? 1 : 0);
-        const int32_t *nb = g.col + rbs[r];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4 *>(row + 64 * k + 4 * l) = u32x4{0u, 0u, 0u, 0u};
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // (the id of the lane's NEXT neighbour is requested before the current one is hashed -- unconditionally, from an address
-        // that always exists: rows of more than 16 neighbours otherwise pay one exposed round trip per 16 neighbours)
-        int cur = nid0[r];
-        int fresh = 0;  // registers this lane was the FIRST to set (the LDS atomic returns what was there: 0 exactly once per register)
-        for (int t = l; t < total; t += kRow) {
-            const int nxt = *(t + kRow < deg ? nb + t + kRow : always_valid);
-            const int64_t nid = t < deg ? (int64_t)cur : i;
-            cur = nxt;
-            const uint64_t hv = hash_u64((uint64_t)(nid + 1));
-            const uint64_t bits = hv >> p;
-            const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
-            fresh += atomicMax(&row[(uint32_t)hv & 255u], (uint32_t)((64 - p) - bl + 1)) == 0u ? 1 : 0;  // (ranks are >= 1)
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // lane l owns registers 16l .. 16l+15
-        u32x4 packed;
-        uint32_t *pw = reinterpret_cast<uint32_t *>(&packed);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pw[k] = pack_hll_quad(row + 16 * l, k);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        int nonzero = 0;
-        float hsum = 0.0f;
-        if (want_cards) {
-            // A hop-1 row has at most deg + 1 non-zero registers, so nearly every row -- every one below 147 neighbours at p = 8 --
-            // is estimated by linear counting, which needs the number of zero registers and nothing else (hashing.py:221-226):
-            // that number comes out of the atomics above.  Only a wavefront holding a row that leaves the linear-counting range
-            // digests the packed registers for the harmonic sum (12 instructions per dword, a third of this kernel's VALU work).
-            nonzero = row16_sum_i(fresh);
-            const int zeros = 256 - nonzero;
-            if (__any(!(zeros > 0 && zeros >= est.lc_min_zeros))) {  // wave-uniform
-                int nz2 = 0;
-                hll_dword_stats(packed.x, nz2, hsum);
-                hll_dword_stats(packed.y, nz2, hsum);
-                hll_dword_stats(packed.z, nz2, hsum);
-                hll_dword_stats(packed.w, nz2, hsum);
-                hsum = row16_sum_f(hsum);
-            }
-        }
-        if (ok && !hub) {
-            *reinterpret_cast<u32x4 *>(hll_out + i * 256 + 16 * l) = packed;
-            mirror_hll16(g.mir, i * 256 + 16 * l, packed);
-            if (want_cards && l == 0) {
-                const float card = hll_estimate(est, 256 - nonzero, hsum);
-                cards_out[i * cards_stride] = card;
-                mirror_card(g.mir, i * cards_stride, card);
-            }
-        }
+        hll_first_hop_row16<true>(row, g.col + rbs[r], deg, total, i, nid0[r], always_valid, p, ok && !hub, hll_out, cards_out, cards_stride, est,
+                                  want_cards, l, g.mir);
     }
 }
 

@@ -138,10 +138,7 @@ __device__ __forceinline__ void table_hub_units(const GraphArgs &g, int worker, 
             if (want_cards) {
                 int nonzero = 0;
                 float hsum = 0.0f;
-                hll_dword_stats(hll_acc.x, nonzero, hsum);
-                hll_dword_stats(hll_acc.y, nonzero, hsum);
-                hll_dword_stats(hll_acc.z, nonzero, hsum);
-                hll_dword_stats(hll_acc.w, nonzero, hsum);
+                hll_chunk_stats(hll_acc, nonzero, hsum);
                 nonzero = row16_sum_i(nonzero);
                 hsum = row16_sum_f(hsum);
                 if (c == 0) {
@@ -242,6 +239,70 @@ struct FirstHopHubLds {
     int s_last, s_m;
 };
 
+// all WAVES wavefronts of the workgroup hash the neighbours t in [lo, hi) of row i (batches of 64, one batch per wave and step); the
+// combined partial rows are left in s.mh_row / s.hll_row.  Called by every thread; begins and ends with a barrier.
+// (first_hop_hub_units below: a hub row or a slice of a mega row; update_hub_first_kernel of ss_update.hip: a whole listed row)
+template <int PPL, int WAVES, bool DO_MH, bool DO_HLL>
+__device__ __forceinline__ void first_hop_hub_walk(FirstHopHubLds<PPL> &s, int64_t i, const int32_t *__restrict__ nb, int deg, int lo, int hi,
+                                                   int p, const uint64_t (&a)[PPL], const uint64_t (&b)[PPL], int lane, int wave,
+                                                   bool force_exact)
+{
+    constexpr int P = PPL * kWave, THREADS = WAVES * kWave;
+    for (int t = threadIdx.x; t < 256; t += THREADS) s.hll_row[t] = 0u;
+    for (int t = threadIdx.x; t < P; t += THREADS) s.mh_row[t] = 0xFFFFFFFFu;
+    __syncthreads();
+    uint32_t acc[PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
+    // slice = the same walk over nb + lo with the degree counted from lo (slot deg - lo is the implicit self loop)
+    if (DO_HLL) first_hop_walk<PPL, false, true>(nb + lo, deg - lo, hi - lo, i, wave, WAVES, p, a, b, acc, s.hll_row, lane);
+    if (DO_MH) {
+        // the two-phase walk (ss_walks.hpp: 4-5 instead of 10 VALU per neighbour and permutation) over this wavefront's batches; a
+        // wavefront whose share is ambiguous (duplicated minimum, key collision) redoes its share exactly
+        first_hop_minhash_row<PPL>(nb + lo, deg - lo, hi - lo, i, p, a, b, acc, lane, false, wave, WAVES, force_exact);
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) atomicMin(&s.mh_row[lane + kWave * q], acc[q]);
+    }
+    __syncthreads();
+}
+
+// wave 0 stores the finished row that the walk left in `s` (+ its cardinality): lane l takes MinHash values l, l + 64, .. and HLL
+// registers 4l .. 4l+3.  zero_mh: the MinHash row is stored as zeros (a row without in-edge and self loop -- no build hub row is
+// one, they have in-edges by definition; the update passes total == 0).  MIR: the row also goes to the peers' tables.
+template <int PPL, bool DO_MH, bool DO_HLL, bool MIR>
+__device__ __forceinline__ void first_hop_hub_finish(const FirstHopHubLds<PPL> &s, int64_t i, bool zero_mh, uint32_t *__restrict__ mh_out,
+                                                     uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride,
+                                                     const EstimatorTables &est, bool want_cards, int lane, const Mirrors &mir)
+{
+    constexpr int P = PPL * kWave;
+    uint32_t mh[PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) mh[q] = DO_MH && !zero_mh ? s.mh_row[lane + kWave * q] : 0u;
+    const uint32_t regs = DO_HLL ? pack_hll_quad(s.hll_row, lane) : 0u;
+    if (DO_MH) {
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+            mh_out[i * P + lane + kWave * q] = mh[q];
+            if constexpr (MIR) mirror_mh1(mir, i * P + lane + kWave * q, mh[q]);
+        }
+    }
+    if (DO_HLL) {
+        *reinterpret_cast<uint32_t *>(hll_out + i * 256 + 4 * lane) = regs;
+        if constexpr (MIR) mirror_hll4(mir, i * 256 + 4 * lane, regs);
+    }
+    if (DO_HLL && want_cards) {
+        int nonzero = 0;
+        float hsum = 0.0f;
+        hll_dword_stats(regs, nonzero, hsum);
+        wave_sum_stats(nonzero, hsum);
+        if (lane == 0) {
+            const float card = hll_estimate(est, 256 - nonzero, hsum);
+            cards_out[i * cards_stride] = card;
+            if constexpr (MIR) mirror_card(mir, i * cards_stride, card);
+        }
+    }
+}
+
 template <int PPL, int WAVES, bool DO_MH, bool DO_HLL>
 __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int worker, int n_workers, const uint64_t *__restrict__ pa,
                                                     const uint64_t *__restrict__ pb, uint32_t *__restrict__ mh_out, int p,
@@ -263,60 +324,11 @@ __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int work
     }
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
 
-    // all waves hash the neighbours t in [lo, hi) of row i (batches of 64, one batch per wave and step); the combined partial rows
-    // are left in s.mh_row / s.hll_row
     auto walk = [&](int64_t i, const int32_t *nb, int deg, int lo, int hi) {
-        for (int t = threadIdx.x; t < 256; t += THREADS) s.hll_row[t] = 0u;
-        for (int t = threadIdx.x; t < P; t += THREADS) s.mh_row[t] = 0xFFFFFFFFu;
-        __syncthreads();
-        uint32_t acc[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-        // slice = the same walk over nb + lo with the degree counted from lo (slot deg - lo is the implicit self loop)
-        if (DO_HLL) first_hop_walk<PPL, false, true>(nb + lo, deg - lo, hi - lo, i, wave, WAVES, p, a, b, acc, s.hll_row, lane);
-        // MinHash: the two-phase walk (ss_walks.hpp: 4-5 instead of 10 VALU per neighbour and permutation) over this wavefront's
-        // batches; a wavefront whose share is ambiguous (duplicated minimum, key collision) redoes its share exactly
-        if (DO_MH && wave * kWave < hi - lo) {  // (wave-uniform) the wavefront has at least one batch
-            const bool amb = force_exact || first_hop_minhash_fast<PPL>(nb + lo, deg - lo, hi - lo, i, a, b, acc, lane, wave, WAVES);
-            if (__any(amb)) {
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-                first_hop_walk<PPL, true, false>(nb + lo, deg - lo, hi - lo, i, wave, WAVES, p, a, b, acc, s.hll_row, lane);
-            }
-        }
-        if (DO_MH) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) atomicMin(&s.mh_row[lane + kWave * q], acc[q]);
-        }
-        __syncthreads();
+        first_hop_hub_walk<PPL, WAVES, DO_MH, DO_HLL>(s, i, nb, deg, lo, hi, p, a, b, lane, wave, force_exact);
     };
-    // wave 0 stores the finished row (+ its cardinality): lane l holds MinHash values l, l + 64, .. and HLL registers 4l .. 4l+3
-    auto finish = [&](int64_t i, const uint32_t (&mh)[PPL], uint32_t regs) {
-        if (DO_MH) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) {
-                mh_out[i * P + lane + kWave * q] = mh[q];
-                mirror_mh1(g.mir, i * P + lane + kWave * q, mh[q]);
-            }
-        }
-        if (DO_HLL) {
-            *reinterpret_cast<uint32_t *>(hll_out + i * 256 + 4 * lane) = regs;
-            mirror_hll4(g.mir, i * 256 + 4 * lane, regs);
-        }
-        if (want_cards) {
-            int nonzero = 0;
-            float hsum = 0.0f;
-            hll_dword_stats(regs, nonzero, hsum);
-            for (int off = 1; off < kWave; off <<= 1) {
-                nonzero += __shfl_xor(nonzero, off);
-                hsum += __shfl_xor(hsum, off);
-            }
-            if (lane == 0) {
-                const float card = hll_estimate(est, 256 - nonzero, hsum);
-                cards_out[i * cards_stride] = card;
-                mirror_card(g.mir, i * cards_stride, card);
-            }
-        }
+    auto finish = [&](int64_t i) {  // (no hub row is empty)
+        first_hop_hub_finish<PPL, DO_MH, DO_HLL, true>(s, i, false, mh_out, hll_out, cards_out, cards_stride, est, want_cards, lane, g.mir);
     };
 
     for (int h = worker; h < n.hubs; h += n_workers) {
@@ -326,12 +338,7 @@ __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int work
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
         walk(i, g.col + rb, deg, 0, total);
-        if (wave == 0) {
-            uint32_t mh[PPL];
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) mh[q] = DO_MH ? s.mh_row[lane + kWave * q] : 0u;
-            finish(i, mh, DO_HLL ? pack_hll_quad(s.hll_row, lane) : 0u);
-        }
+        if (wave == 0) finish(i);
         __syncthreads();
     }
 
@@ -411,11 +418,7 @@ __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int work
                 for (int k = 0; k < 4; ++k) atomicMax(&s.hll_row[4 * lane + k], (regs >> (8 * k)) & 0xFFu);
             }
             __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) mh[q] = DO_MH ? s.mh_row[lane + kWave * q] : 0u;
-                finish(i, mh, DO_HLL ? pack_hll_quad(s.hll_row, lane) : 0u);
-            }
+            if (wave == 0) finish(i);
         }
         __syncthreads();
     }

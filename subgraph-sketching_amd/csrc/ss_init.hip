@@ -33,10 +33,8 @@ __global__ __launch_bounds__(256) void hll_init_kernel(uint8_t *__restrict__ out
         const int64_t i = t >> (p - 4);
         const int64_t c = t & (chunks - 1);
         const uint64_t hv = hash_u64((uint64_t)(first_node + i + 1));
-        const uint64_t idx = hv & (((uint64_t)1 << p) - 1);
-        const uint64_t bits = hv >> p;
-        const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
-        const uint32_t rank = (uint32_t)((64 - p) - bl + 1);  // always in [1, 64-p+1]
+        const uint32_t idx = hll_register_of(hv, 1 << p);
+        const uint32_t rank = hll_rank_of(hv, p);
         u32x4 v = {0u, 0u, 0u, 0u};
         if ((int64_t)(idx >> 4) == c) {
             const uint32_t byte = (uint32_t)(idx & 15u);

@@ -19,8 +19,10 @@
 //   masked_row_zeros_kernel  (debug outputs only) the zero-register counts of the 2h stored rows of every link
 //   masked_pairs_kernel      workgroups stride over the list: the 2h masked rows of a link are built in LDS (4P + M bytes each), then
 //                            one 16-lane group runs the pair arithmetic of ss_pair_math.hpp and the feature algebra of
-//                            ss_feature_algebra.hpp on them, with the cardinalities of the masked rows from the same HLL statistics,
-//                            and overwrites the link's output row
+//                            ss_feature_algebra.hpp on them, with the cardinalities of the masked rows from hll_row16_stats +
+//                            hll_estimate -- the statistics function is shared with masked_row_zeros_kernel, the hop-0 values
+//                            (permuted_hash, hll_rank_of / hll_register_of) with the first-hop kernels of the build -- and
+//                            overwrites the link's output row
 // A workgroup walks a row with 256 / (P / 4 + M / 16) neighbours in flight (one 16-byte chunk per thread), whatever the row's length:
 // a link next to a hub is slow, never wrong.
 #include "ss_feature_algebra.hpp"
@@ -38,15 +40,6 @@ struct MaskedTables {
     const uint8_t *hll[SS_MAX_HOPS];
 };
 
-__device__ __forceinline__ bool masked_ids(const int64_t *links, int64_t q, int64_t N, int64_t &u, int64_t &v)
-{
-    u = links[2 * q];
-    v = links[2 * q + 1];
-    u = u < 0 ? u + N : u;  // torch-style negative indexing, as the plain query
-    v = v < 0 ? v + N : v;
-    return (uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N;
-}
-
 // ---- which links are edges ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kMaskedThreads) void masked_classify_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                          int64_t N, const int64_t *__restrict__ links, int64_t B,
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_classify_kernel(const i
         int hit = 0;
         if (q < B) {
             int64_t u, v;
-            if (masked_ids(links, q, N, u, v) && u != v) {
+            if (link_ids(links, q, N, u, v) && u != v) {
                 // row x of the CSR lists the sources j of the edges j -> x: v -> u sits in row u, u -> v in row v
                 const int64_t ue = rowptr[u + 1], ve = rowptr[v + 1];
                 for (int64_t e = rowptr[u] + l; e < ue && !hit; e += kRow) hit = col[e] == (int32_t)v;
@@ -92,21 +85,13 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_row_zeros_kernel(const 
     for (int64_t q0 = (int64_t)blockIdx.x * groups; q0 < B; q0 += (int64_t)gridDim.x * groups) {  // workgroup-uniform
         const int64_t q = q0 + threadIdx.x / kRow;
         int64_t u = 0, v = 0;
-        const bool ok = q < B && masked_ids(links, q, N, u, v);
+        const bool ok = q < B && link_ids(links, q, N, u, v);
         for (int side = 0; side < 2; ++side)
             for (int k = 0; k < h; ++k) {
                 const int64_t x = side ? v : u;
-                int nonzero = 0;
-                float hsum = 0.0f;
-                if (ok)
-                    for (int c = l; c < CH; c += kRow) {
-                        const u32x4 r = *reinterpret_cast<const u32x4 *>(tabs.hll[k] + x * M + 16 * c);
-                        hll_dword_stats(r.x, nonzero, hsum);
-                        hll_dword_stats(r.y, nonzero, hsum);
-                        hll_dword_stats(r.z, nonzero, hsum);
-                        hll_dword_stats(r.w, nonzero, hsum);
-                    }
-                nonzero = row16_sum_i(nonzero);
+                int nonzero;
+                float hsum;
+                hll_row16_stats(reinterpret_cast<const u32x4 *>(tabs.hll[k] + x * M), ok ? CH : 0, l, nonzero, hsum);
                 if (q < B && l == 0) row_zeros[q * (2 * h) + side * h + k] = ok ? M - nonzero : 0;
             }
     }
@@ -157,7 +142,8 @@ struct MaskedLink {
     }
 };
 
-// R1(x): MinHash and HLL first hop of x over N'(x) + x from node ids (the arithmetic of ss_init.hip / first_hop_walk)
+// R1(x): MinHash and HLL first hop of x over N'(x) + x from node ids (hop-0 values by permuted_hash and hll_rank_of / hll_register_of,
+// the helpers of the first-hop kernels)
 __device__ __forceinline__ void masked_first_hop(const MaskedLink &L, int side, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
                                                  int p, bool self)
 {
@@ -201,9 +187,7 @@ __device__ __forceinline__ void masked_first_hop(const MaskedLink &L, int side, 
         const int64_t nid = e < deg ? (int64_t)nb[e] : x;
         if (e < deg && nid == partner) continue;
         const uint64_t hv = hash_u64((uint64_t)(nid + 1));
-        const uint64_t bits = hv >> p;
-        const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
-        atomicMax(&L.regs[(uint32_t)hv & (uint32_t)(M - 1)], (uint32_t)((64 - p) - bl + 1));
+        atomicMax(&L.regs[hll_register_of(hv, M)], hll_rank_of(hv, p));
     }
     __syncthreads();
     uint32_t *dst_h = reinterpret_cast<uint32_t *>(L.row(side, 0) + L.CM);
@@ -250,7 +234,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
     for (int i = blockIdx.x; i < n; i += gridDim.x) {  // workgroup-uniform
         const int64_t q = list[i];
         int64_t u, v;
-        masked_ids(links, q, N, u, v);  // (listed links are in range and have u != v)
+        link_ids(links, q, N, u, v);  // (listed links are in range and have u != v)
         L.u = u;
         L.v = v;
         masked_first_hop(L, 0, pa, pb, p, u < n_self);
@@ -289,8 +273,8 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
                 }
             }
         }
-        // ---- the pair arithmetic on the masked rows: one 16-lane group, lane l takes chunks l, l + 16, ... (pair_features_kernel's
-        // run-time-shape path, reading LDS instead of the tables)
+        // ---- the pair arithmetic on the masked rows: one 16-lane group, lane l takes chunks l, l + 16, ... (eq4 / union_stats of
+        // ss_pair_math.hpp on LDS rows, as pair_features_kernel's run-time-shape path applies them to table rows)
         if (t < kWave) {
             const int l = t & (kRow - 1);
             const int CM = L.CM;
@@ -308,25 +292,16 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
                     mz[k1 * H + k2] = row16_sum_i((match << 20) | (16 * chunks - nonzero));
                     hs[k1 * H + k2] = row16_sum_f(hsum);
                 }
-            // cardinalities of the masked rows: the statistics of the table hops' epilogue (lane = chunk, DPP row sums)
+            // cardinalities of the masked rows (hll_row16_stats: the statistics of a finished row, as for the stored rows above)
             float c1[H], c2[H];
             int rz[2 * H];
 #pragma unroll
             for (int side = 0; side < 2; ++side)
 #pragma unroll
                 for (int k = 0; k < H; ++k) {
-                    const u32x4 *r = L.row(side, k) + CM;
-                    int nonzero = 0;
-                    float hsum = 0.0f;
-                    for (int cc = l; cc < CH; cc += kRow) {
-                        const u32x4 x = r[cc];
-                        hll_dword_stats(x.x, nonzero, hsum);
-                        hll_dword_stats(x.y, nonzero, hsum);
-                        hll_dword_stats(x.z, nonzero, hsum);
-                        hll_dword_stats(x.w, nonzero, hsum);
-                    }
-                    nonzero = row16_sum_i(nonzero);
-                    hsum = row16_sum_f(hsum);
+                    int nonzero;
+                    float hsum;
+                    hll_row16_stats(L.row(side, k) + CM, CH, l, nonzero, hsum);
                     rz[side * H + k] = L.M - nonzero;
                     const float card = hll_estimate(est, L.M - nonzero, hsum);
                     if (side == 0) c1[k] = card;

@@ -19,11 +19,7 @@ __device__ __forceinline__ int eq4(u32x4 a, u32x4 b)
 // generic path: union of two 16-register chunks -> non-zero count and harmonic sum
 __device__ __forceinline__ void union_stats(u32x4 a, u32x4 b, int &nonzero, float &hsum)
 {
-    const u32x4 m = bytemax16(a, b);
-    hll_dword_stats(m.x, nonzero, hsum);
-    hll_dword_stats(m.y, nonzero, hsum);
-    hll_dword_stats(m.z, nonzero, hsum);
-    hll_dword_stats(m.w, nonzero, hsum);
+    hll_chunk_stats(bytemax16(a, b), nonzero, hsum);
 }
 
 // fast path: a 16-register HLL chunk pre-digested once per row so that each of the h^2 unions costs

@@ -77,7 +77,7 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
     const bool q_ok = q_raw < B;
     const int64_t q = q_ok ? q_cur : B - 1;
     int64_t u = q_ok ? u_next : 0, v = q_ok ? v_next : 0;
-    u = u < 0 ? u + N : u;  // torch-style negative indexing
+    u = u < 0 ? u + N : u;  // torch-style negative indexing (the rule of link_ids, on ids that were requested an iteration ahead)
     v = v < 0 ? v + N : v;
     const bool bad = (uint64_t)u >= (uint64_t)N || (uint64_t)v >= (uint64_t)N;
     if (bad) { u = 0; v = 0; }
@@ -267,10 +267,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
         int u_l = -1, v_l = -1;
         if (l < cnt) {
             q_l = order ? (int64_t)order[base + l] : base + l;
-            int64_t u = links[2 * q_l], v = links[2 * q_l + 1];
-            u = u < 0 ? u + N : u;  // torch-style negative indexing
-            v = v < 0 ? v + N : v;
-            if ((uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N) {
+            int64_t u, v;
+            if (link_ids(links, q_l, N, u, v)) {
                 u_l = (int)u;
                 v_l = (int)v;
             } else if (err) {

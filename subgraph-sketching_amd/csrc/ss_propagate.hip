@@ -73,69 +73,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
     const int32_t *nb = g.col + rb;
 
     // ---------------- MinHash: min over neighbours ----------------
-    if (mh_out) {
-        const int CM = P >> 2;
-        const int SG = TP ? (pow2_ceil(TP >> 2) > kWave ? kWave : pow2_ceil(TP >> 2)) : (pow2_ceil(CM) > kWave ? kWave : pow2_ceil(CM));
-        const int G = kWave / SG;
-        const int sg = lane / SG, cl = lane % SG;
-        for (int cb = 0; cb < CM; cb += SG) {
-            const int c = cb + cl;
-            const bool act = c < CM;
-            u32x4 acc = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            if constexpr (TP == 128) acc = minhash_walk128(mh_in, nb, deg, total, i, lane);
-            else if (act) acc = minhash_walk(mh_in, nb, deg, total, i, sg, G, P, c);
-            for (int off = SG; off < kWave; off <<= 1) acc = min4(acc, shfl_xor4(acc, off));
-            if (total == 0) acc = u32x4{0u, 0u, 0u, 0u};
-            if (act && sg == 0) {
+    if (mh_out)
+        minhash_hop_row<TP>(mh_in, nb, deg, total, i, P, lane, 0, 1, [&](int c, bool mine, const u32x4 &acc) {
+            if (mine) {
                 *reinterpret_cast<u32x4 *>(mh_out + i * P + 4 * c) = acc;
                 mirror_mh4(g.mir, i * P + 4 * c, acc);
             }
-        }
-    }
+        });
 
     // ---------------- HLL: byte-wise max over neighbours, fused cardinality ----------------
-    if (hll_out) {
-        const int CH = M >> 4;
-        const int SG = TM ? (pow2_ceil(TM >> 4) > kWave ? kWave : pow2_ceil(TM >> 4)) : (pow2_ceil(CH) > kWave ? kWave : pow2_ceil(CH));
-        const int G = kWave / SG;
-        const int sg = lane / SG, cl = lane % SG;
-        int nonzero = 0;
-        float hsum = 0.0f;
-        for (int cb = 0; cb < CH; cb += SG) {
-            const int c = cb + cl;
-            const bool act = c < CH;
-            u32x4 acc = {0u, 0u, 0u, 0u};
-            if (act) acc = hll_walk(hll_in, nb, deg, total, i, sg, G, M, c);
-            for (int off = SG; off < kWave; off <<= 1) acc = bytemax16(acc, shfl_xor4(acc, off));
-            if (act && sg == 0) {
-                *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
-                mirror_hll16(g.mir, i * M + 16 * c, acc);
-                if (row_cards) {
-                    hll_dword_stats(acc.x, nonzero, hsum);
-                    hll_dword_stats(acc.y, nonzero, hsum);
-                    hll_dword_stats(acc.z, nonzero, hsum);
-                    hll_dword_stats(acc.w, nonzero, hsum);
+    if (hll_out)
+        hll_hop_row<TM>(
+            hll_in, nb, deg, total, i, M, lane, 0, 1, row_cards, est,
+            [&](int c, bool mine, const u32x4 &acc) {
+                if (mine) {
+                    *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
+                    mirror_hll16(g.mir, i * M + 16 * c, acc);
                 }
-            }
-        }
-        if (row_cards) {
-            // lanes of sub-group 0 hold partial stats; the rest hold 0
-            if (SG == kRow) {  // the 16 lanes of sub-group 0 are one DPP row
-                nonzero = row16_sum_i(nonzero);
-                hsum = row16_sum_f(hsum);
-            } else {
-                for (int off = 1; off < kWave; off <<= 1) {
-                    nonzero += __shfl_xor(nonzero, off);
-                    hsum += __shfl_xor(hsum, off);
-                }
-            }
-            if (lane == 0) {
-                const float card = hll_estimate(est, M - nonzero, hsum);
+                return mine;
+            },
+            [&](float card) {
                 cards_out[i * cards_stride] = card;
                 mirror_card(g.mir, i * cards_stride, card);
-            }
-        }
-    }
+            });
 }
 
 // HLL-only hop, 4 destinations per wavefront (fast path of ss_propagate when the MinHash sketch is absent)

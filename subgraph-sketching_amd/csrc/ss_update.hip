@@ -13,10 +13,13 @@
 //                list is ascending inside a workgroup's 256 rows and in arrival order between workgroups.  Rows with more in-edges than
 //                graph.hub_threshold go to a list of their own, filled from the END of the same array.
 //   row hops     persistent workgroups over rows[0 .. *n) -- the count never leaves the device -- that recompute a listed row from
-//                scratch with the walks of ss_walks.hpp: the same arithmetic, lane mapping and statistics order as the row kernels of
-//                ss_propagate.hip / ss_first_hop.hip, so a recomputed row (and its cardinality) carries the bits a rebuild would give
-//                it.  Listed hub rows are walked by one 16-wavefront workgroup each, partials combined through LDS; hub rows that are
-//                not dirty are never touched.
+//                scratch by CALLING the row bodies of the build kernels (ss_walks.hpp: minhash_hop_row, hll_hop_row, hll_hop_row16,
+//                first_hop_minhash_row, hll_first_hop_row16; ss_hub.hpp: first_hop_hub_walk / first_hop_hub_finish).  The arithmetic,
+//                the lane mapping and the order of the statistics are SHARED with ss_propagate.hip / ss_first_hop.hip, not repeated:
+//                a recomputed row (and its cardinality) carries the bits a rebuild would give it because it runs the rebuild's code,
+//                and a change to a row body changes both.  Only the output side differs (a plain store here, store + peers' tables
+//                in the build).  Listed hub rows are walked by one 16-wavefront workgroup each, partials combined through LDS; hub
+//                rows that are not dirty are never touched.
 #include "ss_hub.hpp"
 
 namespace ss {
@@ -182,7 +185,10 @@ __global__ __launch_bounds__(256) void update_mark_kernel(GraphArgs g, const uin
 // ---- row hops over a device-counted list ----------------------------------------------------------------------------------------
 __device__ __forceinline__ int uniform_row(const int32_t *__restrict__ list, int64_t q) { return __builtin_amdgcn_readfirstlane(list[q]); }
 
-// MinHash table hop, one wavefront per listed row (the MinHash half of propagate_kernel)
+// Every kernel below keeps the list indexing and the row bounds and CALLS the row bodies of the build kernels (ss_walks.hpp, ss_hub.hpp)
+// with a plain store for an output side: there is no second copy of the arithmetic here.
+
+// MinHash table hop, one wavefront per listed row
 template <int TP>
 __global__ __launch_bounds__(256) void update_minhash_rows_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                                   const uint32_t *__restrict__ mh_in, uint32_t *__restrict__ mh_out, int P_rt)
@@ -197,25 +203,13 @@ __global__ __launch_bounds__(256) void update_minhash_rows_kernel(GraphArgs g, c
         const int64_t rb = g.rowptr[i];
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
-        const int32_t *nb = g.col + rb;
-        const int CM = P >> 2;
-        const int SG = TP ? (pow2_ceil(TP >> 2) > kWave ? kWave : pow2_ceil(TP >> 2)) : (pow2_ceil(CM) > kWave ? kWave : pow2_ceil(CM));
-        const int G = kWave / SG;
-        const int sg = lane / SG, cl = lane % SG;
-        for (int cb = 0; cb < CM; cb += SG) {
-            const int c = cb + cl;
-            const bool act = c < CM;
-            u32x4 acc = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            if constexpr (TP == 128) acc = minhash_walk128(mh_in, nb, deg, total, i, lane);
-            else if (act) acc = minhash_walk(mh_in, nb, deg, total, i, sg, G, P, c);
-            for (int off = SG; off < kWave; off <<= 1) acc = min4(acc, shfl_xor4(acc, off));
-            if (total == 0) acc = u32x4{0u, 0u, 0u, 0u};
-            if (act && sg == 0) *reinterpret_cast<u32x4 *>(mh_out + i * P + 4 * c) = acc;
-        }
+        minhash_hop_row<TP>(mh_in, g.col + rb, deg, total, i, P, lane, 0, 1, [&](int c, bool mine, const u32x4 &acc) {
+            if (mine) *reinterpret_cast<u32x4 *>(mh_out + i * P + 4 * c) = acc;
+        });
     }
 }
 
-// HLL table hop + cardinality, any M, one wavefront per listed row (the HLL half of propagate_kernel)
+// HLL table hop + cardinality, any M, one wavefront per listed row
 __global__ __launch_bounds__(256) void update_hll_rows_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                               const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out, int M,
                                                               float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm)
@@ -226,42 +220,18 @@ __global__ __launch_bounds__(256) void update_hll_rows_kernel(GraphArgs g, const
     const int n = *n_ptr;
     const int waves = blockDim.x / kWave;
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
-    const int CH = M >> 4;
-    const int SG = pow2_ceil(CH) > kWave ? kWave : pow2_ceil(CH);
-    const int G = kWave / SG;
-    const int sg = lane / SG, cl = lane % SG;
     for (int64_t q = (int64_t)blockIdx.x * waves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)); q < n; q += (int64_t)gridDim.x * waves) {
         const int64_t i = uniform_row(list, q);
         const int64_t rb = g.rowptr[i];
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
-        const int32_t *nb = g.col + rb;
-        int nonzero = 0;
-        float hsum = 0.0f;
-        for (int cb = 0; cb < CH; cb += SG) {
-            const int c = cb + cl;
-            const bool act = c < CH;
-            u32x4 acc = {0u, 0u, 0u, 0u};
-            if (act) acc = hll_walk(hll_in, nb, deg, total, i, sg, G, M, c);
-            for (int off = SG; off < kWave; off <<= 1) acc = bytemax16(acc, shfl_xor4(acc, off));
-            if (act && sg == 0) {
-                *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
-                hll_dword_stats(acc.x, nonzero, hsum);
-                hll_dword_stats(acc.y, nonzero, hsum);
-                hll_dword_stats(acc.z, nonzero, hsum);
-                hll_dword_stats(acc.w, nonzero, hsum);
-            }
-        }
-        if (SG == kRow) {
-            nonzero = row16_sum_i(nonzero);
-            hsum = row16_sum_f(hsum);
-        } else {
-            for (int off = 1; off < kWave; off <<= 1) {
-                nonzero += __shfl_xor(nonzero, off);
-                hsum += __shfl_xor(hsum, off);
-            }
-        }
-        if (lane == 0) cards_out[i * cards_stride] = hll_estimate(est, M - nonzero, hsum);
+        hll_hop_row<0>(
+            hll_in, g.col + rb, deg, total, i, M, lane, 0, 1, true, est,
+            [&](int c, bool mine, const u32x4 &acc) {
+                if (mine) *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
+                return mine;
+            },
+            [&](float card) { cards_out[i * cards_stride] = card; });
     }
 }
 
@@ -281,7 +251,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void u
     }
 }
 
-// MinHash first hop from node ids, one wavefront per listed row (first_hop_kernel<PPL, true, false>)
+// MinHash first hop from node ids, one wavefront per listed row
 template <int PPL>
 __global__ __launch_bounds__(256) void update_first_minhash_rows_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                                         const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
@@ -306,21 +276,13 @@ __global__ __launch_bounds__(256) void update_first_minhash_rows_kernel(GraphArg
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
         uint32_t acc[PPL];
+        first_hop_minhash_row<PPL>(g.col + rb, deg, total, i, p, a, b, acc, lane, true);
 #pragma unroll
-        for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-        const bool amb = total > 0 && first_hop_minhash_fast<PPL>(g.col + rb, deg, total, i, a, b, acc, lane);
-        if (__any(amb)) {  // the rare ambiguous row is redone by the exact walk
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-            first_hop_walk<PPL, true, false>(g.col + rb, deg, total, i, 0, 1, p, a, b, acc, nullptr, lane);
-        }
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) mh_out[i * P + lane + kWave * q] = total == 0 ? 0u : acc[q];
+        for (int q = 0; q < PPL; ++q) mh_out[i * P + lane + kWave * q] = acc[q];
     }
 }
 
-// HLL first hop from node ids (p = 8), one 16-lane group per listed row (the row path of hll_first_hop_kernel: same LDS row image,
-// same statistics -- the zero count out of the atomics, the harmonic sum only for a wavefront that leaves the linear-counting range)
+// HLL first hop from node ids (p = 8), one 16-lane group per listed row through its LDS row image
 __global__ __launch_bounds__(256) void update_first_hll_rows_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                                     int p, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out,
                                                                     int64_t cards_stride, ss_hll_params prm)
@@ -333,7 +295,6 @@ __global__ __launch_bounds__(256) void update_first_hll_rows_kernel(GraphArgs g,
     const int n = *n_ptr;
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
     const int32_t *always_valid = reinterpret_cast<const int32_t *>(g.rowptr);
-    uint32_t *row = rows[grp];
     for (int64_t q0 = (int64_t)blockIdx.x * groups; q0 < n; q0 += (int64_t)gridDim.x * groups) {  // workgroup-uniform
         const int64_t q = q0 + grp;
         const bool ok = q < n;
@@ -342,46 +303,14 @@ __global__ __launch_bounds__(256) void update_first_hll_rows_kernel(GraphArgs g,
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = ok ? deg + (i < n_self ? 1 : 0) : 0;
         const int32_t *nb = g.col + rb;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4 *>(row + 64 * k + 4 * l) = u32x4{0u, 0u, 0u, 0u};
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        int cur = *(l < deg ? nb + l : always_valid);
-        int fresh = 0;  // registers this lane was the first to set
-        for (int t = l; t < total; t += kRow) {
-            const int nxt = *(t + kRow < deg ? nb + t + kRow : always_valid);
-            const int64_t nid = t < deg ? (int64_t)cur : i;
-            cur = nxt;
-            const uint64_t hv = hash_u64((uint64_t)(nid + 1));
-            const uint64_t bits = hv >> p;
-            const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
-            fresh += atomicMax(&row[(uint32_t)hv & 255u], (uint32_t)((64 - p) - bl + 1)) == 0u ? 1 : 0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        u32x4 packed;
-        uint32_t *pw = reinterpret_cast<uint32_t *>(&packed);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pw[k] = pack_hll_quad(row + 16 * l, k);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const int nonzero = row16_sum_i(fresh);
-        float hsum = 0.0f;
-        const int zeros = 256 - nonzero;
-        if (__any(!(zeros > 0 && zeros >= est.lc_min_zeros))) {  // wave-uniform
-            int nz2 = 0;
-            hll_dword_stats(packed.x, nz2, hsum);
-            hll_dword_stats(packed.y, nz2, hsum);
-            hll_dword_stats(packed.z, nz2, hsum);
-            hll_dword_stats(packed.w, nz2, hsum);
-            hsum = row16_sum_f(hsum);
-        }
-        if (ok) {
-            *reinterpret_cast<u32x4 *>(hll_out + i * 256 + 16 * l) = packed;
-            if (l == 0) cards_out[i * cards_stride] = hll_estimate(est, 256 - nonzero, hsum);
-        }
+        const int nid0 = *(l < deg ? nb + l : always_valid);
+        hll_first_hop_row16<false>(rows[grp], nb, deg, total, i, nid0, always_valid, p, ok, hll_out, cards_out, cards_stride, est, true, l, g.mir);
     }
 }
 
 // ---- listed hub rows: one 16-wavefront workgroup per row, entries N - 1, N - 2, ... of the list -------------------------------------
-// table hop, any P / M: wavefront w takes the neighbours w * G + sg, + 16 * G, ... of the generic walks, partials through LDS
+// table hop, any P / M: wavefront w is part w of 16 of the row bodies' neighbour walk; the wavefronts' folds of a chunk meet in `part`
+// and wavefront 0 stores the row
 __global__ __launch_bounds__(kUpdHubThreads) void update_hub_table_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                                           const uint32_t *__restrict__ mh_in, uint32_t *__restrict__ mh_out, int P,
                                                                           const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out, int M,
@@ -396,82 +325,46 @@ __global__ __launch_bounds__(kUpdHubThreads) void update_hub_table_kernel(GraphA
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
+    // the chunk's folds of all wavefronts -> wavefront 0 (a lane that holds a chunk is a lane of sub-group 0: lane = chunk lane);
+    // called by every thread; true: the lane holds the finished chunk
+    auto combine = [&](bool mine, u32x4 &acc, auto fold) {
+        if (mine) part[wave][lane] = acc;
+        __syncthreads();
+        const bool done = wave == 0 && mine;
+        if (done)
+            for (int w = 1; w < kUpdHubWaves; ++w) acc = fold(acc, part[w][lane]);
+        __syncthreads();
+        return done;
+    };
     for (int q = blockIdx.x; q < n; q += gridDim.x) {  // workgroup-uniform
         const int64_t i = list[g.N - 1 - q];
         const int64_t rb = g.rowptr[i];
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
         const int32_t *nb = g.col + rb;
-        if (mh_out) {
-            const int CM = P >> 2;
-            const int SG = pow2_ceil(CM) > kWave ? kWave : pow2_ceil(CM);
-            const int G = kWave / SG;
-            const int sg = lane / SG, cl = lane % SG;
-            for (int cb = 0; cb < CM; cb += SG) {
-                const int c = cb + cl;
-                const bool act = c < CM;
-                u32x4 acc = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-                if (act) acc = minhash_walk(mh_in, nb, deg, total, i, wave * G + sg, kUpdHubWaves * G, P, c);
-                for (int off = SG; off < kWave; off <<= 1) acc = min4(acc, shfl_xor4(acc, off));
-                if (sg == 0) part[wave][cl] = acc;
-                __syncthreads();
-                if (wave == 0 && sg == 0 && act) {
-                    for (int w = 1; w < kUpdHubWaves; ++w) acc = min4(acc, part[w][cl]);
-                    if (total == 0) acc = u32x4{0u, 0u, 0u, 0u};
-                    *reinterpret_cast<u32x4 *>(mh_out + i * P + 4 * c) = acc;
-                }
-                __syncthreads();
-            }
-        }
-        if (hll_out) {
-            const int CH = M >> 4;
-            const int SG = pow2_ceil(CH) > kWave ? kWave : pow2_ceil(CH);
-            const int G = kWave / SG;
-            const int sg = lane / SG, cl = lane % SG;
-            int nonzero = 0;
-            float hsum = 0.0f;
-            for (int cb = 0; cb < CH; cb += SG) {
-                const int c = cb + cl;
-                const bool act = c < CH;
-                u32x4 acc = {0u, 0u, 0u, 0u};
-                if (act) acc = hll_walk(hll_in, nb, deg, total, i, wave * G + sg, kUpdHubWaves * G, M, c);
-                for (int off = SG; off < kWave; off <<= 1) acc = bytemax16(acc, shfl_xor4(acc, off));
-                if (sg == 0) part[wave][cl] = acc;
-                __syncthreads();
-                if (wave == 0 && sg == 0 && act) {
-                    for (int w = 1; w < kUpdHubWaves; ++w) acc = bytemax16(acc, part[w][cl]);
-                    *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
-                    hll_dword_stats(acc.x, nonzero, hsum);
-                    hll_dword_stats(acc.y, nonzero, hsum);
-                    hll_dword_stats(acc.z, nonzero, hsum);
-                    hll_dword_stats(acc.w, nonzero, hsum);
-                }
-                __syncthreads();
-            }
-            if (wave == 0) {  // wave-uniform: the 16 (or 64) lanes of sub-group 0 hold the partial statistics, the rest 0
-                if (SG == kRow) {
-                    nonzero = row16_sum_i(nonzero);
-                    hsum = row16_sum_f(hsum);
-                } else {
-                    for (int off = 1; off < kWave; off <<= 1) {
-                        nonzero += __shfl_xor(nonzero, off);
-                        hsum += __shfl_xor(hsum, off);
-                    }
-                }
-                if (lane == 0) cards_out[i * cards_stride] = hll_estimate(est, M - nonzero, hsum);
-            }
-        }
+        if (mh_out)
+            minhash_hop_row<0>(mh_in, nb, deg, total, i, P, lane, wave, kUpdHubWaves, [&](int c, bool mine, u32x4 &acc) {
+                if (combine(mine, acc, min4)) *reinterpret_cast<u32x4 *>(mh_out + i * P + 4 * c) = acc;
+            });
+        if (hll_out)
+            hll_hop_row<0>(
+                hll_in, nb, deg, total, i, M, lane, wave, kUpdHubWaves, wave == 0, est,
+                [&](int c, bool mine, u32x4 &acc) {
+                    const bool done = combine(mine, acc, bytemax16);
+                    if (done) *reinterpret_cast<u32x4 *>(hll_out + i * M + 16 * c) = acc;
+                    return done;
+                },
+                [&](float card) { cards_out[i * cards_stride] = card; });
     }
 }
 
-// first hop from node ids: the walks and the finish of first_hop_hub_units for one whole row per workgroup
+// first hop from node ids: one whole row per workgroup through the walk and the finish of the build's hub units (ss_hub.hpp)
 template <int PPL, bool DO_MH, bool DO_HLL>
 __global__ __launch_bounds__(kUpdHubThreads) void update_hub_first_kernel(GraphArgs g, const int32_t *__restrict__ list, const int32_t *__restrict__ n_ptr,
                                                                           const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
                                                                           uint32_t *__restrict__ mh_out, int p, uint8_t *__restrict__ hll_out,
                                                                           float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm)
 {
-    constexpr int P = PPL * kWave;
     __shared__ EstimatorLds lds;
     __shared__ FirstHopHubLds<PPL> s;
     const int n = *n_ptr;
@@ -492,45 +385,9 @@ __global__ __launch_bounds__(kUpdHubThreads) void update_hub_first_kernel(GraphA
         const int64_t rb = g.rowptr[i];
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
-        const int32_t *nb = g.col + rb;
-        for (int t = threadIdx.x; t < 256; t += kUpdHubThreads) s.hll_row[t] = 0u;
-        for (int t = threadIdx.x; t < P; t += kUpdHubThreads) s.mh_row[t] = 0xFFFFFFFFu;
-        __syncthreads();
-        uint32_t acc[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-        if (DO_HLL) first_hop_walk<PPL, false, true>(nb, deg, total, i, wave, kUpdHubWaves, p, a, b, acc, s.hll_row, lane);
-        if (DO_MH && wave * kWave < total) {  // (wave-uniform) the wavefront has at least one batch
-            const bool amb = first_hop_minhash_fast<PPL>(nb, deg, total, i, a, b, acc, lane, wave, kUpdHubWaves);
-            if (__any(amb)) {
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
-                first_hop_walk<PPL, true, false>(nb, deg, total, i, wave, kUpdHubWaves, p, a, b, acc, s.hll_row, lane);
-            }
-        }
-        if (DO_MH) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) atomicMin(&s.mh_row[lane + kWave * q], acc[q]);
-        }
-        __syncthreads();
-        if (wave == 0) {
-            if (DO_MH) {
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) mh_out[i * P + lane + kWave * q] = total == 0 ? 0u : s.mh_row[lane + kWave * q];
-            }
-            if (DO_HLL) {
-                const uint32_t regs = pack_hll_quad(s.hll_row, lane);
-                *reinterpret_cast<uint32_t *>(hll_out + i * 256 + 4 * lane) = regs;
-                int nonzero = 0;
-                float hsum = 0.0f;
-                hll_dword_stats(regs, nonzero, hsum);
-                for (int off = 1; off < kWave; off <<= 1) {
-                    nonzero += __shfl_xor(nonzero, off);
-                    hsum += __shfl_xor(hsum, off);
-                }
-                if (lane == 0) cards_out[i * cards_stride] = hll_estimate(est, 256 - nonzero, hsum);
-            }
-        }
+        first_hop_hub_walk<PPL, kUpdHubWaves, DO_MH, DO_HLL>(s, i, g.col + rb, deg, 0, total, p, a, b, lane, wave, false);
+        // (the update keeps the all-zero rule for a listed row without any neighbour; the build's hub units have no such rule)
+        if (wave == 0) first_hop_hub_finish<PPL, DO_MH, DO_HLL, false>(s, i, total == 0, mh_out, hll_out, cards_out, cards_stride, est, DO_HLL, lane, g.mir);
         __syncthreads();
     }
 }

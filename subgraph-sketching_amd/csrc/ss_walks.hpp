@@ -1,4 +1,6 @@
-// ss_walks.hpp -- the neighbour walks shared by the propagation kernels (ss_propagate.hip, ss_first_hop.hip): table-reading walks (one 16-byte chunk per lane) and the table-free first-hop walk.
+// ss_walks.hpp -- the neighbour walks shared by the propagation kernels (ss_propagate.hip, ss_first_hop.hip): table-reading walks (one 16-byte chunk per lane) and the table-free first-hop walk;
+// and the ROW BODIES built on them -- one row folded by a wavefront or a 16-lane group, reduced, given its statistics and stored (minhash_hop_row, hll_hop_row, hll_hop_row16,
+// first_hop_minhash_row, hll_first_hop_row16) -- that the build kernels and the update kernels of ss_update.hip both call: an updated table equals a rebuilt one bit for bit because of that.
 #pragma once
 #include "ss_common.hpp"
 
@@ -156,6 +158,68 @@ __device__ __forceinline__ u32x4 hll_walk(const uint8_t *__restrict__ hll_in, co
     return hll_acc_result(ae, ao);
 }
 
+// ---- one table-hop row by one wavefront (propagate_kernel, and the update kernels of ss_update.hip: ONE body, so that a row
+// recomputed by an update carries the bits a rebuild gives it) ---------------------------------------------------------------
+// A 16-byte chunk per lane; the wavefront is split into G = 64 / SG sub-groups (SG = pow2 >= chunks per row, <= 64) that walk G
+// neighbours at a time, and their partial folds meet in sub-group 0 through cross-lane shuffles.  A row shared by the wavefronts of
+// a workgroup: this one is wavefront `part` of `parts` (its sub-group sg takes the neighbours part * G + sg, + parts * G, ...).
+// Every lane hands each of its chunks to emit(c, mine, acc) -- c: chunk index, mine: the lane holds the wavefront's fold of an
+// existing chunk; emit is called by all lanes, so it may contain a barrier.
+// MinHash: min over the neighbours; TP > 0: the row size at compile time (TP == 128 walks the whole row: part 0 of 1 only)
+template <int TP, typename Emit>
+__device__ __forceinline__ void minhash_hop_row(const uint32_t *__restrict__ mh_in, const int32_t *__restrict__ nb, int deg, int total,
+                                                int64_t i, int P, int lane, int part, int parts, Emit emit)
+{
+    const int CM = P >> 2;
+    const int SG = TP ? (pow2_ceil(TP >> 2) > kWave ? kWave : pow2_ceil(TP >> 2)) : (pow2_ceil(CM) > kWave ? kWave : pow2_ceil(CM));
+    const int G = kWave / SG;
+    const int sg = lane / SG, cl = lane % SG;
+    for (int cb = 0; cb < CM; cb += SG) {
+        const int c = cb + cl;
+        const bool act = c < CM;
+        u32x4 acc = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        if constexpr (TP == 128) acc = minhash_walk128(mh_in, nb, deg, total, i, lane);
+        else if (act) acc = minhash_walk(mh_in, nb, deg, total, i, part * G + sg, parts * G, P, c);
+        for (int off = SG; off < kWave; off <<= 1) acc = min4(acc, shfl_xor4(acc, off));
+        if (total == 0) acc = u32x4{0u, 0u, 0u, 0u};  // no in-edge, no self loop: all-zero row (PyG default)
+        emit(c, act && sg == 0, acc);
+    }
+}
+
+// HLL: byte-wise max over the neighbours, and -- want_card, wave-uniform -- the row's cardinality from the statistics of the chunks
+// as they are emitted: emit(c, mine, acc) returns whether the lane now holds the FINISHED chunk (it may have folded other wavefronts'
+// partials into acc); lane 0 hands the estimate to put_card.  TM > 0: the row size at compile time.
+template <int TM, typename Emit, typename PutCard>
+__device__ __forceinline__ void hll_hop_row(const uint8_t *__restrict__ hll_in, const int32_t *__restrict__ nb, int deg, int total, int64_t i,
+                                            int M, int lane, int part, int parts, bool want_card, const EstimatorTables &est, Emit emit,
+                                            PutCard put_card)
+{
+    const int CH = M >> 4;
+    const int SG = TM ? (pow2_ceil(TM >> 4) > kWave ? kWave : pow2_ceil(TM >> 4)) : (pow2_ceil(CH) > kWave ? kWave : pow2_ceil(CH));
+    const int G = kWave / SG;
+    const int sg = lane / SG, cl = lane % SG;
+    int nonzero = 0;
+    float hsum = 0.0f;
+    for (int cb = 0; cb < CH; cb += SG) {
+        const int c = cb + cl;
+        const bool act = c < CH;
+        u32x4 acc = {0u, 0u, 0u, 0u};
+        if (act) acc = hll_walk(hll_in, nb, deg, total, i, part * G + sg, parts * G, M, c);
+        for (int off = SG; off < kWave; off <<= 1) acc = bytemax16(acc, shfl_xor4(acc, off));
+        if (emit(c, act && sg == 0, acc) && want_card) hll_chunk_stats(acc, nonzero, hsum);
+    }
+    if (want_card) {
+        // the lanes of sub-group 0 hold the partial statistics, the rest 0
+        if (SG == kRow) {  // the 16 lanes of sub-group 0 are one DPP row
+            nonzero = row16_sum_i(nonzero);
+            hsum = row16_sum_f(hsum);
+        } else {
+            wave_sum_stats(nonzero, hsum);
+        }
+        if (lane == 0) put_card(hll_estimate(est, M - nonzero, hsum));
+    }
+}
+
 // the first <= 16 neighbours of a row walked by ONE 16-lane DPP row: lane c fetches neighbour id c (one coalesced 64-byte
 // load per row instead of one broadcast load per neighbour), the ids reach the other lanes through DPP row_newbcast, and
 // four row chunks are requested before the first is consumed
@@ -212,11 +276,7 @@ __device__ __forceinline__ void first_hop_walk(const int32_t *__restrict__ nb, i
         const uint64_t hv = hash_u64((uint64_t)(nid + 1));
         const uint32_t hv_lo = (uint32_t)hv, hv_hi = (uint32_t)(hv >> 32);
         // HLL (hashing.py:126-137): every lane scatters ITS neighbour's single register into the LDS row
-        if (DO_HLL && t < total) {
-            const uint64_t bits = hv >> p;
-            const int bl = bits ? 64 - __builtin_clzll(bits) : 0;
-            atomicMax(&hll_row[hv_lo & 255u], (uint32_t)((64 - p) - bl + 1));
-        }
+        if (DO_HLL && t < total) atomicMax(&hll_row[hll_register_of(hv, 256)], hll_rank_of(hv, p));
         // MinHash: walk the batch; the neighbour's hash is wave-uniform, each lane evaluates its own permutations
         if (!DO_MH) continue;
         const int cnt = total - base < kWave ? total - base : kWave;
@@ -369,6 +429,89 @@ __device__ __forceinline__ bool first_hop_minhash_fast(const int32_t *__restrict
         ambiguous |= (m1[q] < 64u) | ((m2[q] >> 6) - (m1[q] >> 6) <= 1u);
     }
     return ambiguous;
+}
+
+// ---- one first-hop row (hop 1 from node ids), shared by the build kernels and the update kernels -----------------------------------
+// MinHash by one wavefront, over its batches first_batch, first_batch + batch_stride, ...: the two-phase walk, the wavefront's share
+// redone by the exact walk when any lane flags it ambiguous (or force_exact), `acc` left at 0xFFFFFFFF when the wavefront has no batch.
+// zero_empty: a row without in-edge and self loop becomes the all-zero row (PyG default) -- for a wavefront that owns the whole row.
+template <int PPL>
+__device__ __forceinline__ void first_hop_minhash_row(const int32_t *__restrict__ nb, int deg, int total, int64_t self_row, int p,
+                                                      const uint64_t (&a)[PPL], const uint64_t (&b)[PPL], uint32_t (&acc)[PPL], int lane,
+                                                      bool zero_empty, int first_batch = 0, int batch_stride = 1, bool force_exact = false)
+{
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
+    if (first_batch * kWave < total) {  // (wave-uniform) the wavefront has at least one batch
+        const bool amb = force_exact || first_hop_minhash_fast<PPL>(nb, deg, total, self_row, a, b, acc, lane, first_batch, batch_stride);
+        if (__any(amb)) {
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
+            first_hop_walk<PPL, true, false>(nb, deg, total, self_row, first_batch, batch_stride, p, a, b, acc, nullptr, lane);
+        }
+    }
+    if (zero_empty && total == 0) {
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) acc[q] = 0u;
+    }
+}
+
+// HLL (p = 8) by one 16-lane group through its LDS row image `row` (256 words, touched by this group alone): every lane scatters
+// its neighbours' single registers with LDS atomics, then lane l packs registers 16l .. 16l+15, stores them and -- want_cards --
+// lane 0 the cardinality.  nid0: the id of the lane's first neighbour (col[l], requested by the caller, who may do so rows ahead);
+// always_valid: a word that lanes past the row's end may load; total = 0 with write = false: a group without a row to write.
+// MIR: the row also goes to the peers' tables.
+template <bool MIR>
+__device__ __forceinline__ void hll_first_hop_row16(uint32_t *row, const int32_t *__restrict__ nb, int deg, int total, int64_t i, int nid0,
+                                                    const int32_t *always_valid, int p, bool write, uint8_t *__restrict__ hll_out,
+                                                    float *__restrict__ cards_out, int64_t cards_stride, const EstimatorTables &est,
+                                                    bool want_cards, int l /* lane & 15 */, const Mirrors &mir)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4 *>(row + 64 * k + 4 * l) = u32x4{0u, 0u, 0u, 0u};
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // (the id of the lane's NEXT neighbour is requested before the current one is hashed -- unconditionally, from an address
+    // that always exists: rows of more than 16 neighbours otherwise pay one exposed round trip per 16 neighbours)
+    int cur = nid0;
+    int fresh = 0;  // registers this lane was the FIRST to set (the LDS atomic returns what was there: 0 exactly once per register)
+    for (int t = l; t < total; t += kRow) {
+        const int nxt = *(t + kRow < deg ? nb + t + kRow : always_valid);
+        const int64_t nid = t < deg ? (int64_t)cur : i;
+        cur = nxt;
+        const uint64_t hv = hash_u64((uint64_t)(nid + 1));
+        fresh += atomicMax(&row[hll_register_of(hv, 256)], hll_rank_of(hv, p)) == 0u ? 1 : 0;  // (ranks are >= 1)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // lane l owns registers 16l .. 16l+15
+    u32x4 packed;
+    uint32_t *pw = reinterpret_cast<uint32_t *>(&packed);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pw[k] = pack_hll_quad(row + 16 * l, k);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    int nonzero = 0;
+    float hsum = 0.0f;
+    if (want_cards) {
+        // A hop-1 row has at most deg + 1 non-zero registers, so nearly every row -- every one below 147 neighbours at p = 8 --
+        // is estimated by linear counting, which needs the number of zero registers and nothing else (hashing.py:221-226):
+        // that number comes out of the atomics above.  Only a wavefront holding a row that leaves the linear-counting range
+        // digests the packed registers for the harmonic sum (12 instructions per dword, a third of this kernel's VALU work).
+        nonzero = row16_sum_i(fresh);
+        const int zeros = 256 - nonzero;
+        if (__any(!(zeros > 0 && zeros >= est.lc_min_zeros))) {  // wave-uniform
+            int nz2 = 0;
+            hll_chunk_stats(packed, nz2, hsum);
+            hsum = row16_sum_f(hsum);
+        }
+    }
+    if (write) {
+        *reinterpret_cast<u32x4 *>(hll_out + i * 256 + 16 * l) = packed;
+        if constexpr (MIR) mirror_hll16(mir, i * 256 + 16 * l, packed);
+        if (want_cards && l == 0) {
+            const float card = hll_estimate(est, 256 - nonzero, hsum);
+            cards_out[i * cards_stride] = card;
+            if constexpr (MIR) mirror_card(mir, i * cards_stride, card);
+        }
+    }
 }
 
 // ---- MinHash first hop of R consecutive rows by one wavefront (first_hop_rows_kernel, fused_hop_persistent_kernel) ------
@@ -589,10 +732,7 @@ __device__ __forceinline__ void hll_row16_finish(int64_t i, bool write, const in
     int nonzero = 0;
     float hsum = 0.0f;
     if (want_cards) {
-        hll_dword_stats(acc.x, nonzero, hsum);
-        hll_dword_stats(acc.y, nonzero, hsum);
-        hll_dword_stats(acc.z, nonzero, hsum);
-        hll_dword_stats(acc.w, nonzero, hsum);
+        hll_chunk_stats(acc, nonzero, hsum);
         nonzero = row16_sum_i(nonzero);
         hsum = row16_sum_f(hsum);
     }
