@@ -263,6 +263,28 @@ int ss_pair_features_grouped(const int64_t *links, const int32_t *order, int64_t
                              const float *cards, int64_t cards_stride, const ss_hll_params *prm, uint32_t flags,
                              const float *degrees, float *out, int32_t *err_flag, void *stream);
 
+/* One score per pair instead of its feature row: the structure-feature head both reference models put behind the row --
+ * x = relu(bn_labels(label_lin_layer(sf))), then the label branch's columns of lin (models/elph.py:73-86 LinkPredictor.forward,
+ * :324-352 BUDDY.forward) -- computed by the 16 lanes that have just assembled the row, which is never written.  Inference only:
+ * BatchNorm in eval mode, folded into the linear layer by the caller:
+ *     out[q] = bias + sum_j w2[j] * max(0, shift[j] + sum_i w1[j * dim + i] * x_q[i]),
+ *   x_q = the row ss_pair_features (normalised == 0, dim = h(h+2)) or ss_pair_features_normalised (normalised != 0, dim = 2h(h+2),
+ *   degrees required; without `normalised` degrees must be NULL) writes for pair q.  Sums run i ascending through fmaf, hidden
+ *   units in a fixed tree: a pair's score is bit-identical whatever B, `order` or the launch.
+ *   w1 [dim, dim] / shift [dim] / w2 [dim]: device fp32.  order (nullable): as ss_pair_features_grouped.  out: device fp32 [B],
+ *   out[q] = pair q whatever the order; an id outside [-N, N) sets *err_flag (nullable) and gives NaN. */
+typedef struct ss_structure_head {
+    int32_t dim;
+    int32_t normalised;
+    const float *w1;
+    const float *shift;
+    const float *w2;
+    float bias;
+} ss_structure_head;
+int ss_pair_scores(const int64_t *links, const int32_t *order, int64_t B, int64_t N, int32_t h, const uint32_t *const *mh, int32_t P,
+                   const uint8_t *const *hll, const float *cards, int64_t cards_stride, const ss_hll_params *prm, uint32_t flags,
+                   const float *degrees, const ss_structure_head *head, float *out, int32_t *err_flag, void *stream);
+
 /* Weighted common-neighbour scores of node pairs -- the other per-link precompute of HashDataset.__init__ (SURVEY 8(f)
  * row N4; reference datasets/elph.py:76-77,314 calling heuristics.py:51-70 RA; CN heuristics.py:10-27 and AA :30-48
  * are the same sum with another multiplier):

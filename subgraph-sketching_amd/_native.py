@@ -42,6 +42,11 @@ class PprGraphStruct(ctypes.Structure):
                 ('hub_rows', c_void_p), ('hub_seg', c_void_p), ('seg_hub', c_void_p), ('n_hubs', c_int64), ('n_segments', c_int64)]
 
 
+class StructureHeadStruct(ctypes.Structure):
+    """mirror of `struct ss_structure_head`"""
+    _fields_ = [('dim', c_int32), ('normalised', c_int32), ('w1', c_void_p), ('shift', c_void_p), ('w2', c_void_p), ('bias', c_float)]
+
+
 PPR_SEGMENT, PPR_MAX_COLUMNS = 256, 4096  # SS_PPR_SEGMENT / SS_PPR_MAX_COLUMNS of include/subgraph_sketch.h
 ABI_VERSION = 129  # ss_version() of the library this module's struct mirrors and signatures describe
 PROF_MINHASH_HOP, PROF_HLL_HOP, PROF_FIRST_HOP_MH, PROF_FIRST_HOP_HLL, PROF_PAIRS, PROF_CSR, PROF_HUB, PROF_FUSED, PROF_MINHASH_ROWS = range(9)  # SS_PROF_* tags
@@ -83,6 +88,8 @@ SIGNATURES = {
     'ss_pair_features_grouped_kernel': (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32, POINTER(c_void_p), c_int32,
                                                   POINTER(c_void_p), c_void_p, c_int64, POINTER(HllParams), c_uint32, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+    'ss_pair_scores': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, POINTER(c_void_p), c_int32, POINTER(c_void_p), c_void_p,
+                                 c_int64, POINTER(HllParams), c_uint32, c_void_p, POINTER(StructureHeadStruct), c_void_p, c_void_p, c_void_p]),
     'ss_common_neighbour_scores': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                              c_void_p]),
     'ss_common_neighbour_scores_f32': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,

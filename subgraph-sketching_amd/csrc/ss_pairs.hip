@@ -16,7 +16,10 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <type_traits>
+
 #include "ss_feature_algebra.hpp"
+#include "ss_head.hpp"
 #include "ss_pair_math.hpp"
 
 namespace ss {
@@ -36,18 +39,24 @@ struct PairTables {
 // evaluation lists 4 267-4 297 -> 3 962 us per 8 M links: the first node's rows come from the L2, a fifth wavefront hides more of what
 // is left); on uniformly random pairs the same budget is level to 9 % slower (HBM-resident tables, B = 262 144: 143 -> 157 us), so
 // ss_pair_features keeps the default budget; six / five wavefronts spill in earnest (+25 %).
-template <int H, int TP, int TM, bool OCC = false>
+// Head... (ss_pair_scores, ss_head.hpp): empty -- the feature query, this very signature -- or ONE HeadArgs: the same walk
+// up to and including assemble_features, then the structure-feature head instead of the row.  `out` is then float [B], one score per
+// pair, the dbg_* pointers are null and degrees non-null <=> the head takes the degree-normalised copy too; the head's parameters
+// are staged into LDS with the estimator tables.  One source for the pair body; with an empty pack nothing of the head is instantiated.
+template <int H, int TP, int TM, bool OCC = false, typename... Head>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC ? (H == 2 ? 5 : H == 3 ? 4 : 1) : 1)))
 void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t N, PairTables tabs,
                                                             int P_rt, int M_rt, const float *__restrict__ cards, int64_t cards_stride,
                                                             ss_hll_params prm, uint32_t flags, float *__restrict__ out,
                                                             int32_t *__restrict__ dbg_match, int32_t *__restrict__ dbg_zero,
                                                             float *__restrict__ dbg_inter, int32_t *__restrict__ err,
-                                                            const float *__restrict__ degrees, const int32_t *__restrict__ order)
+                                                            const float *__restrict__ degrees, const int32_t *__restrict__ order, Head... head)
 {
+    constexpr bool HEAD = sizeof...(Head) != 0;
     // order (nullable): position t of the walk is pair order[t] (ss_pair_features_grouped: pairs with the same first node are
     // consecutive positions, i.e. neighbouring lane groups of one workgroup -- their rows of u meet in the CU's L1 / the L2)
     __shared__ EstimatorLds lds;
+    __shared__ typename std::conditional<HEAD, HeadLds, char>::type head_lds;  // (the feature kernels never touch it: no LDS of theirs)
     // the estimator tables are staged into LDS AFTER the first pair's sketch rows have been requested (first loop iteration
     // below): their 2.6 KB come out of the L2 while the 12 KiB of rows per wavefront travel, instead of 2 us before them
     EstimatorTables est = {};
@@ -110,6 +119,7 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
         q_cur = q_next;
         if (q_raw + 2 * stride < B) q_next = order ? (int64_t)order[q_raw + 2 * stride] : q_raw + 2 * stride;  // one position further ahead
         if (!staged) {  // workgroup-uniform (the trip count is): the barrier inside is reached by every thread
+            if constexpr (HEAD) stage_head(head_lds, the_head(head...));  // (no barrier of its own: the one inside stage_tables)
             est = stage_tables(lds, prm);
             staged = true;
         }
@@ -152,6 +162,7 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
         q_cur = q_next;
         if (q_raw + 2 * stride < B) q_next = order ? (int64_t)order[q_raw + 2 * stride] : q_raw + 2 * stride;
         if (!staged) {
+            if constexpr (HEAD) stage_head(head_lds, the_head(head...));
             est = stage_tables(lds, prm);
             staged = true;
         }
@@ -203,6 +214,24 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
 #pragma unroll
     for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
     if (bad) my_f = __uint_as_float(0x7FC00000u);
+    if constexpr (HEAD) {
+        // every lane of the row holds f[]: the head runs where the row would have been stored.  The normalised copy of feature l is
+        // computed in lane l exactly as the epilogue below computes it (a pair past the end or out of range reads node 0's degree)
+        float normed = 0.0f;
+        if (degrees) {
+            const float normaliser = sqrtf(degrees[u] * degrees[v]);
+            normed = my_f / normaliser;
+            if (isnan(normed) || isinf(normed)) normed = 0.0f;
+        }
+        const HeadArgs &hd = the_head(head...);
+        float score = head_score<NF>(head_lds, hd.dim, hd.bias, f, normed, degrees != nullptr, l, row_base);
+        if (bad) score = __uint_as_float(0x7FC00000u);
+        if (q_ok && l == 0) {
+            out[q] = score;
+            if (bad && err) *err = 1;
+        }
+        continue;
+    }
     if (q_ok && degrees) {
         // fused BUDDY._append_degree_normalised (reference models/elph.py:276-293): rows become [f, f / sqrt(d_u * d_v)]
         // with NaN / Inf (zero-degree nodes) replaced by 0
@@ -395,11 +424,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
     }
 }
 
-template <int H, int TP, int TM>
+// HEAD: the kernel with *head behind its arguments (ss_pair_scores) -- the same grid and the same choice of register budget
+template <int H, int TP, int TM, bool HEAD = false>
 int launch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &tabs, int P, int M, const float *cards,
                  int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
                  int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
-                 bool grouped = false)
+                 bool grouped = false, const HeadArgs *head = nullptr)
 {
     const int pairs_per_block = 256 / kRow;
     // pairs per 16-lane group the grid is sized for: ONE while that still fits the chip in a single round of workgroups (ELPH
@@ -427,7 +457,14 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &t
     const bool occ = occ_env >= 0 ? occ_env != 0 : (grouped || small_launch);
     {
         ProfileSpan span(stream, SS_PROF_PAIRS, true);
-        if (occ && TP == 128 && H >= 2)
+        if constexpr (HEAD) {
+            if (occ && TP == 128 && H >= 2)
+                span.launch(pair_features_kernel<H, TP, TM, (TP == 128 && H >= 2), HeadArgs>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P,
+                            M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order, *head);
+            else
+                span.launch(pair_features_kernel<H, TP, TM, false, HeadArgs>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards,
+                            cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order, *head);
+        } else if (occ && TP == 128 && H >= 2)
             span.launch(pair_features_kernel<H, TP, TM, (TP == 128 && H >= 2)>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards,
                         cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order);
         else
@@ -438,23 +475,23 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &t
     return SS_OK;
 }
 
-template <int H>
+template <int H, bool HEAD = false>
 int dispatch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &tabs, int P, int M, const float *cards,
                    int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
                    int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
-                   bool grouped = false)
+                   bool grouped = false, const HeadArgs *head = nullptr)
 {
 #define SS_PAIRS_FAST(TP)                                                                                                      \
     if (P == TP && M == 256)                                                                                                    \
-        return launch_pairs<H, TP, 256>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero,     \
-                                        dbg_inter, err, degrees, stream, order, grouped);
+        return launch_pairs<H, TP, 256, HEAD>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, \
+                                              dbg_inter, err, degrees, stream, order, grouped, head);
     SS_PAIRS_FAST(128)  // the reference's default shape
     SS_PAIRS_FAST(64)   // the other permutation counts the first hop is specialised for (ss_first_hop: P / 64 = 1 .. 4)
     SS_PAIRS_FAST(192)
     SS_PAIRS_FAST(256)
 #undef SS_PAIRS_FAST
-    return launch_pairs<H, 0, 0>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter,
-                                 err, degrees, stream, order, grouped);
+    return launch_pairs<H, 0, 0, HEAD>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter,
+                                       err, degrees, stream, order, grouped, head);
 }
 
 template <int H, int TP>
@@ -524,6 +561,43 @@ static int pair_features_impl(const int64_t *links, int64_t B, int64_t N, int32_
         case 1: return dispatch_pairs<1>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
         case 2: return dispatch_pairs<2>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
         default: return dispatch_pairs<3>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
+    }
+}
+
+// One score per pair: the structure-feature head of both reference models (models/elph.py:73-86 LinkPredictor.forward, :324-352
+// BUDDY.forward -- label_lin_layer, bn_labels in eval mode, ReLU, the label branch's columns of lin) behind the ordinary walk, so
+// that no feature row is ever written.  head->w1 / shift / w2 are device arrays of the BatchNorm-folded parameters (ss_head.hpp).
+extern "C" int ss_pair_scores(const int64_t *links, const int32_t *order, int64_t B, int64_t N, int32_t h, const uint32_t *const *mh,
+                              int32_t P, const uint8_t *const *hll, const float *cards, int64_t cards_stride, const ss_hll_params *prm,
+                              uint32_t flags, const float *degrees, const ss_structure_head *head, float *out, int32_t *err_flag,
+                              void *stream)
+{
+    using namespace ss;
+    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
+    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
+    if (B == 0) return SS_OK;
+    const int rc = check_params(prm);
+    if (rc != SS_OK) return rc;
+    if (N == 0 || !links || !mh || !hll || !cards || !head || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
+    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
+    if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices)
+    const int nf = h * (h + 2);
+    if (head->dim != (head->normalised ? 2 * nf : nf) || !head->w1 || !head->shift || !head->w2) return SS_ERR_INVALID_ARG;
+    if ((head->normalised != 0) != (degrees != nullptr)) return SS_ERR_INVALID_ARG;  // the head's width decides, not the pointer
+    PairTables tabs = {};
+    for (int k = 0; k < h; ++k) {
+        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
+        tabs.mh[k] = mh[k];
+        tabs.hll[k] = hll[k];
+    }
+    const HeadArgs args = {head->w1, head->shift, head->w2, head->bias, head->dim};
+    const int M = 1 << prm->p;
+    hipStream_t s = (hipStream_t)stream;
+    const bool grouped = order != nullptr;  // a walk with locality: the capped register budget, as ss_pair_features_grouped
+    switch (h) {
+        case 1: return dispatch_pairs<1, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
+        case 2: return dispatch_pairs<2, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
+        default: return dispatch_pairs<3, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
     }
 }
 

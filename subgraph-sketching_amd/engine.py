@@ -413,11 +413,9 @@ class ElphHashes(object):
                 raise ValueError('hash tables of different hops must have the same shape')
         return mh, hll, N, P
 
-    def _pair_kernel(self, links, hash_table, cards, want_debug=False, degrees=None, floor_sf=None, group_batch=None, out=None):
-        """runs ss_pair_features for links [B,2]; returns (features [B,nf] (or [B,2nf] with degrees) on device, debug dict or None).
-        group_batch: the links are first grouped by their first node and walked in that order, `group_batch` pairs per launch
-        (knobs.GROUP_LINKS_MIN; same rows, in the caller's order).  out: the rows are written THERE (a contiguous float32
-        [B, width] tensor on the compute device -- a slice of a larger result, dist.sharded_precompute) instead of a fresh tensor"""
+    def _query_inputs(self, links, hash_table, cards, degrees, floor_sf, out, out_width, what):
+        """what every launch of the pair kernel takes, resolved once per call (the feature query and score_links share it);
+        out_width: columns per link of a caller-supplied `out` (None: one float per link, a 1-D tensor)"""
         # where the links live, else where the packed tables already are, else cards, else the current device
         first = hash_table.get(1) if hasattr(hash_table, 'get') else None
         device = _compute_device(links, first.mh_u32 if isinstance(first, HopSketch) else None, cards)
@@ -447,15 +445,14 @@ class ElphHashes(object):
                 raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
             if cd.stride(1) != 1:
                 cd = cd.contiguous()
-        nf = h * (h + 2)
-        width = 2 * nf if degrees is not None else nf
-        if out is not None and (out.device != device or out.dtype != torch.float32 or tuple(out.shape) != (B, width) or not out.is_contiguous()):
-            raise ValueError(f'out must be a contiguous float32 [{B}, {width}] tensor on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}')
+        shape = (B,) if out_width is None else (B, out_width)
+        if out is not None and (out.device != device or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f'out must be a contiguous float32 {list(shape)} tensor on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}')
         mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
         hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
         floor = self.floor_sf if floor_sf is None else floor_sf  # DeviceFeatureStore records HashDataset's post-hoc floor
         flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if floor else 0)
-        strict, err = self._bounds(device, f'get_subgraph_features({B} links, num_nodes={N})')
+        strict, err = self._bounds(device, f'{what}({B} links, num_nodes={N})')
         if strict:
             err = _error_flag(device)  # (non-strict launches never touch the shared flag)
         dg = None
@@ -463,6 +460,18 @@ class ElphHashes(object):
             dg = degrees.to(device=device, dtype=torch.float32).contiguous()
             if dg.dim() != 1 or dg.numel() != N:
                 raise ValueError(f'degrees must have shape [{N}], got {tuple(dg.shape)}')
+        return device, params, lk, (mh, hll), mh_ptrs, hll_ptrs, N, P, B, cd, flags, strict, err, dg
+
+    def _pair_kernel(self, links, hash_table, cards, want_debug=False, degrees=None, floor_sf=None, group_batch=None, out=None):
+        """runs ss_pair_features for links [B,2]; returns (features [B,nf] (or [B,2nf] with degrees) on device, debug dict or None).
+        group_batch: the links are first grouped by their first node and walked in that order, `group_batch` pairs per launch
+        (knobs.GROUP_LINKS_MIN; same rows, in the caller's order).  out: the rows are written THERE (a contiguous float32
+        [B, width] tensor on the compute device -- a slice of a larger result, dist.sharded_precompute) instead of a fresh tensor"""
+        h = self.max_hops
+        nf = h * (h + 2)
+        width = 2 * nf if degrees is not None else nf
+        device, params, lk, _tables, mh_ptrs, hll_ptrs, N, P, B, cd, flags, strict, err, dg = self._query_inputs(
+            links, hash_table, cards, degrees, floor_sf, out, width, 'get_subgraph_features')
         if group_batch and not want_debug and 1 < B < (1 << 31) and N < (1 << 31):
             # a list that already has its runs (a coalesced edge list, an evaluation set listing every source's negatives together)
             # is walked as it is: grouping it again costs ~8 % and scatters the output rows.  One small reduction + ONE host read
@@ -524,6 +533,104 @@ class ElphHashes(object):
         if strict and B > 0 and _take_error(device):
             raise IndexError(f'links refer to nodes outside [-{N}, {N})')
         return out, dbg
+
+    def _score_kernel(self, links, hash_table, cards, head, degrees=None, group_batch=None, out=None):
+        """runs ss_pair_scores for links [B,2]: float32 [B] on the compute device.  group_batch / out: as _pair_kernel"""
+        device, params, lk, _tables, mh_ptrs, hll_ptrs, N, P, B, cd, flags, strict, err, dg = self._query_inputs(
+            links, hash_table, cards, degrees, None, out, None, 'score_links')
+        h = self.max_hops
+        hd = head._device(device)
+        lib = _native.lib()
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float32, device=device)
+
+        def launch(lk_ptr, order_ptr, nb, out_ptr):
+            _native.check(lib.ss_pair_scores(lk_ptr, order_ptr, nb, N, h, mh_ptrs, P, hll_ptrs, _ptr(cd), cd.stride(0), byref(params.struct),
+                                             flags, _ptr(dg), byref(hd.struct), out_ptr, _ptr(err), _stream(device)), 'ss_pair_scores')
+
+        if group_batch and 1 < B < (1 << 31) and N < (1 << 31):
+            # the walk of get_subgraph_features over a large link set, one float per link instead of a row: grouped by first node
+            # unless the list already has its runs (one host read), gathered / scattered around the launch for sets of gigabytes
+            mode = getattr(self, 'group_links', 'auto')
+            if mode == 'auto':
+                mode = float((lk[1:, 0] == lk[:-1, 0]).sum().item()) < 0.5 * (B - 1)
+            order = group_links_by_source(lk, N, device) if mode else None
+            for s0 in range(0, B, group_batch):
+                nb = min(group_batch, B - s0)
+                with _Span('pair_scores', device):
+                    if order is not None and B >= knobs.GROUP_GATHER_MIN:
+                        o = c_void_p(order.data_ptr() + 4 * s0)
+                        lk_c = torch.empty((nb, 2), dtype=torch.int64, device=device)
+                        sc_c = torch.empty((nb,), dtype=torch.float32, device=device)
+                        _native.check(lib.ss_gather_links(_ptr(lk), o, nb, _ptr(lk_c), _stream(device)), 'ss_gather_links')
+                        launch(_ptr(lk_c), None, nb, _ptr(sc_c))
+                        _native.check(lib.ss_scatter_feature_rows(_ptr(sc_c), o, nb, 1, _ptr(out), _stream(device)), 'ss_scatter_feature_rows')
+                    elif order is not None:  # every launch writes out[order[s0 + t]] of the ONE output tensor
+                        launch(_ptr(lk), c_void_p(order.data_ptr() + 4 * s0), nb, _ptr(out))
+                    else:                    # as listed: a slice of the links and the matching slice of the output
+                        launch(c_void_p(lk.data_ptr() + 16 * s0), None, nb, c_void_p(out.data_ptr() + 4 * s0))
+        else:
+            with _Span('pair_scores', device):
+                launch(_ptr(lk), None, B, _ptr(out))
+        if strict and B > 0 and _take_error(device):
+            raise IndexError(f'links refer to nodes outside [-{N}, {N})')
+        return out
+
+    def score_links(self, links, hash_table, cards, head, degrees=None, batch_size=11000000, out=None, **unsupported):
+        """one float per link: the structure-feature head of a trained model applied to the row get_subgraph_features would return,
+        inside the pair kernel -- the row is never written (csrc/ss_head.hpp).  For link q
+
+            score[q] = b2 + sum_j w2[j] * max(0, t'[j] + sum_i W'[j][i] * x_q[i]),
+
+        x_q = exactly the row get_subgraph_features(links, hash_table, cards, degrees=degrees) holds for q (same use_zero_one /
+        floor_sf flags, NaN / Inf -> 0 rule of the normalised half and negative-id wrapping).  For a model without node features,
+        embeddings and RA this is its eval-mode logit; for every other model the label branch's exact share of it (INTEGRATION.md
+        shows the three lines that add the rest).
+        @param head: a `StructureHead` (head.py) whose dim matches max_hash_hops; head.normalised requires `degrees`, and `degrees`
+               without it is a ValueError
+        @param degrees: float tensor [N], as get_subgraph_features takes it
+        @param batch_size: pairs per kernel launch (scores do not depend on it, bit for bit)
+        @param out: optional contiguous float32 [n_links] tensor on the compute device the scores are written into
+        @return: float32 [n_links] on links.device; an id outside [-N, N) gives NaN and is reported as get_subgraph_features
+                 reports it, in every strict_bounds mode
+        Inference only -- there are no gradients.  Out of scope (ValueError where an argument suggests otherwise): a head on the
+        masked query (mask_target), lazy stores, dist.sharded_precompute, a head inside topk_candidates.  No CPU fallback."""
+        from .head import StructureHead
+        if unsupported:
+            names = ', '.join(sorted(unsupported))
+            raise ValueError(f'score_links does not take {names}: the head runs behind the plain query only (no mask_target, no lazy store)')
+        if not isinstance(head, StructureHead):
+            raise ValueError(f'head must be a StructureHead (StructureHead.from_module(model)), got {type(head).__name__}')
+        if head.hops != self.max_hops:
+            raise ValueError(f'head.dim = {head.dim} belongs to max_hash_hops = {head.hops}, this engine has max_hash_hops = {self.max_hops}')
+        if head.normalised and degrees is None:
+            raise ValueError('head.normalised: the head takes the degree-normalised copy of the row, give degrees')
+        if degrees is not None and not head.normalised:
+            raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
+        if links.dim() == 1:
+            links = links.unsqueeze(0)
+        _native.lib()  # (NativeLibraryMissing before anything else is touched)
+        n = links.size(0)
+        batch_size = max(int(batch_size), 1)
+        if knobs.GROUP_LINKS_MIN and n >= knobs.GROUP_LINKS_MIN and n < (1 << 31):
+            scores = self._score_kernel(links, hash_table, cards, head, degrees=degrees, group_batch=batch_size, out=out)
+        elif n <= batch_size:
+            scores = self._score_kernel(links, hash_table, cards, head, degrees=degrees, out=out)
+        elif out is not None:
+            if out.dim() != 1 or out.size(0) != n or not out.is_contiguous():
+                raise ValueError(f'out must be a contiguous float32 [{n}] tensor on the compute device, got {out.dtype} {tuple(out.shape)}')
+            for s in range(0, n, batch_size):
+                self._score_kernel(links[s:s + batch_size], hash_table, cards, head, degrees=degrees, out=out[s:s + batch_size])
+            scores = out
+        else:
+            scores = torch.cat([self._score_kernel(links[s:s + batch_size], hash_table, cards, head, degrees=degrees)
+                                for s in range(0, n, batch_size)], dim=0)
+        if scores.device == links.device or out is not None:
+            return scores
+        res = scores.to(links.device)
+        if self.strict_bounds == 'deferred':  # the copy back has waited for the launches: the report is final (as get_subgraph_features)
+            self._deferred.raise_if_set()
+        return res
 
     def _get_intersections(self, edge_list, hash_table):
         """set-intersection estimates jaccard * union for every (k1, k2) (reference :167-189).

@@ -25,6 +25,7 @@ from .containers import (PACKED_FORMAT, HopSketch, LazyMinhash, SketchTable, _pa
 from .csr import CsrGraph, _CsrCache, _default_csr_cache, build_csr, default_hub_threshold, group_links_by_source  # noqa: F401
 from .propagation import HllPropagation, MinhashPropagation, _first_hop_from_ids, _hop0_marker, _propagate  # noqa: F401
 from .engine import LABEL_LOOKUP, ElphHashes  # noqa: F401
+from .head import StructureHead  # noqa: F401
 
 _KNOBS = ('KERNEL_TIMER', 'GROUP_LINKS_MIN', 'GROUP_GATHER_MIN', 'LAZY_MINHASH', 'DEFER_FIRST_HOP', 'DEFER_TABLE_HOP', 'HUB_THRESHOLD',
           'REUSE_CSR_BY_CONTENT', 'FUSED_STAGE_MAX_TABLE_BYTES')

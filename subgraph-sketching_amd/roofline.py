@@ -106,6 +106,23 @@ def pair_bytes(P=128, p=8, h=2):
     return 2 * h * (4 * P + (1 << p)) + 16 + 8 * h + 4 * h * (h + 2)
 
 
+def score_pair_bytes(P=128, p=8, h=2, normalised=False):
+    """per pair of the scoring launch (ss_pair_scores): the query's bytes with ONE fp32 score stored instead of the
+    h(h+2) features; with `normalised` the two fp32 degrees are read as the normalised query reads them.  The head's parameters
+    (<= 3.8 KB, staged into LDS once per workgroup out of the L2) are not per-pair bytes."""
+    return 2 * h * (4 * P + (1 << p)) + 16 + 8 * h + 4 + (8 if normalised else 0)
+
+
+def pair_query_bytes(pairs, P=128, p=8, h=2):
+    """bytes of get_subgraph_features over `pairs` links walked as listed: pairs * pair_bytes()"""
+    return pairs * pair_bytes(P, p, h)
+
+
+def score_query_bytes(pairs, P=128, p=8, h=2, normalised=False):
+    """bytes of score_links over `pairs` links walked as listed: pairs * score_pair_bytes()"""
+    return pairs * score_pair_bytes(P, p, h, normalised)
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
