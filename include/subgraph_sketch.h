@@ -364,6 +364,18 @@ int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const uint32_t *m
 int ss_topk_exclude(const int64_t *sources, int32_t S, int64_t N, const int64_t *rowptr, const int32_t *col, int64_t *keys,
                     size_t keys_bytes, void *stream);
 
+/* One-vs-all link candidates ranked by the structure head: keys[s][v] ranks v for sources[s] by the score ss_pair_scores gives
+ * the pair (sources[s], v) -- the source first, the row is not symmetric -- bit for bit (-0 becomes +0): all h^2 intersection
+ * estimates, the feature row of ss_pair_features[_normalised] (same flags, cards, degrees), then the head, the row never written.
+ * Arguments as ss_pair_scores takes them (head->dim = h(h+2), or 2h(h+2) with head->normalised, which requires degrees; without
+ * it degrees must be NULL) and as ss_topk_scan does (keys [S, N] int64 of ss_topk_workspace_bytes(N, S) bytes, the same key
+ * encoding and sentinel, N < 2^32 - 1, err_flag set by an id outside [-N, N), whose row is all sentinels).  ss_topk_exclude
+ * applies an exclude list to these keys as it does to ss_topk_scan's. */
+int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, int32_t h, const uint32_t *const *mh, const uint8_t *const *hll,
+                       int32_t P, const float *cards, int64_t cards_stride, const ss_hll_params *prm, uint32_t flags,
+                       const float *degrees, const ss_structure_head *head, int64_t *keys, size_t keys_bytes, int32_t *err_flag,
+                       void *stream);
+
 /* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
  * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
  * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,

@@ -15,17 +15,14 @@
 // reads them).  The harmonic sums therefore add the same terms in the same order and the estimate is bit-identical to the
 // query's dbg_inter.  Lane j of a row then finishes source j of each group of 16: estimator, key, store.
 //
-// Key: high word = the score's bits made monotone (signed int32 order == float order, -0 folded into +0), low word = 0xFFFFFFFF - v:
-// signed int64 order == (score descending, id ascending).  Ineligible entries (v == u, an out-of-range source, excluded edges)
-// hold kTopkSentinel, below every real key.
+// Key (ss_topk_key.hpp, shared with the scan that ranks by the structure head, ss_topk_head.hip): signed int64 order == (score
+// descending, id ascending); ineligible entries (v == u, an out-of-range source, excluded edges) hold kTopkSentinel.
 #include "ss_pair_math.hpp"
+#include "ss_topk_key.hpp"
 
 namespace ss {
 
 constexpr int kTopkSources = 32;            // sources staged per workgroup
-constexpr int kTopkRows = 256 / kRow;       // candidates in flight per workgroup
-constexpr int kTopkGrid = 4096;             // workgroups a scan launch aims for (all blocks of sources together)
-constexpr int64_t kTopkSentinel = INT64_MIN;
 
 struct TopkTables {
     const uint32_t *mh_u;   // hop-k1 rows (sources)
@@ -33,15 +30,6 @@ struct TopkTables {
     const uint32_t *mh_v;   // hop-k2 rows (candidates)
     const uint8_t *hll_v;
 };
-
-__device__ __forceinline__ int64_t topk_key(float score, int64_t v)
-{
-    uint32_t b = __float_as_uint(score);
-    if (b == 0x80000000u) b = 0u;                                     // -0 ranks (and decodes) as +0
-    const uint32_t m = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // unsigned order == float order
-    const uint64_t hi = (uint64_t)(m ^ 0x80000000u);                  // signed order == float order
-    return (int64_t)((hi << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)v));
-}
 
 // CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape
 template <int CMPL>

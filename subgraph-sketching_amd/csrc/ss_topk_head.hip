@@ -1,0 +1,283 @@
+// ss_topk_head.hip -- one-vs-all link candidates ranked by the structure head: for a block of sources and EVERY node v, the score
+// ss_pair_scores gives the pair (u, v), written as the unique 64-bit ranking keys of ss_topk.hip (ElphHashes.topk_links).
+//
+// Serves what a trained ELPH / BUDDY model is asked at full ranking -- the k nodes it ranks highest for a source, its hard
+// negatives, MRR / Hits@K over all nodes (reference models/elph.py:73-86, :324-352 on the rows of hashing.py:258-323) -- without
+// the [S * N, 2] link list and the 2h gathered rows per pair of the composition score_links + torch.topk.
+//
+// Mapping (topk_scan_kernel's): one 16-lane DPP row per candidate v, lane l owning the 16-byte chunks l, l + 16, ... of a sketch
+// row.  A workgroup (16 rows) stages a block of sources once -- ALL h hops of each: MinHash chunks, HLL digests, cards[u][0..h)
+// and degrees[u] -- and every candidate row holds ITS h hops in registers (digests made once per candidate, cards[v] / degrees[v]
+// loaded once per candidate) while it walks the staged sources.  Per (u, v) all h^2 (match, zeros, harmonic sum) statistics are
+// accumulated with the helpers of ss_pair_math.hpp under the chunk ownership of pair_features_kernel and reduced with row16_sum_*,
+// then the pair kernel's own epilogue runs on the row: lane c < h^2 estimates combination c, the row assembles the features
+// (assemble_features), lane i makes the degree-normalised copy of feature i, head_score sums the head (DESIGN 3.11's orders).
+// Every operation and every order is the pair kernel's, so the score is bit-identical to ss_pair_scores' for the link (u, v).
+// The key of source j of a group of 16 is parked in lane j and the group's keys leave in one store.
+//
+// Sources per workgroup (kernel parameter SB, topk_head_sources()): as many of {32, 16, 8} as leave TWO workgroups per CU
+// (2 x 80 KiB of the 160 KiB LDS) next to the estimator and head tables -- a source costs 256 * CMPL + 576 bytes per hop.
+#include "ss_feature_algebra.hpp"
+#include "ss_head.hpp"
+#include "ss_pair_math.hpp"
+#include "ss_topk_key.hpp"
+
+extern "C" size_t ss_topk_workspace_bytes(int64_t N, int32_t S);
+
+namespace ss {
+
+struct TopkHeadTables {
+    const uint32_t *mh[SS_MAX_HOPS];
+    const uint8_t *hll[SS_MAX_HOPS];
+};
+
+constexpr int kTopkHeadLds = 80 * 1024;  // LDS a workgroup may take: two per CU
+
+// bytes of LDS per staged source: its id, cards, degree and, on the fast shapes, h rows of MinHash chunks and HLL digests
+constexpr int topk_head_source_bytes(int H, int CMPL)
+{
+    return 8 + 4 * H + 4 + (CMPL > 0 ? H * (CMPL * kRow * 16 + kRow * (16 + 16 + 4)) : 0);
+}
+
+constexpr int topk_head_sources(int H, int CMPL)
+{
+    const int fixed = (int)sizeof(EstimatorLds) + (int)sizeof(HeadLds) + 64;  // (64: alignment between the arrays)
+    for (int sb = 32; sb > 8; sb >>= 1)
+        if (fixed + sb * topk_head_source_bytes(H, CMPL) <= kTopkHeadLds) return sb;
+    return 8;
+}
+
+// CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape (the sources' rows are read from global memory)
+template <int H, int CMPL>
+__global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__restrict__ sources, int S, int64_t N, TopkHeadTables tabs,
+                                                               int P_rt, int M, const float *__restrict__ cards, int64_t cards_stride,
+                                                               ss_hll_params prm, uint32_t flags, const float *__restrict__ degrees,
+                                                               HeadArgs head, int64_t *__restrict__ keys, int32_t *__restrict__ err)
+{
+    constexpr int SB = topk_head_sources(H, CMPL);
+    constexpr int NF = H * (H + 2);
+    constexpr int NC = H * H;
+    constexpr int CM = CMPL > 0 ? CMPL * kRow : 1;  // staged MinHash chunks per source and hop
+    constexpr int CH = CMPL > 0 ? kRow : 1;         // staged HLL chunks per source and hop (M = 256)
+    constexpr int HS = CMPL > 0 ? H : 1;
+    __shared__ EstimatorLds est_lds;
+    __shared__ HeadLds head_lds;
+    __shared__ u32x4 s_mh[SB][HS][CM];
+    __shared__ u32x4 s_pe[SB][HS][CH], s_po[SB][HS][CH];
+    __shared__ uint32_t s_zm[SB][HS][CH];
+    __shared__ int64_t s_u[SB];  // wrapped source id, -1: none / out of range
+    __shared__ float s_c1[SB][H];
+    __shared__ float s_deg[SB];
+
+    const int P = CMPL > 0 ? CMPL * 64 : P_rt;
+    const int s0 = blockIdx.y * SB;
+    const int ns = S - s0 < SB ? S - s0 : SB;
+    if (threadIdx.x < SB) {
+        int64_t u = -1;
+        if ((int)threadIdx.x < ns) {
+            u = sources[s0 + threadIdx.x];
+            u = u < 0 ? u + N : u;  // torch-style negative indexing, as the pair query
+            if ((uint64_t)u >= (uint64_t)N) {
+                if (err) *err = 1;
+                u = -1;
+            }
+        }
+        s_u[threadIdx.x] = u;
+#pragma unroll
+        for (int k = 0; k < H; ++k) s_c1[threadIdx.x][k] = u >= 0 ? cards[u * cards_stride + k] : 0.0f;
+        s_deg[threadIdx.x] = (u >= 0 && degrees) ? degrees[u] : 0.0f;
+    }
+    __syncthreads();
+    if constexpr (CMPL > 0) {
+        for (int i = threadIdx.x; i < SB * H * CM; i += blockDim.x) {
+            const int s = i / (H * CM), k = (i / CM) % H, c = i % CM;
+            const int64_t u = s_u[s];
+            s_mh[s][k][c] = u >= 0 ? *reinterpret_cast<const u32x4 *>(tabs.mh[k] + u * (CMPL * 64) + 4 * c) : u32x4{0u, 0u, 0u, 0u};
+        }
+        for (int i = threadIdx.x; i < SB * H * CH; i += blockDim.x) {
+            const int s = i / (H * CH), k = (i / CH) % H, c = i % CH;
+            const int64_t u = s_u[s];
+            const HllChunk d = digest_chunk(u >= 0 ? *reinterpret_cast<const u32x4 *>(tabs.hll[k] + u * 256 + 16 * c) : u32x4{0u, 0u, 0u, 0u});
+            s_pe[s][k][c] = u32x4{d.pe[0], d.pe[1], d.pe[2], d.pe[3]};
+            s_po[s][k][c] = u32x4{d.po[0], d.po[1], d.po[2], d.po[3]};
+            s_zm[s][k][c] = d.zero_mask;
+        }
+    }
+    stage_head(head_lds, head);                              // (no barrier of its own: the one inside stage_tables)
+    const EstimatorTables est = stage_tables(est_lds, prm);  // (its barrier also publishes the staged rows)
+
+    const int l = threadIdx.x & (kRow - 1);
+    const int row_base = (threadIdx.x & (kWave - 1)) & ~(kRow - 1);
+    const bool normalised = degrees != nullptr;
+    const int64_t stride = (int64_t)gridDim.x * kTopkRows;
+    // no barrier below: rows may run different numbers of candidates (the shuffles of the epilogue stay inside a row, whose lanes
+    // share v)
+    for (int64_t v = (int64_t)blockIdx.x * kTopkRows + threadIdx.x / kRow; v < N; v += stride) {
+        u32x4 mv[HS][CMPL > 0 ? CMPL : 1];
+        HllChunk hv[HS];
+        if constexpr (CMPL > 0) {
+#pragma unroll
+            for (int k = 0; k < H; ++k) {
+#pragma unroll
+                for (int c = 0; c < CMPL; ++c) mv[k][c] = *reinterpret_cast<const u32x4 *>(tabs.mh[k] + v * (CMPL * 64) + 4 * (l + kRow * c));
+            }
+#pragma unroll
+            for (int k = 0; k < H; ++k) hv[k] = digest_chunk(*reinterpret_cast<const u32x4 *>(tabs.hll[k] + v * 256 + 16 * l));
+        }
+        float c2[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) c2[k] = cards[v * cards_stride + k];
+        const float deg_v = normalised ? degrees[v] : 0.0f;
+
+        for (int g = 0; g < ns; g += kRow) {  // a group of 16 sources: the key of source g + j is parked in lane j
+            int64_t my_key = kTopkSentinel;
+            const int nj = ns - g < kRow ? ns - g : kRow;
+            for (int j = 0; j < nj; ++j) {  // row-uniform
+                const int s = g + j;
+                const int64_t u = s_u[s];
+                int mz[NC];    // (match << 20) | zeros, row total
+                float hs[NC];  // harmonic sum, row total
+                if constexpr (CMPL > 0) {
+#pragma unroll
+                    for (int k1 = 0; k1 < H; ++k1) {
+                        const u32x4 pe = s_pe[s][k1][l], po = s_po[s][k1][l];
+                        const HllChunk hu = {{pe.x, pe.y, pe.z, pe.w}, {po.x, po.y, po.z, po.w}, s_zm[s][k1][l]};
+                        u32x4 mu[CMPL];
+#pragma unroll
+                        for (int c = 0; c < CMPL; ++c) mu[c] = s_mh[s][k1][l + kRow * c];
+#pragma unroll
+                        for (int k2 = 0; k2 < H; ++k2) {
+                            int match = 0, zeros = 0;
+                            float hsum = 0.0f;
+#pragma unroll
+                            for (int c = 0; c < CMPL; ++c) match += eq4(mu[c], mv[k2][c]);
+                            union_stats_digested(hu, hv[k2], zeros, hsum);
+                            mz[k1 * H + k2] = row16_sum_i((match << 20) | zeros);
+                            hs[k1 * H + k2] = row16_sum_f(hsum);
+                        }
+                    }
+                } else {
+                    const int64_t ur = u < 0 ? 0 : u;  // (an invalid source's entries become the sentinel below)
+                    const int CMr = P >> 2, CHr = M >> 4;
+#pragma unroll
+                    for (int k1 = 0; k1 < H; ++k1)
+#pragma unroll
+                        for (int k2 = 0; k2 < H; ++k2) {
+                            int match = 0, nonzero = 0;
+                            float hsum = 0.0f;
+                            for (int c = l; c < CMr; c += kRow)
+                                match += eq4(*reinterpret_cast<const u32x4 *>(tabs.mh[k1] + ur * P + 4 * c),
+                                             *reinterpret_cast<const u32x4 *>(tabs.mh[k2] + v * P + 4 * c));
+                            int chunks = 0;
+                            for (int c = l; c < CHr; c += kRow, ++chunks)
+                                union_stats(*reinterpret_cast<const u32x4 *>(tabs.hll[k1] + ur * M + 16 * c),
+                                            *reinterpret_cast<const u32x4 *>(tabs.hll[k2] + v * M + 16 * c), nonzero, hsum);
+                            mz[k1 * H + k2] = row16_sum_i((match << 20) | (16 * chunks - nonzero));
+                            hs[k1 * H + k2] = row16_sum_f(hsum);
+                        }
+                }
+                // from here on the epilogue of pair_features_kernel<..., HeadArgs>, operation for operation:
+                // lane c < H^2 finishes combination c: I = (match / P) * hll_count(union)
+                int my_mz = mz[0];
+                float my_hs = hs[0];
+#pragma unroll
+                for (int c = 1; c < NC; ++c) {
+                    my_mz = (l == c) ? mz[c] : my_mz;
+                    my_hs = (l == c) ? hs[c] : my_hs;
+                }
+                float my_I = 0.0f;
+                if (l < NC) my_I = intersection_estimate(est, (int)((uint32_t)my_mz >> 20), my_mz & 0xFFFFF, my_hs, P);
+                float I[H][H];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) I[c / H][c % H] = __shfl(my_I, row_base + c);
+                float c1[H];
+#pragma unroll
+                for (int k = 0; k < H; ++k) c1[k] = s_c1[s][k];
+                float f[NF];
+                assemble_features<H>(I, c1, c2, flags, f);
+                float normed = 0.0f;
+                if (normalised) {  // the normalised copy of feature l in lane l, as the feature epilogue computes it
+                    float my_f = f[0];
+#pragma unroll
+                    for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
+                    const float normaliser = sqrtf(s_deg[s] * deg_v);
+                    normed = my_f / normaliser;
+                    if (isnan(normed) || isinf(normed)) normed = 0.0f;
+                }
+                const float score = head_score<NF>(head_lds, head.dim, head.bias, f, normed, normalised, l, row_base);
+                const int64_t key = (u >= 0 && u != v) ? topk_key(score, v) : kTopkSentinel;
+                my_key = l == j ? key : my_key;
+            }
+            if (l < nj) keys[(int64_t)(s0 + g + l) * N + v] = my_key;
+        }
+    }
+}
+
+template <int H, int CMPL>
+void launch_topk_score_scan(const int64_t *sources, int S, int64_t N, const TopkHeadTables &tabs, int P, int M, const float *cards,
+                            int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
+                            int64_t *keys, int32_t *err, hipStream_t stream)
+{
+    constexpr int SB = topk_head_sources(H, CMPL);
+    static_assert(SB >= 8 && SB <= 32, "threads 0 .. SB - 1 stage the source ids");
+    const int64_t blocks_y = (S + SB - 1) / SB;
+    int64_t blocks_x = (kTopkGrid + blocks_y - 1) / blocks_y;
+    const int64_t need_x = (N + kTopkRows - 1) / kTopkRows;
+    if (blocks_x > need_x) blocks_x = need_x;
+    hipLaunchKernelGGL((topk_score_scan_kernel<H, CMPL>), dim3((unsigned)blocks_x, (unsigned)blocks_y), dim3(256), 0, stream, sources, S, N, tabs,
+                       P, M, cards, cards_stride, prm, flags, degrees, head, keys, err);
+}
+
+template <int H>
+void dispatch_topk_score_scan(const int64_t *sources, int S, int64_t N, const TopkHeadTables &tabs, int P, int M, const float *cards,
+                              int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
+                              int64_t *keys, int32_t *err, hipStream_t stream)
+{
+#define SS_TOPK_HEAD(CMPL) \
+    launch_topk_score_scan<H, CMPL>(sources, S, N, tabs, P, M, cards, cards_stride, prm, flags, degrees, head, keys, err, stream)
+    const bool fast = M == 256 && (P == 64 || P == 128 || P == 192 || P == 256);  // dispatch_pairs' fast shapes
+    if (!fast) SS_TOPK_HEAD(0);
+    else if (P == 64) SS_TOPK_HEAD(1);
+    else if (P == 128) SS_TOPK_HEAD(2);
+    else if (P == 192) SS_TOPK_HEAD(3);
+    else SS_TOPK_HEAD(4);
+#undef SS_TOPK_HEAD
+}
+
+}  // namespace ss
+
+extern "C" int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, int32_t h, const uint32_t *const *mh, const uint8_t *const *hll,
+                                  int32_t P, const float *cards, int64_t cards_stride, const ss_hll_params *prm, uint32_t flags,
+                                  const float *degrees, const ss_structure_head *head, int64_t *keys, size_t keys_bytes, int32_t *err_flag,
+                                  void *stream)
+{
+    using namespace ss;
+    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
+    const int rc = check_params(prm);
+    if (rc != SS_OK) return rc;
+    if (S < 0 || N <= 0 || N >= ((int64_t)1 << 32) - 1) return SS_ERR_INVALID_ARG;  // (the key's low word holds 0xFFFFFFFF - v)
+    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
+    if (S == 0) return SS_OK;
+    if (!sources || !mh || !hll || !cards || !head || !keys || cards_stride < h) return SS_ERR_INVALID_ARG;
+    const int nf = h * (h + 2);
+    if (head->dim != (head->normalised ? 2 * nf : nf) || !head->w1 || !head->shift || !head->w2) return SS_ERR_INVALID_ARG;
+    if ((head->normalised != 0) != (degrees != nullptr)) return SS_ERR_INVALID_ARG;  // the head's width decides, not the pointer
+    if (keys_bytes < ss_topk_workspace_bytes(N, S)) return SS_ERR_WORKSPACE;
+    TopkHeadTables tabs = {};
+    for (int k = 0; k < h; ++k) {
+        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
+        tabs.mh[k] = mh[k];
+        tabs.hll[k] = hll[k];
+    }
+    if (((int64_t)S + 7) / 8 > 65535) return SS_ERR_INVALID_ARG;  // (grid.y, at the smallest block of sources)
+    const HeadArgs args = {head->w1, head->shift, head->w2, head->bias, head->dim};
+    const int M = 1 << prm->p;
+    hipStream_t s = (hipStream_t)stream;
+    switch (h) {
+        case 1: dispatch_topk_score_scan<1>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
+        case 2: dispatch_topk_score_scan<2>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
+        default: dispatch_topk_score_scan<3>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
+    }
+    SS_LAUNCH_CHECK();
+    return SS_OK;
+}

@@ -594,7 +594,7 @@ class ElphHashes(object):
         @return: float32 [n_links] on links.device; an id outside [-N, N) gives NaN and is reported as get_subgraph_features
                  reports it, in every strict_bounds mode
         Inference only -- there are no gradients.  Out of scope (ValueError where an argument suggests otherwise): a head on the
-        masked query (mask_target), lazy stores, dist.sharded_precompute, a head inside topk_candidates.  No CPU fallback."""
+        masked query (mask_target), lazy stores, dist.sharded_precompute.  The head inside the one-vs-all scan is topk_links.  No CPU fallback."""
         from .head import StructureHead
         if unsupported:
             names = ', '.join(sorted(unsupported))
@@ -650,13 +650,24 @@ class ElphHashes(object):
         @param k: 1 <= k <= N;  @param hops: (k1, k2), 1 <= k1, k2 <= max_hash_hops
         @param exclude: optional int64 [2, E] edge_index: every v with an edge u -> v in it is no candidate of u (nor is u itself)
         @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows
-                 with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only."""
+                 with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only.
+        Ranking by a trained model's structure head instead of one raw estimate: topk_links."""
         try:
             k1, k2 = (int(x) for x in hops)
         except (TypeError, ValueError):
             raise ValueError(f'hops must be a pair (k1, k2), got {hops!r}')
         if not (1 <= k1 <= self.max_hops and 1 <= k2 <= self.max_hops):
             raise ValueError(f'hops must lie in [1, {self.max_hops}], got {(k1, k2)}')
+        src, ex, N, P = self._topk_arguments(sources, hash_table, k, exclude)
+
+        def scan(lib, sb, nb, N, P, mh, hll, params, keys, nbytes, err, stream):
+            _native.check(lib.ss_topk_scan(sb, nb, N, _ptr(mh[k1 - 1]), _ptr(hll[k1 - 1]), _ptr(mh[k2 - 1]), _ptr(hll[k2 - 1]), P,
+                                           byref(params.struct), _ptr(keys), nbytes, _ptr(err), stream), 'ss_topk_scan')
+
+        return self._topk_run('topk_candidates', src, ex, hash_table, int(k), scan)
+
+    def _topk_arguments(self, sources, hash_table, k, exclude):
+        """what topk_candidates and topk_links check before a device is touched: (sources, exclude or None, N, P)"""
         src = torch.as_tensor(sources)
         if src.dim() != 1 or src.dtype.is_floating_point or src.dtype == torch.bool:
             raise ValueError(f'sources must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
@@ -675,14 +686,23 @@ class ElphHashes(object):
             raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
         if ex is not None and not ex.is_cuda and ex.numel() and (int(ex.min()) < -N or int(ex.max()) >= N):
             raise IndexError(f'exclude refers to nodes outside [-{N}, {N})')
+        return src, ex, N, P
+
+    def _topk_run(self, what, src, ex, hash_table, k, scan, cards=None, degrees=None):
+        """the walk both one-vs-all queries share: blocks of sources bounded by _TOPK_KEY_BYTES, `scan` filling a block's keys, the
+        exclude CSR, torch.topk on the unique keys, _decode_topk_keys.  cards / degrees: resolved on the compute device and handed
+        to `scan` (topk_links)"""
         home = src.device
         S = src.numel()
         first = hash_table.get(1) if hasattr(hash_table, 'get') else None
         device = _compute_device(src, first.mh_u32 if isinstance(first, HopSketch) else None)
         mh, hll, N, P = self._resolve_tables(hash_table, device)
         params = self._params(device)
+        extra = ()
+        if cards is not None:
+            extra = self._topk_cards(cards, degrees, N, device)
         lk = src.to(device=device, dtype=torch.int64).contiguous()
-        strict, err = self._bounds(device, f'topk_candidates({S} sources, num_nodes={N})')
+        strict, err = self._bounds(device, f'{what}({S} sources, num_nodes={N})')
         csr = None
         if ex is not None:
             ex = ex.to(device=device, dtype=torch.int64)
@@ -701,8 +721,7 @@ class ElphHashes(object):
             nb = min(blk, S - b0)
             sb = c_void_p(lk.data_ptr() + 8 * b0)
             with _Span('topk_scan', device):
-                _native.check(lib.ss_topk_scan(sb, nb, N, _ptr(mh[k1 - 1]), _ptr(hll[k1 - 1]), _ptr(mh[k2 - 1]), _ptr(hll[k2 - 1]), P,
-                                               byref(params.struct), _ptr(keys), nbytes, _ptr(err), _stream(device)), 'ss_topk_scan')
+                scan(lib, sb, nb, N, P, mh, hll, params, keys, nbytes, err, _stream(device), *extra)
             if csr is not None:
                 with _Span('topk_exclude', device):
                     _native.check(lib.ss_topk_exclude(sb, nb, N, _ptr(csr.rowptr), _ptr(csr.col), _ptr(keys), nbytes, _stream(device)),
@@ -718,6 +737,71 @@ class ElphHashes(object):
         if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
             self._deferred.raise_if_set()
         return ids, scores
+
+    def _topk_cards(self, cards, degrees, N, device):
+        """(cards float32 [N, >= h] with unit column stride, degrees float32 [N] or None) on `device`, as _query_inputs resolves them"""
+        h = self.max_hops
+        made_with = getattr(cards, '_ss_tables', None)
+        if made_with is not None and not hll_tables.same_tables(made_with, self.tables_id):
+            raise ValueError(f'cards were estimated with HLL++ tables {made_with}, this engine uses {self.tables_id}: '
+                             f'a feature row would mix two bias tables (rebuild the cache or load the same tables)')
+        tag = getattr(cards, '_ss_cards', None)
+        if cards.device == device and cards.dtype == torch.float32:
+            cd = cards
+        elif tag is not None and tag[0] == cards._version and tag[1].device == device:
+            cd = tag[1]
+        else:
+            cd = cards.to(device=device, dtype=torch.float32)
+            _tag(cards, '_ss_cards', cd)
+        if cd.dim() != 2 or cd.size(0) != N or cd.size(1) < h:
+            raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
+        if cd.stride(1) != 1:
+            cd = cd.contiguous()
+        dg = None
+        if degrees is not None:
+            dg = degrees.to(device=device, dtype=torch.float32).contiguous()
+            if dg.dim() != 1 or dg.numel() != N:
+                raise ValueError(f'degrees must have shape [{N}], got {tuple(dg.shape)}')
+        return cd, dg
+
+    def topk_links(self, sources, hash_table, cards, k, head, degrees=None, exclude=None):
+        """the k link partners a trained model's structure head ranks highest for every source: topk_candidates' one-vs-all scan with
+        score_links' score instead of one raw intersection estimate (csrc/ss_topk_head.hip) -- what full-ranking
+        evaluation (MRR / Hits@K over all nodes), hard-negative mining by the model's own score and candidate generation ask for.
+        The score of candidate v for source u is bit-identical to score_links([[u, v]], hash_table, cards, head, degrees=degrees)
+        (u first: the row is not symmetric; -0.0 comes back as +0.0); no link list and no feature row is ever written.
+        @param sources: int64 [S] node ids (torch-style negative ids allowed), CPU or device
+        @param hash_table, cards, head, degrees: as score_links takes them (head.normalised requires degrees; degrees without it is
+               a ValueError)
+        @param k: 1 <= k <= N
+        @param exclude: optional int64 [2, E] edge_index: every v with an edge u -> v in it is no candidate of u (nor is u itself)
+        @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows
+                 with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only.
+        Ids outside [-N, N) are reported as topk_candidates reports them.  Non-finite scores (overflow under absurd weights) are
+        outside the contract.  Inference only; out of scope: the masked query behind the scan, dist sharding.  No CPU fallback."""
+        from .head import StructureHead
+        if not isinstance(head, StructureHead):
+            raise ValueError(f'head must be a StructureHead (StructureHead.from_module(model)), got {type(head).__name__}')
+        if head.hops != self.max_hops:
+            raise ValueError(f'head.dim = {head.dim} belongs to max_hash_hops = {head.hops}, this engine has max_hash_hops = {self.max_hops}')
+        if head.normalised and degrees is None:
+            raise ValueError('head.normalised: the head takes the degree-normalised copy of the row, give degrees')
+        if degrees is not None and not head.normalised:
+            raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
+        if cards is None:
+            raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
+        src, ex, N, P = self._topk_arguments(sources, hash_table, k, exclude)
+        h = self.max_hops
+        flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if self.floor_sf else 0)
+
+        def scan(lib, sb, nb, N, P, mh, hll, params, keys, nbytes, err, stream, cd, dg):
+            hd = head._device(keys.device)
+            mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
+            hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
+            _native.check(lib.ss_topk_score_scan(sb, nb, N, h, mh_ptrs, hll_ptrs, P, _ptr(cd), cd.stride(0), byref(params.struct), flags,
+                                                 _ptr(dg), byref(hd.struct), _ptr(keys), nbytes, _ptr(err), stream), 'ss_topk_score_scan')
+
+        return self._topk_run('topk_links', src, ex, hash_table, int(k), scan, cards=cards, degrees=degrees)
 
     def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, mask_target=False):
         """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph

@@ -123,6 +123,30 @@ def score_query_bytes(pairs, P=128, p=8, h=2, normalised=False):
     return pairs * score_pair_bytes(P, p, h, normalised)
 
 
+def topk_links_sources(h, P, M):
+    """sources a workgroup of the scoring scan stages (csrc/ss_topk_head.hip topk_head_sources): the most of {32, 16, 8} that
+    leave two workgroups per CU -- 80 KiB each -- next to the estimator tables (8 196 B), the head (3 840 B) and 64 B of alignment;
+    a source costs 12 + 4h bytes and, on the fast shapes (M = 256, P in {64, 128, 192, 256}), h rows of 4P + 576 bytes of LDS"""
+    fast = M == 256 and P in (64, 128, 192, 256)
+    per_source = 12 + 4 * h + (h * (4 * P + 576) if fast else 0)
+    for sb in (32, 16):
+        if 8196 + 3840 + 64 + sb * per_source <= 80 * 1024:
+            return sb
+    return 8
+
+
+def topk_links_bytes(N, S, h, P, M):
+    """algorithmic bytes of one ss_topk_score_scan launch (ElphHashes.topk_links): every candidate's h rows of 4P + M
+    bytes once per block of staged sources, the sources' h rows once per workgroup (the launch aims for 4 096 workgroups, 16
+    candidates in flight each), one int64 key per (source, candidate).  The candidates' cards / degrees (4h + 4 bytes against h
+    rows), the exclude pass and torch.topk's read of the keys are not in it."""
+    R = 4 * P + M
+    sb = topk_links_sources(h, P, M)
+    blocks_y = -(-S // sb)
+    blocks_x = min(-(-4096 // max(blocks_y, 1)), -(-N // 16))
+    return blocks_y * N * h * R + blocks_x * S * h * R + 8 * S * N
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
