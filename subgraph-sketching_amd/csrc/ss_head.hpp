@@ -26,6 +26,17 @@ struct HeadArgs {
     int dim;
 };
 
+// ss_structure_head (host struct, device pointers) -> the kernel's view.  false: no head, not a head of hop count h, or its width and
+// `degrees` disagree (the head's width decides whether the normalised copy exists, not the pointer)
+inline bool make_head_args(const ss_structure_head *head, int h, const float *degrees, HeadArgs &out)
+{
+    const int nf = h * (h + 2);
+    if (!head || head->dim != (head->normalised ? 2 * nf : nf) || !head->w1 || !head->shift || !head->w2) return false;
+    if ((head->normalised != 0) != (degrees != nullptr)) return false;
+    out = {head->w1, head->shift, head->w2, head->bias, head->dim};
+    return true;
+}
+
 // (the pair kernel carries its head as a parameter pack that is empty for the feature query: this names the one element)
 __device__ __forceinline__ const HeadArgs &the_head(const HeadArgs &h) { return h; }
 

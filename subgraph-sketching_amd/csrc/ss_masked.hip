@@ -35,11 +35,6 @@ constexpr int kMaskedThreads = 256;
 constexpr int kMaskedHeaderBytes = 256;  // int32 word 0: links listed
 constexpr int kMaskedGrid = 4096;        // workgroups of masked_pairs_kernel (they stride over the device-side count)
 
-struct MaskedTables {
-    const uint32_t *mh[SS_MAX_HOPS];
-    const uint8_t *hll[SS_MAX_HOPS];
-};
-
 // ---- which links are edges ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kMaskedThreads) void masked_classify_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                          int64_t N, const int64_t *__restrict__ links, int64_t B,
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_classify_kernel(const i
 
 // ---- debug: zero registers of the stored rows of every link (the masked kernel overwrites those of the links it serves) ------------
 __global__ __launch_bounds__(kMaskedThreads) void masked_row_zeros_kernel(const int64_t *__restrict__ links, int64_t B, int64_t N, int h,
-                                                                          MaskedTables tabs, int M, int32_t *__restrict__ row_zeros)
+                                                                          HopTables tabs, int M, int32_t *__restrict__ row_zeros)
 {
     const int l = threadIdx.x & (kRow - 1);
     const int groups = kMaskedThreads / kRow;
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_row_zeros_kernel(const 
 struct MaskedLink {
     const int64_t *rowptr;
     const int32_t *col;
-    MaskedTables tabs;
+    HopTables tabs;
     int64_t u, v;
     int P, M, CM, W4, S;
     u32x4 *rows;     // [2][H][W4]: side (u, v), hop - 1
@@ -200,7 +195,7 @@ template <int H>
 __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs g, const int64_t *__restrict__ links, int64_t N,
                                                                       const int32_t *__restrict__ counter, const int32_t *__restrict__ list,
                                                                       const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
-                                                                      MaskedTables tabs, int P, ss_hll_params prm, uint32_t flags,
+                                                                      HopTables tabs, int P, ss_hll_params prm, uint32_t flags,
                                                                       float *__restrict__ out, int32_t *__restrict__ dbg_match,
                                                                       int32_t *__restrict__ dbg_zero, int32_t *__restrict__ dbg_row_zeros)
 {
@@ -285,12 +280,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
 #pragma unroll
                 for (int k2 = 0; k2 < H; ++k2) {
                     const u32x4 *ru = L.row(0, k1), *rv = L.row(1, k2);
-                    int match = 0, nonzero = 0, chunks = 0;
-                    float hsum = 0.0f;
-                    for (int cc = l; cc < CM; cc += kRow) match += eq4(ru[cc], rv[cc]);
-                    for (int cc = l; cc < CH; cc += kRow, ++chunks) union_stats(ru[CM + cc], rv[CM + cc], nonzero, hsum);
-                    mz[k1 * H + k2] = row16_sum_i((match << 20) | (16 * chunks - nonzero));
-                    hs[k1 * H + k2] = row16_sum_f(hsum);
+                    pair_stats_generic(ru, rv, ru + CM, rv + CM, CM, CH, l, mz[k1 * H + k2], hs[k1 * H + k2]);
                 }
             // cardinalities of the masked rows (hll_row16_stats: the statistics of a finished row, as for the stored rows above)
             float c1[H], c2[H];
@@ -307,13 +297,9 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
                     if (side == 0) c1[k] = card;
                     else c2[k] = card;
                 }
-            int my_mz = mz[0];
-            float my_hs = hs[0];
-#pragma unroll
-            for (int cc = 1; cc < NC; ++cc) {
-                my_mz = (l == cc) ? mz[cc] : my_mz;
-                my_hs = (l == cc) ? hs[cc] : my_hs;
-            }
+            // (written out, not a shared function: that moved the VGPRs at h >= 2, a wavefront per SIMD at h = 3 -- DESIGN_EXPERIMENTS "One source for the pair finish")
+            const int my_mz = lane_select(mz, l);
+            const float my_hs = lane_select(hs, l);
             float my_I = 0.0f;
             const int my_match = (int)((uint32_t)my_mz >> 20), my_zeros = my_mz & 0xFFFFF;
             if (l < NC) my_I = intersection_estimate(est, my_match, my_zeros, my_hs, P);
@@ -323,12 +309,8 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
             for (int cc = 0; cc < NC; ++cc) I[cc / H][cc % H] = __shfl(my_I, row_base + cc);
             float f[NF];
             assemble_features<H>(I, c1, c2, flags, f);
-            float my_f = f[0];
-#pragma unroll
-            for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
-            int my_rz = rz[0];
-#pragma unroll
-            for (int k = 1; k < 2 * H; ++k) my_rz = (l == k) ? rz[k] : my_rz;
+            const float my_f = lane_select(f, l);
+            const int my_rz = lane_select(rz, l);
             if (t < kRow) {
                 if (l < NF) out[q * NF + l] = my_f;
                 if (l < NC) {
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
 
 template <int H>
 static void launch_masked(const GraphArgs &g, const int64_t *links, int64_t B, int64_t N, const int32_t *counter, const int32_t *list,
-                          const uint64_t *a, const uint64_t *b, const MaskedTables &tabs, int P, const ss_hll_params &prm, uint32_t flags,
+                          const uint64_t *a, const uint64_t *b, const HopTables &tabs, int P, const ss_hll_params &prm, uint32_t flags,
                           float *out, int32_t *dbg_match, int32_t *dbg_zero, int32_t *dbg_row_zeros, size_t dyn_bytes, hipStream_t s)
 {
     const unsigned grid = (unsigned)(B < kMaskedGrid ? B : kMaskedGrid);
@@ -367,14 +349,10 @@ extern "C" int ss_masked_pair_features(const ss_csr_graph *graph, const int64_t 
                                        size_t workspace_bytes, void *stream)
 {
     using namespace ss;
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (B < 0 || N < 0 || B >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    const int rc = check_params(prm);
-    if (rc != SS_OK) return rc;
-    if (B == 0) return SS_OK;
+    const int rc = check_pair_query_args(h, B >= 0 && N >= 0 && B < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), prm, P, B == 0);
+    if (rc != SS_OK || B == 0) return rc;
     if (!graph || !graph->rowptr || !graph->col || graph->num_nodes != N || !a || !b || !mh || !hll || !workspace) return SS_ERR_INVALID_ARG;
     if (graph->row_begin != 0 || graph->row_end != 0) return SS_ERR_INVALID_ARG;
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
     const int W4 = (P >> 2) + (M >> 4);
     if (W4 > kMaskedThreads) return SS_ERR_UNSUPPORTED;  // a sketch row is walked with one 16-byte chunk per thread
@@ -384,11 +362,8 @@ extern "C" int ss_masked_pair_features(const ss_csr_graph *graph, const int64_t 
     const int rq = ss_pair_features(links, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, nullptr, err_flag,
                                     stream);
     if (rq != SS_OK) return rq;
-    MaskedTables tabs = {};
-    for (int k = 0; k < h; ++k) {
-        tabs.mh[k] = mh[k];
-        tabs.hll[k] = hll[k];
-    }
+    HopTables tabs;
+    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;  // (the plain query above has seen every entry)
     int32_t *counter = static_cast<int32_t *>(workspace);
     int32_t *list = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(workspace) + kMaskedHeaderBytes);
     if (hipMemsetAsync(workspace, 0, kMaskedHeaderBytes, s) != hipSuccess) return SS_ERR_LAUNCH;

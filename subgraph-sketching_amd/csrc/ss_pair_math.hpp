@@ -1,9 +1,14 @@
 // ss_pair_math.hpp -- the per-pair arithmetic of the set-intersection estimate I[k1, k2] = J * U (reference hashing.py:167-189),
-// shared by the pair query (ss_pairs.hip) and the one-vs-all scan (ss_topk.hip).  Both kernels give lane l of a 16-lane row the
-// chunks l, l + 16, ... of a sketch row, accumulate a pair's statistics per lane with these helpers in chunk order, and reduce
-// them with row16_sum_i / row16_sum_f: that is what makes their fp32 harmonic sums -- and so their estimates -- bit-identical.
+// shared by the pair query (ss_pairs.hip), the masked query (ss_masked.hip) and the one-vs-all scans (ss_topk.hip, ss_topk_head.hip).
+// Every kernel gives lane l of a 16-lane row the chunks l, l + 16, ... of a sketch row, accumulates a pair's statistics per lane with
+// these helpers in chunk order, and reduces them with row16_sum_i / row16_sum_f: that is what makes their fp32 harmonic sums -- and so
+// their estimates -- bit-identical.  The run-time-shape statistic (pair_stats_generic), the lane select and the degree-normalised copy
+// have ONE source here for pair_features_kernel, pair_features_runs_kernel, topk_score_scan_kernel and masked_pairs_kernel.  The finish
+// of a pair between them -- lane c < h^2: intersection_estimate, __shfl of I to the row, assemble_features -- stays written out in each
+// of the four: as one function it changed their registers (DESIGN_EXPERIMENTS "One source for the pair finish").  The host half at the
+// end is what their entry points share: the table pointers and the argument checks.
 #pragma once
-#include "ss_common.hpp"
+#include "ss_feature_algebra.hpp"
 
 namespace ss {
 
@@ -67,6 +72,75 @@ __device__ __forceinline__ float intersection_estimate(const EstimatorTables &es
 {
     const float jac = (float)match / (float)P;
     return jac * hll_estimate(est, zeros, hsum);
+}
+
+// lane k of a row keeps element k of an array every lane holds (lanes >= N keep element 0).  Every element is read BEFORE its select:
+// with `(l == k) ? a[k] : x` the optimiser, which sees this function before it is inlined, sinks the conditional loads into one load at
+// a selected offset, and the caller's array then stays in scratch / LDS instead of registers.
+template <typename T, int N>
+__device__ __forceinline__ T lane_select(const T (&a)[N], int l)
+{
+    T x = a[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) {
+        const T ak = a[k];
+        x = (l == k) ? ak : x;
+    }
+    return x;
+}
+
+// run-time sketch shape: the row totals (match << 20) | zeros and harmonic sum of ONE (k1, k2) from rows of CM MinHash and CH HLL
+// chunks, in global memory or LDS (P <= 2048: the packed word uses all 32 bits)
+__device__ __forceinline__ void pair_stats_generic(const u32x4 *mh_u, const u32x4 *mh_v, const u32x4 *hll_u, const u32x4 *hll_v, int CM,
+                                                   int CH, int l, int &mz, float &hs)
+{
+    int match = 0, nonzero = 0, chunks = 0;
+    float hsum = 0.0f;
+    for (int c = l; c < CM; c += kRow) match += eq4(mh_u[c], mh_v[c]);
+    for (int c = l; c < CH; c += kRow, ++chunks) union_stats(hll_u[c], hll_v[c], nonzero, hsum);
+    mz = row16_sum_i((match << 20) | (16 * chunks - nonzero));
+    hs = row16_sum_f(hsum);
+}
+
+// BUDDY._append_degree_normalised (reference models/elph.py:276-293) for one feature: f / sqrt(d_u * d_v), NaN / Inf (zero-degree nodes)
+// replaced by 0.  What a pair with ids out of range gets differs per caller on purpose and stays there: the feature epilogue NaNs my_f
+// before this copy and the copy after it, the head path NaNs only the score, the run-aware kernel writes its NaN row before it gets here.
+__device__ __forceinline__ float degree_normalised(float my_f, float du, float dv)
+{
+    const float normed = my_f / sqrtf(du * dv);
+    return (isnan(normed) || isinf(normed)) ? 0.0f : normed;
+}
+
+// ---- host side: what the entry points of these kernels share ----------------------------------------------------------------------
+struct HopTables {
+    const uint32_t *mh[SS_MAX_HOPS];
+    const uint8_t *hll[SS_MAX_HOPS];
+};
+
+inline bool fill_hop_tables(const uint32_t *const *mh, const uint8_t *const *hll, int h, HopTables &out)
+{
+    out = {};
+    for (int k = 0; k < h; ++k) {
+        if (!mh[k] || !hll[k]) return false;
+        out.mh[k] = mh[k];
+        out.hll[k] = hll[k];
+    }
+    return true;
+}
+
+// the shapes with compile-time kernels: p = 8 and the permutation counts the first hop is specialised for (ss_first_hop: P / 64 = 1 .. 4)
+inline bool is_fast_pair_shape(int P, int M) { return M == 256 && (P == 64 || P == 128 || P == 192 || P == 256); }
+
+// Hop count, the caller's own size checks, HLL parameters, sketch width -- in the one order that decides which code comes back.
+// `empty`: the entry points that answer an empty query with SS_OK before they look at P pass B == 0 (and return right after).
+inline int check_pair_query_args(int h, bool sizes_ok, const ss_hll_params *prm, int P, bool empty = false)
+{
+    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;  // hashing.py:54, 308-309
+    if (!sizes_ok) return SS_ERR_INVALID_ARG;
+    const int rc = check_params(prm);
+    if (rc != SS_OK) return rc;
+    if (!empty && (P <= 0 || (P & 3) || P > 2048)) return SS_ERR_INVALID_ARG;
+    return SS_OK;
 }
 
 }  // namespace ss

@@ -26,11 +26,6 @@ namespace ss {
 
 constexpr int kPairGrid = 256 * 32;  // most workgroups a launch uses; each loops over its share of the pairs
 
-struct PairTables {
-    const uint32_t *mh[SS_MAX_HOPS];
-    const uint8_t *hll[SS_MAX_HOPS];
-};
-
 // TP, TM > 0: compile-time sketch sizes, all 2H rows register-resident (fast path).
 // TP = TM = 0: run-time sizes, rows re-read per (k1,k2) (parameter sweeps / tests; not tuned).
 // OCC (walks with locality, ss_pair_features_grouped: links grouped by their first node or listed that way): left alone the register
@@ -45,7 +40,7 @@ struct PairTables {
 // are staged into LDS with the estimator tables.  One source for the pair body; with an empty pack nothing of the head is instantiated.
 template <int H, int TP, int TM, bool OCC = false, typename... Head>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC ? (H == 2 ? 5 : H == 3 ? 4 : 1) : 1)))
-void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t N, PairTables tabs,
+void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t N, HopTables tabs,
                                                             int P_rt, int M_rt, const float *__restrict__ cards, int64_t cards_stride,
                                                             ss_hll_params prm, uint32_t flags, float *__restrict__ out,
                                                             int32_t *__restrict__ dbg_match, int32_t *__restrict__ dbg_zero,
@@ -166,37 +161,23 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
             est = stage_tables(lds, prm);
             staged = true;
         }
-        const int CM = P >> 2, CH = M >> 4;
 #pragma unroll
         for (int k1 = 0; k1 < H; ++k1)
 #pragma unroll
-            for (int k2 = 0; k2 < H; ++k2) {
-                int match = 0, nonzero = 0;
-                float hsum = 0.0f;
-                for (int c = l; c < CM; c += kRow)
-                    match += eq4(*reinterpret_cast<const u32x4 *>(tabs.mh[k1] + u * P + 4 * c),
-                                 *reinterpret_cast<const u32x4 *>(tabs.mh[k2] + v * P + 4 * c));
-                int chunks = 0;
-                for (int c = l; c < CH; c += kRow, ++chunks)
-                    union_stats(*reinterpret_cast<const u32x4 *>(tabs.hll[k1] + u * M + 16 * c),
-                                *reinterpret_cast<const u32x4 *>(tabs.hll[k2] + v * M + 16 * c), nonzero, hsum);
-                mz[k1 * H + k2] = row16_sum_i((match << 20) | (16 * chunks - nonzero));
-                hs[k1 * H + k2] = row16_sum_f(hsum);
-            }
+            for (int k2 = 0; k2 < H; ++k2)
+                pair_stats_generic(reinterpret_cast<const u32x4 *>(tabs.mh[k1] + u * P), reinterpret_cast<const u32x4 *>(tabs.mh[k2] + v * P),
+                                   reinterpret_cast<const u32x4 *>(tabs.hll[k1] + u * M), reinterpret_cast<const u32x4 *>(tabs.hll[k2] + v * M),
+                                   P >> 2, M >> 4, l, mz[k1 * H + k2], hs[k1 * H + k2]);
     }
 
+    const int row_base = (threadIdx.x & (kWave - 1)) & ~(kRow - 1);
     // lane c < H^2 finishes combination c: I = (match / P) * hll_count(union)   (hashing.py:184-187)
-    int my_mz = mz[0];
-    float my_hs = hs[0];
-#pragma unroll
-    for (int c = 1; c < NC; ++c) {
-        my_mz = (l == c) ? mz[c] : my_mz;
-        my_hs = (l == c) ? hs[c] : my_hs;
-    }
+    // (written out, not a shared function: that moved the scratch bytes of <3, 128, 256, true, HeadArgs> -- DESIGN_EXPERIMENTS "One source for the pair finish")
+    const int my_mz = lane_select(mz, l);
+    const float my_hs = lane_select(hs, l);
     float my_I = 0.0f;
     const int my_match = (int)((uint32_t)my_mz >> 20), my_zeros = my_mz & 0xFFFFF;  // P <= 2048: the packed word uses all 32 bits
     if (l < NC) my_I = intersection_estimate(est, my_match, my_zeros, my_hs, P);
-    const int row_base = (threadIdx.x & (kWave - 1)) & ~(kRow - 1);
     float I[H][H];
 #pragma unroll
     for (int c = 0; c < NC; ++c) I[c / H][c % H] = __shfl(my_I, row_base + c);
@@ -210,19 +191,12 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
     float f[NF];
     assemble_features<H>(I, c1, c2, flags, f);
 
-    float my_f = f[0];
-#pragma unroll
-    for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
+    float my_f = lane_select(f, l);
     if (bad) my_f = __uint_as_float(0x7FC00000u);
     if constexpr (HEAD) {
         // every lane of the row holds f[]: the head runs where the row would have been stored.  The normalised copy of feature l is
-        // computed in lane l exactly as the epilogue below computes it (a pair past the end or out of range reads node 0's degree)
-        float normed = 0.0f;
-        if (degrees) {
-            const float normaliser = sqrtf(degrees[u] * degrees[v]);
-            normed = my_f / normaliser;
-            if (isnan(normed) || isinf(normed)) normed = 0.0f;
-        }
+        // computed in lane l by the function the epilogue below calls (a pair past the end or out of range reads node 0's degree)
+        const float normed = degrees ? degree_normalised(my_f, degrees[u], degrees[v]) : 0.0f;
         const HeadArgs &hd = the_head(head...);
         float score = head_score<NF>(head_lds, hd.dim, hd.bias, f, normed, degrees != nullptr, l, row_base);
         if (bad) score = __uint_as_float(0x7FC00000u);
@@ -233,11 +207,8 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
         continue;
     }
     if (q_ok && degrees) {
-        // fused BUDDY._append_degree_normalised (reference models/elph.py:276-293): rows become [f, f / sqrt(d_u * d_v)]
-        // with NaN / Inf (zero-degree nodes) replaced by 0
-        const float normaliser = sqrtf(degrees[u] * degrees[v]);
-        float normed = my_f / normaliser;
-        if (isnan(normed) || isinf(normed)) normed = 0.0f;
+        // fused BUDDY._append_degree_normalised: rows become [f, f / sqrt(d_u * d_v)]
+        float normed = degree_normalised(my_f, degrees[u], degrees[v]);
         if (bad) normed = __uint_as_float(0x7FC00000u);
         if (l < NF) {
             out[q * (2 * NF) + l] = my_f;
@@ -267,7 +238,7 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
 // CAP: ask the register allocator for 4 (H <= 2) / 3 (H = 3) wavefronts per SIMD (some spills) instead of 3 / 2
 template <int H, int TP, int TM, bool CAP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H == 3 ? 3 : 4) : 1))) void pair_features_runs_kernel(const int64_t *__restrict__ links, const int32_t *__restrict__ order,
-                                                                 int64_t B, int64_t N, int K, PairTables tabs,
+                                                                 int64_t B, int64_t N, int K, HopTables tabs,
                                                                  const float *__restrict__ cards, int64_t cards_stride, ss_hll_params prm,
                                                                  uint32_t flags, float *__restrict__ out, int32_t *__restrict__ err,
                                                                  const float *__restrict__ degrees)
@@ -391,14 +362,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
                     }
                 }
             }
-            // lane c < H^2 finishes combination c, exactly as pair_features_kernel does
-            int my_mz = mz[0];
-            float my_hs = hs[0];
-#pragma unroll
-            for (int c = 1; c < NC; ++c) {
-                my_mz = (l == c) ? mz[c] : my_mz;
-                my_hs = (l == c) ? hs[c] : my_hs;
-            }
+            // lane c < H^2 finishes combination c, as pair_features_kernel does
+            // (written out, not a shared function: that moved the scratch bytes of the CAP builds -- DESIGN_EXPERIMENTS "One source for the pair finish")
+            const int my_mz = lane_select(mz, l);
+            const float my_hs = lane_select(hs, l);
             float my_I = 0.0f;
             if (l < NC) my_I = intersection_estimate(est, (int)((uint32_t)my_mz >> 20), my_mz & 0xFFFFF, my_hs, TP);
             float I[H][H];
@@ -406,13 +373,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
             for (int c = 0; c < NC; ++c) I[c / H][c % H] = __shfl(my_I, row_base + c);
             float f[NF];
             assemble_features<H>(I, c1, c2, flags, f);
-            float my_f = f[0];
-#pragma unroll
-            for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
-            if (degrees) {  // fused BUDDY._append_degree_normalised, as in pair_features_kernel
-                const float normaliser = sqrtf(degrees[ur] * degrees[vr]);
-                float normed = my_f / normaliser;
-                if (isnan(normed) || isinf(normed)) normed = 0.0f;
+            const float my_f = lane_select(f, l);
+            if (degrees) {
+                const float normed = degree_normalised(my_f, degrees[ur], degrees[vr]);
                 if (l < NF) {
                     out[q * (2 * NF) + l] = my_f;
                     out[q * (2 * NF) + NF + l] = normed;
@@ -426,7 +389,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
 
 // HEAD: the kernel with *head behind its arguments (ss_pair_scores) -- the same grid and the same choice of register budget
 template <int H, int TP, int TM, bool HEAD = false>
-int launch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &tabs, int P, int M, const float *cards,
+int launch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
                  int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
                  int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
                  bool grouped = false, const HeadArgs *head = nullptr)
@@ -457,36 +420,31 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &t
     const bool occ = occ_env >= 0 ? occ_env != 0 : (grouped || small_launch);
     {
         ProfileSpan span(stream, SS_PROF_PAIRS, true);
-        if constexpr (HEAD) {
-            if (occ && TP == 128 && H >= 2)
-                span.launch(pair_features_kernel<H, TP, TM, (TP == 128 && H >= 2), HeadArgs>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P,
-                            M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order, *head);
-            else
-                span.launch(pair_features_kernel<H, TP, TM, false, HeadArgs>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards,
-                            cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order, *head);
-        } else if (occ && TP == 128 && H >= 2)
-            span.launch(pair_features_kernel<H, TP, TM, (TP == 128 && H >= 2)>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards,
-                        cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order);
-        else
-            span.launch(pair_features_kernel<H, TP, TM>, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards, cards_stride, prm,
-                        flags, out, dbg_match, dbg_zero, dbg_inter, err, degrees, order);
+        constexpr bool HAS_OCC = TP == 128 && H >= 2;  // (elsewhere both names below are the one default-budget kernel)
+        const auto launch = [&](auto kernel, auto... head_args) {
+            span.launch(kernel, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match,
+                        dbg_zero, dbg_inter, err, degrees, order, head_args...);
+        };
+        if constexpr (HEAD) launch(occ ? pair_features_kernel<H, TP, TM, HAS_OCC, HeadArgs> : pair_features_kernel<H, TP, TM, false, HeadArgs>, *head);
+        else launch(occ ? pair_features_kernel<H, TP, TM, HAS_OCC> : pair_features_kernel<H, TP, TM>);
     }
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
 template <int H, bool HEAD = false>
-int dispatch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables &tabs, int P, int M, const float *cards,
+int dispatch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
                    int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
                    int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
                    bool grouped = false, const HeadArgs *head = nullptr)
 {
+    const bool fast = is_fast_pair_shape(P, M);
 #define SS_PAIRS_FAST(TP)                                                                                                      \
-    if (P == TP && M == 256)                                                                                                    \
+    if (P == TP && fast)                                                                                                        \
         return launch_pairs<H, TP, 256, HEAD>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, \
                                               dbg_inter, err, degrees, stream, order, grouped, head);
     SS_PAIRS_FAST(128)  // the reference's default shape
-    SS_PAIRS_FAST(64)   // the other permutation counts the first hop is specialised for (ss_first_hop: P / 64 = 1 .. 4)
+    SS_PAIRS_FAST(64)
     SS_PAIRS_FAST(192)
     SS_PAIRS_FAST(256)
 #undef SS_PAIRS_FAST
@@ -495,7 +453,7 @@ int dispatch_pairs(const int64_t *links, int64_t B, int64_t N, const PairTables 
 }
 
 template <int H, int TP>
-int launch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const PairTables &tabs, const float *cards,
+int launch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const HopTables &tabs, const float *cards,
                      int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *err, const float *degrees,
                      hipStream_t stream)
 {
@@ -522,7 +480,7 @@ int launch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int6
 }
 
 template <int H>
-int dispatch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const PairTables &tabs, int P, const float *cards,
+int dispatch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const HopTables &tabs, int P, const float *cards,
                        int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *err, const float *degrees,
                        hipStream_t stream)
 {
@@ -542,19 +500,11 @@ static int pair_features_impl(const int64_t *links, int64_t B, int64_t N, int32_
                               float *dbg_inter, int32_t *err_flag, void *stream, const int32_t *order = nullptr, bool grouped = false)
 {
     using namespace ss;
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;  // hashing.py:54, 308-309
-    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
-    const int rc = check_params(prm);
-    if (rc != SS_OK) return rc;
-    if (B == 0) return SS_OK;
+    const int rc = check_pair_query_args(h, B >= 0 && N >= 0, prm, P, B == 0);
+    if (rc != SS_OK || B == 0) return rc;
     if (N == 0 || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
-    PairTables tabs = {};
-    for (int k = 0; k < h; ++k) {
-        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
-        tabs.mh[k] = mh[k];
-        tabs.hll[k] = hll[k];
-    }
+    HopTables tabs;
+    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
     hipStream_t s = (hipStream_t)stream;
     switch (h) {
@@ -575,22 +525,14 @@ extern "C" int ss_pair_scores(const int64_t *links, const int32_t *order, int64_
     using namespace ss;
     if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
     if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    const int rc = check_params(prm);
+    if (B == 0) return SS_OK;  // (before prm is looked at, unlike the feature queries: so the two checks above are written out here)
+    const int rc = check_pair_query_args(h, true, prm, P);
     if (rc != SS_OK) return rc;
-    if (N == 0 || !links || !mh || !hll || !cards || !head || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
+    if (N == 0 || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
     if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices)
-    const int nf = h * (h + 2);
-    if (head->dim != (head->normalised ? 2 * nf : nf) || !head->w1 || !head->shift || !head->w2) return SS_ERR_INVALID_ARG;
-    if ((head->normalised != 0) != (degrees != nullptr)) return SS_ERR_INVALID_ARG;  // the head's width decides, not the pointer
-    PairTables tabs = {};
-    for (int k = 0; k < h; ++k) {
-        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
-        tabs.mh[k] = mh[k];
-        tabs.hll[k] = hll[k];
-    }
-    const HeadArgs args = {head->w1, head->shift, head->w2, head->bias, head->dim};
+    HeadArgs args;
+    HopTables tabs;
+    if (!make_head_args(head, h, degrees, args) || !fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
     hipStream_t s = (hipStream_t)stream;
     const bool grouped = order != nullptr;  // a walk with locality: the capped register budget, as ss_pair_features_grouped
@@ -687,14 +629,10 @@ static int pair_features_grouped_impl(int which /* -1: chosen per hop count, 0: 
                                       uint32_t flags, const float *degrees, float *out, int32_t *err_flag, void *stream)
 {
     using namespace ss;
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
-    const int rc = check_params(prm);
-    if (rc != SS_OK) return rc;
-    if (B == 0) return SS_OK;
+    const int rc = check_pair_query_args(h, B >= 0 && N >= 0, prm, P, B == 0);
+    if (rc != SS_OK || B == 0) return rc;
     if (N == 0 || N >= ((int64_t)1 << 31) || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
-    const bool fast = prm->p == 8 && (P == 64 || P == 128 || P == 192 || P == 256);
+    const bool fast = is_fast_pair_shape(P, 1 << prm->p);
     // Which kernel (measured, tools/probe_pair_runs.py -> profiles/round3_pair_runs_*.json, 4 M links): WITH an order the ordinary
     // kernel -- neighbouring lane groups take neighbouring positions, so the rows of a shared first node meet in the CU's L1 / the
     // L2 -- is ahead or level at every hop count (ppa-size tables, h = 2, random links grouped: 2.69 against 2.63 G pairs/s;
@@ -716,12 +654,8 @@ static int pair_features_grouped_impl(int which /* -1: chosen per hop count, 0: 
                                   err_flag, stream, order, /*grouped=*/true);
     }
     if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices, as on the other path)
-    PairTables tabs = {};
-    for (int k = 0; k < h; ++k) {
-        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
-        tabs.mh[k] = mh[k];
-        tabs.hll[k] = hll[k];
-    }
+    HopTables tabs;
+    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     switch (h) {
         case 1: return dispatch_pair_runs<1>(links, order, B, N, tabs, P, cards, cards_stride, *prm, flags, out, err_flag, degrees, s);

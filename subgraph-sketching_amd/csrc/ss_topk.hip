@@ -9,7 +9,7 @@
 // Mapping (the pair query's): one 16-lane DPP row per candidate v, lane l owning the 16-byte chunks l, l + 16, ... of a row.
 // A workgroup (16 rows) stages kTopkSources sources; each row holds its candidate's hop-k2 chunks in registers and walks the staged
 // sources.  Per (u, v) the statistics are accumulated per lane with the helpers of ss_pair_math.hpp and reduced with row16_sum_*,
-// exactly as pair_features_kernel does for that sketch shape: the fast shapes (p = 8, P in {64, 128, 192, 256}) compare digested
+// as pair_features_kernel does for that sketch shape (the generic shapes through pair_stats_generic, the function it calls): the fast shapes (p = 8, P in {64, 128, 192, 256}) compare digested
 // HLL chunks (the candidate's digest made once per candidate, the sources' once per workgroup, kept in LDS), every other shape
 // takes the generic byte-wise union, reading the sources' rows from global memory (cache-resident: every row of the workgroup
 // reads them).  The harmonic sums therefore add the same terms in the same order and the estimate is bit-identical to the
@@ -95,27 +95,24 @@ __global__ __launch_bounds__(256) void topk_scan_kernel(const int64_t *__restric
             const int nj = ns - g < kRow ? ns - g : kRow;
             for (int j = 0; j < nj; ++j) {  // row-uniform
                 const int s = g + j;
-                int match = 0, zeros = 0;
-                float hsum = 0.0f;
+                int mz;
+                float hs;
                 if constexpr (CMPL > 0) {
+                    int match = 0, zeros = 0;
+                    float hsum = 0.0f;
 #pragma unroll
                     for (int c = 0; c < CMPL; ++c) match += eq4(s_mh[s][l + kRow * c], mv[c]);
                     const u32x4 pe = s_pe[s][l], po = s_po[s][l];
                     const HllChunk hu = {{pe.x, pe.y, pe.z, pe.w}, {po.x, po.y, po.z, po.w}, s_zm[s][l]};
                     union_stats_digested(hu, hv, zeros, hsum);
+                    mz = row16_sum_i((match << 20) | zeros);
+                    hs = row16_sum_f(hsum);
                 } else {
                     const int64_t u = s_u[s] < 0 ? 0 : s_u[s];  // (an invalid source's entries become the sentinel below)
-                    for (int c = l; c < (P >> 2); c += kRow)
-                        match += eq4(*reinterpret_cast<const u32x4 *>(tabs.mh_u + u * P + 4 * c),
-                                     *reinterpret_cast<const u32x4 *>(tabs.mh_v + v * P + 4 * c));
-                    int nonzero = 0, chunks = 0;
-                    for (int c = l; c < (M >> 4); c += kRow, ++chunks)
-                        union_stats(*reinterpret_cast<const u32x4 *>(tabs.hll_u + u * M + 16 * c),
-                                    *reinterpret_cast<const u32x4 *>(tabs.hll_v + v * M + 16 * c), nonzero, hsum);
-                    zeros = 16 * chunks - nonzero;
+                    pair_stats_generic(reinterpret_cast<const u32x4 *>(tabs.mh_u + u * P), reinterpret_cast<const u32x4 *>(tabs.mh_v + v * P),
+                                       reinterpret_cast<const u32x4 *>(tabs.hll_u + u * M), reinterpret_cast<const u32x4 *>(tabs.hll_v + v * M),
+                                       P >> 2, M >> 4, l, mz, hs);
                 }
-                const int mz = row16_sum_i((match << 20) | zeros);
-                const float hs = row16_sum_f(hsum);
                 my_mz = l == j ? mz : my_mz;
                 my_hs = l == j ? hs : my_hs;
             }
@@ -162,10 +159,9 @@ extern "C" int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const 
                             size_t keys_bytes, int32_t *err_flag, void *stream)
 {
     using namespace ss;
-    const int rc = check_params(prm);
+    const int rc = check_pair_query_args(/*h=*/1, true, prm, P);  // (one hop pair: no hop count of its own)
     if (rc != SS_OK) return rc;
     if (S < 0 || N <= 0 || N >= ((int64_t)1 << 32) - 1) return SS_ERR_INVALID_ARG;  // (the key's low word holds 0xFFFFFFFF - v)
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
     if (S == 0) return SS_OK;
     if (!sources || !mh_src || !hll_src || !mh_cand || !hll_cand || !keys) return SS_ERR_INVALID_ARG;
     if (keys_bytes < ss_topk_workspace_bytes(N, S)) return SS_ERR_WORKSPACE;
@@ -178,8 +174,7 @@ extern "C" int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const 
     if (blocks_x > need_x) blocks_x = need_x;
     const dim3 grid((unsigned)blocks_x, (unsigned)blocks_y);
     hipStream_t s = (hipStream_t)stream;
-    const bool fast = M == 256 && (P == 64 || P == 128 || P == 192 || P == 256);  // dispatch_pairs' fast shapes
-    if (!fast) hipLaunchKernelGGL(topk_scan_kernel<0>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
+    if (!is_fast_pair_shape(P, M)) hipLaunchKernelGGL(topk_scan_kernel<0>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
     else if (P == 64) hipLaunchKernelGGL(topk_scan_kernel<1>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
     else if (P == 128) hipLaunchKernelGGL(topk_scan_kernel<2>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
     else if (P == 192) hipLaunchKernelGGL(topk_scan_kernel<3>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);

@@ -9,10 +9,11 @@
 // row.  A workgroup (16 rows) stages a block of sources once -- ALL h hops of each: MinHash chunks, HLL digests, cards[u][0..h)
 // and degrees[u] -- and every candidate row holds ITS h hops in registers (digests made once per candidate, cards[v] / degrees[v]
 // loaded once per candidate) while it walks the staged sources.  Per (u, v) all h^2 (match, zeros, harmonic sum) statistics are
-// accumulated with the helpers of ss_pair_math.hpp under the chunk ownership of pair_features_kernel and reduced with row16_sum_*,
-// then the pair kernel's own epilogue runs on the row: lane c < h^2 estimates combination c, the row assembles the features
-// (assemble_features), lane i makes the degree-normalised copy of feature i, head_score sums the head (DESIGN 3.11's orders).
-// Every operation and every order is the pair kernel's, so the score is bit-identical to ss_pair_scores' for the link (u, v).
+// accumulated with the helpers of ss_pair_math.hpp under the chunk ownership of pair_features_kernel (generic shapes: its own
+// pair_stats_generic) and reduced with row16_sum_*, then the pair kernel's epilogue runs on the row through the functions it calls: lane
+// c < h^2 estimates combination c (lane_select, intersection_estimate), the row assembles the features (assemble_features), lane i
+// makes the degree-normalised copy of feature i (degree_normalised), head_score sums the head (DESIGN 3.11's orders).  Every operation
+// and every order is the pair kernel's, so the score is bit-identical to ss_pair_scores' for the link (u, v).
 // The key of source j of a group of 16 is parked in lane j and the group's keys leave in one store.
 //
 // Sources per workgroup (kernel parameter SB, topk_head_sources()): as many of {32, 16, 8} as leave TWO workgroups per CU
@@ -25,11 +26,6 @@
 extern "C" size_t ss_topk_workspace_bytes(int64_t N, int32_t S);
 
 namespace ss {
-
-struct TopkHeadTables {
-    const uint32_t *mh[SS_MAX_HOPS];
-    const uint8_t *hll[SS_MAX_HOPS];
-};
 
 constexpr int kTopkHeadLds = 80 * 1024;  // LDS a workgroup may take: two per CU
 
@@ -49,7 +45,7 @@ constexpr int topk_head_sources(int H, int CMPL)
 
 // CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape (the sources' rows are read from global memory)
 template <int H, int CMPL>
-__global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__restrict__ sources, int S, int64_t N, TopkHeadTables tabs,
+__global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__restrict__ sources, int S, int64_t N, HopTables tabs,
                                                                int P_rt, int M, const float *__restrict__ cards, int64_t cards_stride,
                                                                ss_hll_params prm, uint32_t flags, const float *__restrict__ degrees,
                                                                HeadArgs head, int64_t *__restrict__ keys, int32_t *__restrict__ err)
@@ -158,33 +154,18 @@ __global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__r
                     }
                 } else {
                     const int64_t ur = u < 0 ? 0 : u;  // (an invalid source's entries become the sentinel below)
-                    const int CMr = P >> 2, CHr = M >> 4;
 #pragma unroll
                     for (int k1 = 0; k1 < H; ++k1)
 #pragma unroll
-                        for (int k2 = 0; k2 < H; ++k2) {
-                            int match = 0, nonzero = 0;
-                            float hsum = 0.0f;
-                            for (int c = l; c < CMr; c += kRow)
-                                match += eq4(*reinterpret_cast<const u32x4 *>(tabs.mh[k1] + ur * P + 4 * c),
-                                             *reinterpret_cast<const u32x4 *>(tabs.mh[k2] + v * P + 4 * c));
-                            int chunks = 0;
-                            for (int c = l; c < CHr; c += kRow, ++chunks)
-                                union_stats(*reinterpret_cast<const u32x4 *>(tabs.hll[k1] + ur * M + 16 * c),
-                                            *reinterpret_cast<const u32x4 *>(tabs.hll[k2] + v * M + 16 * c), nonzero, hsum);
-                            mz[k1 * H + k2] = row16_sum_i((match << 20) | (16 * chunks - nonzero));
-                            hs[k1 * H + k2] = row16_sum_f(hsum);
-                        }
+                        for (int k2 = 0; k2 < H; ++k2)
+                            pair_stats_generic(reinterpret_cast<const u32x4 *>(tabs.mh[k1] + ur * P), reinterpret_cast<const u32x4 *>(tabs.mh[k2] + v * P),
+                                               reinterpret_cast<const u32x4 *>(tabs.hll[k1] + ur * M), reinterpret_cast<const u32x4 *>(tabs.hll[k2] + v * M),
+                                               P >> 2, M >> 4, l, mz[k1 * H + k2], hs[k1 * H + k2]);
                 }
-                // from here on the epilogue of pair_features_kernel<..., HeadArgs>, operation for operation:
-                // lane c < H^2 finishes combination c: I = (match / P) * hll_count(union)
-                int my_mz = mz[0];
-                float my_hs = hs[0];
-#pragma unroll
-                for (int c = 1; c < NC; ++c) {
-                    my_mz = (l == c) ? mz[c] : my_mz;
-                    my_hs = (l == c) ? hs[c] : my_hs;
-                }
+                // from here on the epilogue of pair_features_kernel<..., HeadArgs>: its finish line for line, then the functions it calls
+                // (written out, not a shared function: that moved the VGPRs at h >= 2 -- DESIGN_EXPERIMENTS "One source for the pair finish")
+                const int my_mz = lane_select(mz, l);
+                const float my_hs = lane_select(hs, l);
                 float my_I = 0.0f;
                 if (l < NC) my_I = intersection_estimate(est, (int)((uint32_t)my_mz >> 20), my_mz & 0xFFFFF, my_hs, P);
                 float I[H][H];
@@ -195,15 +176,7 @@ __global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__r
                 for (int k = 0; k < H; ++k) c1[k] = s_c1[s][k];
                 float f[NF];
                 assemble_features<H>(I, c1, c2, flags, f);
-                float normed = 0.0f;
-                if (normalised) {  // the normalised copy of feature l in lane l, as the feature epilogue computes it
-                    float my_f = f[0];
-#pragma unroll
-                    for (int k = 1; k < NF; ++k) my_f = (l == k) ? f[k] : my_f;
-                    const float normaliser = sqrtf(s_deg[s] * deg_v);
-                    normed = my_f / normaliser;
-                    if (isnan(normed) || isinf(normed)) normed = 0.0f;
-                }
+                const float normed = normalised ? degree_normalised(lane_select(f, l), s_deg[s], deg_v) : 0.0f;
                 const float score = head_score<NF>(head_lds, head.dim, head.bias, f, normed, normalised, l, row_base);
                 const int64_t key = (u >= 0 && u != v) ? topk_key(score, v) : kTopkSentinel;
                 my_key = l == j ? key : my_key;
@@ -214,7 +187,7 @@ __global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__r
 }
 
 template <int H, int CMPL>
-void launch_topk_score_scan(const int64_t *sources, int S, int64_t N, const TopkHeadTables &tabs, int P, int M, const float *cards,
+void launch_topk_score_scan(const int64_t *sources, int S, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
                             int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
                             int64_t *keys, int32_t *err, hipStream_t stream)
 {
@@ -229,14 +202,13 @@ void launch_topk_score_scan(const int64_t *sources, int S, int64_t N, const Topk
 }
 
 template <int H>
-void dispatch_topk_score_scan(const int64_t *sources, int S, int64_t N, const TopkHeadTables &tabs, int P, int M, const float *cards,
+void dispatch_topk_score_scan(const int64_t *sources, int S, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
                               int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
                               int64_t *keys, int32_t *err, hipStream_t stream)
 {
 #define SS_TOPK_HEAD(CMPL) \
     launch_topk_score_scan<H, CMPL>(sources, S, N, tabs, P, M, cards, cards_stride, prm, flags, degrees, head, keys, err, stream)
-    const bool fast = M == 256 && (P == 64 || P == 128 || P == 192 || P == 256);  // dispatch_pairs' fast shapes
-    if (!fast) SS_TOPK_HEAD(0);
+    if (!is_fast_pair_shape(P, M)) SS_TOPK_HEAD(0);
     else if (P == 64) SS_TOPK_HEAD(1);
     else if (P == 128) SS_TOPK_HEAD(2);
     else if (P == 192) SS_TOPK_HEAD(3);
@@ -252,25 +224,17 @@ extern "C" int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, 
                                   void *stream)
 {
     using namespace ss;
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    const int rc = check_params(prm);
+    const int rc = check_pair_query_args(h, true, prm, P);
     if (rc != SS_OK) return rc;
     if (S < 0 || N <= 0 || N >= ((int64_t)1 << 32) - 1) return SS_ERR_INVALID_ARG;  // (the key's low word holds 0xFFFFFFFF - v)
-    if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
     if (S == 0) return SS_OK;
-    if (!sources || !mh || !hll || !cards || !head || !keys || cards_stride < h) return SS_ERR_INVALID_ARG;
-    const int nf = h * (h + 2);
-    if (head->dim != (head->normalised ? 2 * nf : nf) || !head->w1 || !head->shift || !head->w2) return SS_ERR_INVALID_ARG;
-    if ((head->normalised != 0) != (degrees != nullptr)) return SS_ERR_INVALID_ARG;  // the head's width decides, not the pointer
+    if (!sources || !mh || !hll || !cards || !keys || cards_stride < h) return SS_ERR_INVALID_ARG;
+    HeadArgs args;
+    if (!make_head_args(head, h, degrees, args)) return SS_ERR_INVALID_ARG;
     if (keys_bytes < ss_topk_workspace_bytes(N, S)) return SS_ERR_WORKSPACE;
-    TopkHeadTables tabs = {};
-    for (int k = 0; k < h; ++k) {
-        if (!mh[k] || !hll[k]) return SS_ERR_INVALID_ARG;
-        tabs.mh[k] = mh[k];
-        tabs.hll[k] = hll[k];
-    }
+    HopTables tabs;
+    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
     if (((int64_t)S + 7) / 8 > 65535) return SS_ERR_INVALID_ARG;  // (grid.y, at the smallest block of sources)
-    const HeadArgs args = {head->w1, head->shift, head->w2, head->bias, head->dim};
     const int M = 1 << prm->p;
     hipStream_t s = (hipStream_t)stream;
     switch (h) {

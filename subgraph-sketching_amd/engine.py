@@ -413,6 +413,48 @@ class ElphHashes(object):
                 raise ValueError('hash tables of different hops must have the same shape')
         return mh, hll, N, P
 
+    def _device_cards(self, cards, N, device):
+        """cards as float32 [N, >= max_hops] with unit column stride on `device`"""
+        h = self.max_hops
+        made_with = getattr(cards, '_ss_tables', None)
+        if made_with is not None and not hll_tables.same_tables(made_with, self.tables_id):
+            raise ValueError(f'cards were estimated with HLL++ tables {made_with}, this engine uses {self.tables_id}: '
+                             f'a feature row would mix two bias tables (rebuild the cache or load the same tables)')
+        # ELPH keeps `cards` on the CPU and the reference re-uploads it on every call (hashing.py:274): keep a device
+        # twin on the tensor, invalidated by in-place edits, so repeated eval batches do not pay the copy again
+        tag = getattr(cards, '_ss_cards', None)
+        if cards.device == device and cards.dtype == torch.float32:
+            cd = cards
+        elif tag is not None and tag[0] == cards._version and tag[1].device == device:
+            cd = tag[1]
+        else:
+            cd = cards.to(device=device, dtype=torch.float32)
+            _tag(cards, '_ss_cards', cd)
+        if cd.dim() != 2 or cd.size(0) != N or cd.size(1) < h:
+            raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
+        return cd if cd.stride(1) == 1 else cd.contiguous()
+
+    def _device_degrees(self, degrees, N, device):
+        """degrees (or None) as contiguous float32 [N] on `device`"""
+        if degrees is None:
+            return None
+        dg = degrees.to(device=device, dtype=torch.float32).contiguous()
+        if dg.dim() != 1 or dg.numel() != N:
+            raise ValueError(f'degrees must have shape [{N}], got {tuple(dg.shape)}')
+        return dg
+
+    def _check_head(self, head, degrees):
+        """what score_links and topk_links ask of their head before anything else is touched"""
+        from .head import StructureHead
+        if not isinstance(head, StructureHead):
+            raise ValueError(f'head must be a StructureHead (StructureHead.from_module(model)), got {type(head).__name__}')
+        if head.hops != self.max_hops:
+            raise ValueError(f'head.dim = {head.dim} belongs to max_hash_hops = {head.hops}, this engine has max_hash_hops = {self.max_hops}')
+        if head.normalised and degrees is None:
+            raise ValueError('head.normalised: the head takes the degree-normalised copy of the row, give degrees')
+        if degrees is not None and not head.normalised:
+            raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
+
     def _query_inputs(self, links, hash_table, cards, degrees, floor_sf, out, out_width, what):
         """what every launch of the pair kernel takes, resolved once per call (the feature query and score_links share it);
         out_width: columns per link of a caller-supplied `out` (None: one float per link, a 1-D tensor)"""
@@ -424,27 +466,7 @@ class ElphHashes(object):
         mh, hll, N, P = self._resolve_tables(hash_table, device, rows=lk)
         h = self.max_hops
         B = lk.size(0)
-        if cards is None:
-            cd = torch.zeros((N, h), dtype=torch.float32, device=device)
-        else:
-            made_with = getattr(cards, '_ss_tables', None)
-            if made_with is not None and not hll_tables.same_tables(made_with, self.tables_id):
-                raise ValueError(f'cards were estimated with HLL++ tables {made_with}, this engine uses {self.tables_id}: '
-                                 f'a feature row would mix two bias tables (rebuild the cache or load the same tables)')
-            # ELPH keeps `cards` on the CPU and the reference re-uploads it on every call (hashing.py:274): keep a device
-            # twin on the tensor, invalidated by in-place edits, so repeated eval batches do not pay the copy again
-            tag = getattr(cards, '_ss_cards', None)
-            if cards.device == device and cards.dtype == torch.float32:
-                cd = cards
-            elif tag is not None and tag[0] == cards._version and tag[1].device == device:
-                cd = tag[1]
-            else:
-                cd = cards.to(device=device, dtype=torch.float32)
-                _tag(cards, '_ss_cards', cd)
-            if cd.dim() != 2 or cd.size(0) != N or cd.size(1) < h:
-                raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
-            if cd.stride(1) != 1:
-                cd = cd.contiguous()
+        cd = torch.zeros((N, h), dtype=torch.float32, device=device) if cards is None else self._device_cards(cards, N, device)
         shape = (B,) if out_width is None else (B, out_width)
         if out is not None and (out.device != device or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
             raise ValueError(f'out must be a contiguous float32 {list(shape)} tensor on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}')
@@ -455,11 +477,7 @@ class ElphHashes(object):
         strict, err = self._bounds(device, f'{what}({B} links, num_nodes={N})')
         if strict:
             err = _error_flag(device)  # (non-strict launches never touch the shared flag)
-        dg = None
-        if degrees is not None:
-            dg = degrees.to(device=device, dtype=torch.float32).contiguous()
-            if dg.dim() != 1 or dg.numel() != N:
-                raise ValueError(f'degrees must have shape [{N}], got {tuple(dg.shape)}')
+        dg = self._device_degrees(degrees, N, device)
         return device, params, lk, (mh, hll), mh_ptrs, hll_ptrs, N, P, B, cd, flags, strict, err, dg
 
     def _pair_kernel(self, links, hash_table, cards, want_debug=False, degrees=None, floor_sf=None, group_batch=None, out=None):
@@ -595,18 +613,10 @@ class ElphHashes(object):
                  reports it, in every strict_bounds mode
         Inference only -- there are no gradients.  Out of scope (ValueError where an argument suggests otherwise): a head on the
         masked query (mask_target), lazy stores, dist.sharded_precompute.  The head inside the one-vs-all scan is topk_links.  No CPU fallback."""
-        from .head import StructureHead
         if unsupported:
             names = ', '.join(sorted(unsupported))
             raise ValueError(f'score_links does not take {names}: the head runs behind the plain query only (no mask_target, no lazy store)')
-        if not isinstance(head, StructureHead):
-            raise ValueError(f'head must be a StructureHead (StructureHead.from_module(model)), got {type(head).__name__}')
-        if head.hops != self.max_hops:
-            raise ValueError(f'head.dim = {head.dim} belongs to max_hash_hops = {head.hops}, this engine has max_hash_hops = {self.max_hops}')
-        if head.normalised and degrees is None:
-            raise ValueError('head.normalised: the head takes the degree-normalised copy of the row, give degrees')
-        if degrees is not None and not head.normalised:
-            raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
+        self._check_head(head, degrees)
         if links.dim() == 1:
             links = links.unsqueeze(0)
         _native.lib()  # (NativeLibraryMissing before anything else is touched)
@@ -700,7 +710,7 @@ class ElphHashes(object):
         params = self._params(device)
         extra = ()
         if cards is not None:
-            extra = self._topk_cards(cards, degrees, N, device)
+            extra = (self._device_cards(cards, N, device), self._device_degrees(degrees, N, device))
         lk = src.to(device=device, dtype=torch.int64).contiguous()
         strict, err = self._bounds(device, f'{what}({S} sources, num_nodes={N})')
         csr = None
@@ -738,32 +748,6 @@ class ElphHashes(object):
             self._deferred.raise_if_set()
         return ids, scores
 
-    def _topk_cards(self, cards, degrees, N, device):
-        """(cards float32 [N, >= h] with unit column stride, degrees float32 [N] or None) on `device`, as _query_inputs resolves them"""
-        h = self.max_hops
-        made_with = getattr(cards, '_ss_tables', None)
-        if made_with is not None and not hll_tables.same_tables(made_with, self.tables_id):
-            raise ValueError(f'cards were estimated with HLL++ tables {made_with}, this engine uses {self.tables_id}: '
-                             f'a feature row would mix two bias tables (rebuild the cache or load the same tables)')
-        tag = getattr(cards, '_ss_cards', None)
-        if cards.device == device and cards.dtype == torch.float32:
-            cd = cards
-        elif tag is not None and tag[0] == cards._version and tag[1].device == device:
-            cd = tag[1]
-        else:
-            cd = cards.to(device=device, dtype=torch.float32)
-            _tag(cards, '_ss_cards', cd)
-        if cd.dim() != 2 or cd.size(0) != N or cd.size(1) < h:
-            raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
-        if cd.stride(1) != 1:
-            cd = cd.contiguous()
-        dg = None
-        if degrees is not None:
-            dg = degrees.to(device=device, dtype=torch.float32).contiguous()
-            if dg.dim() != 1 or dg.numel() != N:
-                raise ValueError(f'degrees must have shape [{N}], got {tuple(dg.shape)}')
-        return cd, dg
-
     def topk_links(self, sources, hash_table, cards, k, head, degrees=None, exclude=None):
         """the k link partners a trained model's structure head ranks highest for every source: topk_candidates' one-vs-all scan with
         score_links' score instead of one raw intersection estimate (csrc/ss_topk_head.hip) -- what full-ranking
@@ -779,15 +763,7 @@ class ElphHashes(object):
                  with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only.
         Ids outside [-N, N) are reported as topk_candidates reports them.  Non-finite scores (overflow under absurd weights) are
         outside the contract.  Inference only; out of scope: the masked query behind the scan, dist sharding.  No CPU fallback."""
-        from .head import StructureHead
-        if not isinstance(head, StructureHead):
-            raise ValueError(f'head must be a StructureHead (StructureHead.from_module(model)), got {type(head).__name__}')
-        if head.hops != self.max_hops:
-            raise ValueError(f'head.dim = {head.dim} belongs to max_hash_hops = {head.hops}, this engine has max_hash_hops = {self.max_hops}')
-        if head.normalised and degrees is None:
-            raise ValueError('head.normalised: the head takes the degree-normalised copy of the row, give degrees')
-        if degrees is not None and not head.normalised:
-            raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
+        self._check_head(head, degrees)
         if cards is None:
             raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
         src, ex, N, P = self._topk_arguments(sources, hash_table, k, exclude)
