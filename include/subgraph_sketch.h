@@ -376,6 +376,21 @@ int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, int32_t h, 
                        const float *degrees, const ss_structure_head *head, int64_t *keys, size_t keys_bytes, int32_t *err_flag,
                        void *stream);
 
+/* Each link's exact rank among all nodes by the structure head -- what MRR / Hits@K of positive links over all N candidates need
+ * (reference src/evaluation.py ranks a positive among sampled negatives): for link q = (u, t) = links[q] and every node v other
+ * than u and t, the score ss_pair_scores gives the pair (u, v), bit for bit, is compared with thr[q] and COUNTED:
+ *     counts[q][0] += #{v : s(u, v) >  thr[q]},     counts[q][1] += #{v : s(u, v) == thr[q]}     (float compares: -0 == +0).
+ *   links: device int64 [L, 2] (torch-style negative ids wrapped; a link with an id outside [-N, N) sets err_flag, nullable, and
+ *   adds nothing).  thr: device fp32 [L], what ss_pair_scores wrote for the same links with the same arguments -- the scan holds no
+ *   second form of the score, so thr[q] compares exactly with s(u, t).  counts: device int64 [L, 2], ZEROED by the caller: the
+ *   workgroups of the launch add into it with 64-bit integer atomics, nothing else is stored, and the sums do not depend on the
+ *   grid.  Every other argument as ss_topk_score_scan takes it.  N < 2^32; L <= 8 * 65535 per launch.  An exclude list is the
+ *   caller's correction: subtract the comparisons of ss_pair_scores over the excluded pairs (ElphHashes.rank_links). */
+int ss_rank_score_scan(const int64_t *links, const float *thr, int32_t L, int64_t N, int32_t h, const uint32_t *const *mh,
+                       const uint8_t *const *hll, int32_t P, const float *cards, int64_t cards_stride, const ss_hll_params *prm,
+                       uint32_t flags, const float *degrees, const ss_structure_head *head, int64_t *counts, int32_t *err_flag,
+                       void *stream);
+
 /* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
  * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
  * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,

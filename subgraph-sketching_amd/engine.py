@@ -25,6 +25,9 @@ LABEL_LOOKUP = {1: {0: (1, 1), 1: (0, 1), 2: (1, 0)},
 # ---- one-vs-all link candidates (ElphHashes.topk_candidates, csrc/ss_topk.hip) -----------------------------------------------------
 TOPK_SENTINEL = -(1 << 63)  # the key of an ineligible candidate (v == u, excluded, out-of-range source): below every real key
 _TOPK_KEY_BYTES = 1 << 31   # bound on one block's key buffer [sources, N] int64 (rows do not depend on it; not a user knob)
+# ---- each link's rank among all nodes (ElphHashes.rank_links, csrc/ss_rank.hip): rows depend on neither constant ------------------------
+_RANK_LAUNCH_LINKS = 8 * 65535  # links per ss_rank_score_scan launch: grid.y at the smallest block of staged links
+_RANK_EXCLUDE_PAIRS = 1 << 22   # excluded (link, partner) pairs scored and compared at a time (the exclusion correction)
 
 
 def _decode_topk_keys(keys):
@@ -676,11 +679,12 @@ class ElphHashes(object):
 
         return self._topk_run('topk_candidates', src, ex, hash_table, int(k), scan)
 
-    def _topk_arguments(self, sources, hash_table, k, exclude):
-        """what topk_candidates and topk_links check before a device is touched: (sources, exclude or None, N, P)"""
+    def _topk_arguments(self, sources, hash_table, k, exclude, what='sources'):
+        """what topk_candidates, topk_links and rank_links (its links, flattened: what='links') check before a device is touched:
+        (sources, exclude or None, N, P)"""
         src = torch.as_tensor(sources)
         if src.dim() != 1 or src.dtype.is_floating_point or src.dtype == torch.bool:
-            raise ValueError(f'sources must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
+            raise ValueError(f'{what} must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
         N, P = _table_shape(hash_table, 1)
         _check_sizes(P, self.p)
         k = int(k)
@@ -693,7 +697,7 @@ class ElphHashes(object):
                 raise ValueError(f'exclude must be an integer [2, E] edge_index, got {ex.dtype} {tuple(ex.shape)}')
         # CPU ids are checked here, as the reference's CPU indexing would; device ids are reported late (strict_bounds)
         if not src.is_cuda and src.numel() and (int(src.min()) < -N or int(src.max()) >= N):
-            raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
+            raise IndexError(f'{what} refer to nodes outside [-{N}, {N})')
         if ex is not None and not ex.is_cuda and ex.numel() and (int(ex.min()) < -N or int(ex.max()) >= N):
             raise IndexError(f'exclude refers to nodes outside [-{N}, {N})')
         return src, ex, N, P
@@ -762,7 +766,8 @@ class ElphHashes(object):
         @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows
                  with fewer than k eligible candidates end in id -1 / score -inf.  A row depends on its own source only.
         Ids outside [-N, N) are reported as topk_candidates reports them.  Non-finite scores (overflow under absurd weights) are
-        outside the contract.  Inference only; out of scope: the masked query behind the scan, dist sharding.  No CPU fallback."""
+        outside the contract.  Inference only; out of scope: the masked query behind the scan, dist sharding.  No CPU fallback.
+        The exact rank of a GIVEN link among all nodes (MRR / Hits@K at any depth, no keys): rank_links."""
         self._check_head(head, degrees)
         if cards is None:
             raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
@@ -778,6 +783,129 @@ class ElphHashes(object):
                                                  _ptr(dg), byref(hd.struct), _ptr(keys), nbytes, _ptr(err), stream), 'ss_topk_score_scan')
 
         return self._topk_run('topk_links', src, ex, hash_table, int(k), scan, cards=cards, degrees=degrees)
+
+    def rank_links(self, links, hash_table, cards, head, degrees=None, exclude=None, **unsupported):
+        """at which rank a trained model's structure head puts each link (u, t) among ALL link partners of u: what MRR / Hits@K of
+        positive links over all nodes ask for (reference src/evaluation.py ranks a positive among sampled negatives).  With s(u, v)
+        the float32 score_links([[u, v]], hash_table, cards, head, degrees=degrees) returns, bit for bit, and the candidates
+        C_q = {v in [0, N) : v != u, v != t, (u -> v) not in exclude} of link q = (u, t):
+
+            greater[q] = #{v in C_q : s(u, v) > s(u, t)},     equal[q] = #{v in C_q : s(u, v) == s(u, t)}
+
+        (float compares: -0.0 == +0.0, as topk_links folds it).  Optimistic rank 1 + greater, pessimistic 1 + greater + equal; the
+        place of t in the topk_links(u, k = N) row is greater + #{tied v < t}.  The one-vs-all scan of topk_links with two counters
+        per link in registers instead of its 8 N bytes of ranking keys per source: 16 bytes per link are written, nothing is
+        selected (csrc/ss_rank.hip).
+        @param links: int [L, 2] (or [2]) rows (u, t), torch-style negative ids allowed, CPU or device; u == t is a link like any other
+        @param hash_table, cards, head, degrees: as score_links / topk_links take them (head.normalised requires degrees; degrees
+               without it is a ValueError)
+        @param exclude: optional int [2, E] edge_index read as a SET of directed pairs u -> v (duplicates, self loops, negative ids
+               allowed): such a v is no candidate of u.  The target is never a candidate of itself, so (u -> t) in it changes nothing
+               (the filtered setting, where positives are edges)
+        @return: (greater int64 [L], equal int64 [L]) on links.device.  A row depends on its own link only -- not on L, the order,
+                 duplicates or how the call is split into launches.  Ids outside [-N, N), in links or exclude, are reported as
+                 topk_links reports them; both counts of such a link are -1.
+        Non-finite scores are outside the contract.  Inference only; out of scope: the masked query behind the scan, dist sharding,
+        de-duplicating links that share a source (each link is scanned on its own).  No CPU fallback."""
+        if unsupported:
+            names = ', '.join(sorted(unsupported))
+            raise ValueError(f'rank_links does not take {names}: the head runs behind the plain query only (no mask_target, no lazy store)')
+        self._check_head(head, degrees)
+        if cards is None:
+            raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
+        lk = torch.as_tensor(links)
+        if lk.dim() == 1:
+            lk = lk.unsqueeze(0)
+        if lk.dim() != 2 or lk.size(1) != 2:
+            raise ValueError(f'links must be an integer [L, 2] tensor, got {lk.dtype} {tuple(lk.shape)}')
+        _, ex, N, P = self._topk_arguments(lk.reshape(-1), hash_table, 1, exclude, what='links')
+        home, L = lk.device, lk.size(0)
+        if L == 0:
+            return torch.empty(0, dtype=torch.int64, device=home), torch.empty(0, dtype=torch.int64, device=home)
+        first = hash_table.get(1) if hasattr(hash_table, 'get') else None
+        device = _compute_device(lk, first.mh_u32 if isinstance(first, HopSketch) else None, cards)
+        mh, hll, N, P = self._resolve_tables(hash_table, device)
+        params = self._params(device)
+        cd, dg, hd = self._device_cards(cards, N, device), self._device_degrees(degrees, N, device), head._device(device)
+        h = self.max_hops
+        mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
+        hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
+        flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if self.floor_sf else 0)
+        lk = lk.to(device=device, dtype=torch.int64).contiguous()
+        strict, err = self._bounds(device, f'rank_links({L} links, num_nodes={N})')
+        csr = None
+        if ex is not None:
+            ex = ex.to(device=device, dtype=torch.int64)
+            ex = torch.where(ex < 0, ex + N, ex)  # (ids below -N stay negative: out of range)
+            csr = build_csr(ex.flip(0), N, device, check=strict, err_flag=None if strict else err)  # row u = {v : u -> v}
+        if strict:
+            err = _error_flag(device)
+        lib = _native.lib()
+
+        def scores(pairs, out):
+            """the ONE form of s(u, v): the launch behind score_links, for the thresholds and for the excluded pairs"""
+            with _Span('pair_scores', device):
+                _native.check(lib.ss_pair_scores(_ptr(pairs), None, pairs.size(0), N, h, mh_ptrs, P, hll_ptrs, _ptr(cd), cd.stride(0),
+                                                 byref(params.struct), flags, _ptr(dg), byref(hd.struct), _ptr(out), _ptr(err),
+                                                 _stream(device)), 'ss_pair_scores')
+            return out
+
+        thr = scores(lk, torch.empty((L,), dtype=torch.float32, device=device))
+        counts = torch.zeros((L, 2), dtype=torch.int64, device=device)
+        for s0 in range(0, L, _RANK_LAUNCH_LINKS):
+            nb = min(_RANK_LAUNCH_LINKS, L - s0)
+            with _Span('rank_scan', device):
+                _native.check(lib.ss_rank_score_scan(c_void_p(lk.data_ptr() + 16 * s0), c_void_p(thr.data_ptr() + 4 * s0), nb, N, h, mh_ptrs,
+                                                     hll_ptrs, P, _ptr(cd), cd.stride(0), byref(params.struct), flags, _ptr(dg),
+                                                     byref(hd.struct), c_void_p(counts.data_ptr() + 16 * s0), _ptr(err), _stream(device)),
+                              'ss_rank_score_scan')
+        wrapped = torch.where(lk < 0, lk + N, lk)
+        bad = ((wrapped < 0) | (wrapped >= N)).any(dim=1)
+        if csr is not None:
+            with _Span('rank_exclude', device):
+                self._rank_exclusion(counts, wrapped, bad, thr, csr, N, scores)
+        counts.masked_fill_(bad.unsqueeze(1), -1)
+        if strict and _take_error(device):
+            raise IndexError(f'links refer to nodes outside [-{N}, {N})')
+        greater, equal = counts[:, 0].contiguous(), counts[:, 1].contiguous()
+        if home == device:
+            return greater, equal
+        greater, equal = greater.to(home), equal.to(home)
+        if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
+            self._deferred.raise_if_set()
+        return greater, equal
+
+    @staticmethod
+    def _rank_exclusion(counts, links, bad, thr, csr, N, scores):
+        """the scan has counted every v != u, t; the excluded partners of each link's source are taken back out of counts [L, 2]:
+        the set {v : u -> v in the exclude CSR} \\ {u, t} per link, s(u, v) from `scores`, compared with thr as the scan compares.
+        links: wrapped ids; bad: links with an id out of range (they take no part).  Two host reads (the sizes of the two gathers)."""
+        device = links.device
+        u = links[:, 0].masked_fill(bad, 0)
+        # the rows of the DISTINCT sources, each partner once: sorted keys source * N + v (the CSR's rows hold duplicates, unordered)
+        us, of_link = torch.unique(u, return_inverse=True)
+        deg = csr.rowptr[us + 1] - csr.rowptr[us]
+        ends = torch.cumsum(deg, 0)
+        total = int(ends[-1].item())
+        if total == 0:
+            return
+        e = torch.arange(total, dtype=torch.int64, device=device)
+        s = torch.searchsorted(ends, e, right=True)
+        v = csr.col[csr.rowptr[us[s]] + (e - (ends[s] - deg[s]))].to(torch.int64)
+        keys = torch.unique(s * N + v)
+        row = torch.searchsorted(keys, torch.arange(us.numel() + 1, dtype=torch.int64, device=device) * N)
+        # per link the extent of its source's row in `keys`; the pairs (link, partner) are walked flat, _RANK_EXCLUDE_PAIRS at a time
+        n_q = (row[of_link + 1] - row[of_link]).masked_fill(bad, 0)
+        q_ends = torch.cumsum(n_q, 0)
+        pairs = int(q_ends[-1].item())
+        for a in range(0, pairs, _RANK_EXCLUDE_PAIRS):
+            e = torch.arange(a, min(a + _RANK_EXCLUDE_PAIRS, pairs), dtype=torch.int64, device=device)
+            q = torch.searchsorted(q_ends, e, right=True)
+            v = keys[row[of_link[q]] + (e - (q_ends[q] - n_q[q]))] % N
+            sc = scores(torch.stack([u[q], v], dim=1).contiguous(), torch.empty((e.numel(),), dtype=torch.float32, device=device))
+            candidate = (v != links[q, 0]) & (v != links[q, 1])
+            hit = torch.stack([(sc > thr[q]) & candidate, (sc == thr[q]) & candidate], dim=1).to(torch.int64)
+            counts.index_add_(0, q, -hit)
 
     def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, mask_target=False):
         """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph

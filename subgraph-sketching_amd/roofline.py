@@ -147,6 +147,30 @@ def topk_links_bytes(N, S, h, P, M):
     return blocks_y * N * h * R + blocks_x * S * h * R + 8 * S * N
 
 
+def rank_links_queries(h, P, M):
+    """links a workgroup of the ranking scan stages (csrc/ss_rank.hip rank_queries): topk_links_sources' rule with 20 more bytes per
+    staged entry -- the target id, the threshold and the two 32-bit sums -- so 32 + 4h bytes next to the h rows of the fast shapes"""
+    fast = M == 256 and P in (64, 128, 192, 256)
+    per_query = 32 + 4 * h + (h * (4 * P + 576) if fast else 0)
+    for qb in (32, 16):
+        if 8196 + 3840 + 64 + qb * per_query <= 80 * 1024:
+            return qb
+    return 8
+
+
+def rank_links_bytes(N, L, h, P, M):
+    """algorithmic bytes of one ss_rank_score_scan launch (ElphHashes.rank_links): every candidate's h rows of 4P + M
+    bytes once per block of staged links -- table rows read once per workgroup pass --, the sources' h rows, the 16-byte link and its
+    4-byte threshold once per workgroup (the launch aims for 4 096 workgroups, 16 candidates in flight each), and the two int64 counts
+    of every link: 16 L bytes written, whatever N.  The candidates' cards / degrees, the threshold launch (score_query_bytes(L)) and
+    the exclusion correction (score_query_bytes over the excluded pairs) are not in it."""
+    R = 4 * P + M
+    qb = rank_links_queries(h, P, M)
+    blocks_y = -(-L // qb)
+    blocks_x = min(-(-4096 // max(blocks_y, 1)), -(-N // 16))
+    return blocks_y * N * h * R + blocks_x * L * (h * R + 20) + 16 * L
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
