@@ -11,6 +11,8 @@ References: tests/large_table_restatement.py (one hop in blocked stock torch ope
 tests/test_large_table_restatement_host.py) for whole tables; the C oracle on a COMPACTED table (the distinct rows a query touches,
 gathered to the host and renumbered) for queries.  Supported limits these tests establish: DESIGN.md section 4.
 
+update_hash_tables, mask_target, score_links, topk_links, rank_links and PPR at these sizes: tests/test_large_tables_links_gpu.py.
+
 Measured peaks (`torch.cuda.max_memory_allocated()`, profiles/large_tables_tests.txt) set the fixtures' free-memory requirements."""
 from argparse import Namespace
 
@@ -20,12 +22,13 @@ import torch
 
 from conftest import oracle_params
 import large_table_restatement as R
+from large_table_helpers import ATOL, GB, LIVE as _LIVE, Big as _Big, boundary_links as _boundary_links, compacted_oracle as _compacted_oracle, \
+    feature_tol as _feature_tol, release_all as _release_all
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-5, 1e-4
+RTOL = 1e-5
 LC_RTOL = 3e-7
-GB = 1 << 30
 SHAPES = {'A': ((1 << 23) + (1 << 18), [1 << 22, 1 << 23]), 'B': ((1 << 24) + (1 << 18), [1 << 22, 1 << 23, 1 << 24])}
 # free device memory a fixture asks for: the measured peak of its tests + 10 % (profiles/large_tables_tests.txt)
 NEEDS = {'A': int(1.1 * 52526602240), 'B': int(1.1 * 83686005760), 'spmm': int(1.1 * 9886710784)}
@@ -49,32 +52,6 @@ def _eh(ssa, **kw):
     eh = ssa.ElphHashes(Namespace(max_hash_hops=2, hll_p=8, minhash_num_perm=128, floor_sf=False, use_zero_one=True), **kw)
     eh.hll_tables = ssa.hll_tables.load(eh.p, prefer='regenerated')
     return eh
-
-
-class _Big(object):
-    """what a fixture holds; release() reports the peak of the tests that used it and drops its device tensors (building fixture B
-    and the last test release fixture A: a module-scoped fixture would otherwise live until the end of the module)"""
-    table = None
-
-    def release(self):
-        if self.table is None:
-            return
-        peak = torch.cuda.max_memory_allocated()
-        print(f'\n[large tables] fixture {self.name}: N = {self.n}, peak torch.cuda.max_memory_allocated() = {peak} bytes ({peak / GB:.2f} GiB)')
-        for name in ('graph', 'blocks', 'table', 'cards', 'eh'):
-            setattr(self, name, None)
-        torch.cuda.empty_cache()
-
-
-_LIVE = []
-
-
-def _release_all(dev):
-    for big in _LIVE:
-        big.release()
-    del _LIVE[:]
-    torch.cuda.synchronize(dev)
-    torch.cuda.empty_cache()
 
 
 def _make(ssa, dev, name):
@@ -152,54 +129,6 @@ def _check_build(ssa, big, variant, monkeypatch):
     _assert_tables(table, big, f'fixture {big.name}, {variant}')
     if variant != 'default':  # (the default build's cards: test 3)
         assert torch.equal(cards, big.cards)
-
-
-def _wrap(ids, n):
-    return torch.where(ids < 0, ids + n, ids)
-
-
-def _compacted_oracle(big, links, degrees=None, debug=False):
-    """oracle.pair_features on the distinct rows `links` touch, gathered to the host and renumbered"""
-    from oracle import oracle
-    ids = _wrap(links.to(torch.int64), big.n)
-    uniq, inv = torch.unique(ids.flatten(), return_inverse=True)
-    otab = {k: {'minhash': big.table[k].mh_u32.index_select(0, uniq).cpu().numpy().view(np.uint32),
-                'hll': big.table[k].hll_u8.index_select(0, uniq).cpu().numpy()} for k in (1, 2)}
-    ocards = big.cards.index_select(0, uniq).cpu().numpy()
-    small = inv.reshape(-1, 2).cpu().numpy()
-    res = oracle.pair_features(small, otab, ocards, 2, big.prm, debug=debug)
-    feats, dbg = res if debug else (res, None)
-    if degrees is not None:
-        feats = oracle.append_degree_normalised(feats, small, degrees.index_select(0, uniq).cpu().numpy())
-    return feats, dbg
-
-
-def _feature_tol(ofeat):
-    return dict(rtol=1e-4, atol=ATOL * max(1.0, float(np.abs(ofeat).max()) / 100))
-
-
-def _boundary_links(big, dev, count, seed):
-    """links whose endpoints are (low, high), (high, low), (high, high) across every boundary, the boundary rows themselves, N - 1,
-    the hubs, u == v, and negative ids that wrap to high rows"""
-    gen = torch.Generator(device=dev).manual_seed(seed)
-    n, w = big.n, big.graph.window
-    parts = []
-    per = (count - 64) // (4 * len(big.bounds))
-    for b in big.bounds:
-        lo = torch.randint(b - w, b, (per, 2), device=dev, generator=gen)
-        hi = torch.randint(b, b + w, (per, 2), device=dev, generator=gen)
-        far = torch.randint(b + w, n, (per, 2), device=dev, generator=gen)
-        parts += [torch.stack([lo[:, 0], hi[:, 0]], 1), torch.stack([hi[:, 1], lo[:, 1]], 1), hi, torch.stack([far[:, 0], hi[:, 0]], 1)]
-        parts.append(torch.tensor([[b, b - 1], [b - 1, b], [b, b], [b + 1, b], [b, n - 1], [n - 1, b], [0, b], [b, big.graph.mega],
-                                   [big.graph.hubs[0], b - 1]], device=dev))
-    parts.append(torch.tensor([[n - 1, n - 1], [n - 1, 0], [n - 2, n - 1], [big.graph.mega, big.graph.hubs[1]]], device=dev))
-    links = torch.cat(parts)
-    fill = torch.randint(0, n, (count - links.size(0), 2), device=dev, generator=gen)
-    links = torch.cat([links, fill])[:count].contiguous()
-    links[::5] -= n        # torch-style negative ids: -1 is row N - 1, -(2^18) is row 2^23 (fixture A) / 2^24 (B)
-    links[7, 0] = links[7, 1]
-    links[1] = torch.tensor([-1, -(1 << 18)], device=dev)
-    return links
 
 
 # ---------------------------------------------------------------------------------------------------
