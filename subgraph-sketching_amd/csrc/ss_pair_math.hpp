@@ -6,7 +6,9 @@
 // have ONE source here for pair_features_kernel, pair_features_runs_kernel, topk_score_scan_kernel and masked_pairs_kernel.  The finish
 // of a pair between them -- lane c < h^2: intersection_estimate, __shfl of I to the row, assemble_features -- stays written out in each
 // of the four: as one function it changed their registers (DESIGN_EXPERIMENTS "One source for the pair finish").  The host half at the
-// end is what their entry points share: the table pointers and the argument checks.
+// end is what their entry points share: the table pointers and the argument checks.  rank_score_scan_kernel (ss_rank.hip) repeats the
+// body of topk_score_scan_kernel: one source for the two was built and measured -- two instantiations changed occupancy and the scan
+// was 1 - 2 % slower -- so both stay written out and share their host half only (ss_head_scan.hpp, DESIGN_EXPERIMENTS 3.13).
 #pragma once
 #include "ss_feature_algebra.hpp"
 

@@ -19,29 +19,17 @@
 //
 // Links per workgroup (rank_queries()): as many of {32, 16, 8} as leave TWO workgroups per CU (2 x 80 KiB of the 160 KiB LDS) next
 // to the estimator and head tables -- a link costs 256 * CMPL + 576 bytes per hop plus 32 + 4 h bytes of ids, sizes, threshold and sums.
+// The budget behind it, the launch geometry, the (h, CMPL) dispatch and the shared entry checks: ss_head_scan.hpp.  The kernel body is
+// written out here and in ss_topk_head.hip: one source for both was measured and dropped (DESIGN_EXPERIMENTS 3.13).
 #include "ss_feature_algebra.hpp"
-#include "ss_head.hpp"
+#include "ss_head_scan.hpp"
 #include "ss_pair_math.hpp"
 #include "ss_topk_key.hpp"
 
 namespace ss {
 
-constexpr int kRankLds = 80 * 1024;  // LDS a workgroup may take: two per CU
-
-// bytes of LDS per staged link: source and target ids, cards, degree, threshold, two sums and, on the fast shapes, h rows of MinHash
-// chunks and HLL digests of the source
-constexpr int rank_query_bytes(int H, int CMPL)
-{
-    return 8 + 8 + 4 * H + 4 + 4 + 8 + (CMPL > 0 ? H * (CMPL * kRow * 16 + kRow * (16 + 16 + 4)) : 0);
-}
-
-constexpr int rank_queries(int H, int CMPL)
-{
-    const int fixed = (int)sizeof(EstimatorLds) + (int)sizeof(HeadLds) + 64;  // (64: alignment between the arrays)
-    for (int qb = 32; qb > 8; qb >>= 1)
-        if (fixed + qb * rank_query_bytes(H, CMPL) <= kRankLds) return qb;
-    return 8;
-}
+// links per workgroup: next to the entry of ss_head_scan.hpp a link stages its target id, its threshold and two sums
+constexpr int rank_queries(int H, int CMPL) { return head_scan_entries(H, CMPL, 8 + 4 + 8); }
 
 // CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape (the sources' rows are read from global memory)
 template <int H, int CMPL>
@@ -221,36 +209,6 @@ __global__ __launch_bounds__(256) void rank_score_scan_kernel(const int64_t *__r
     }
 }
 
-template <int H, int CMPL>
-void launch_rank_score_scan(const int64_t *links, const float *thr, int L, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                            int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
-                            int64_t *counts, int32_t *err, hipStream_t stream)
-{
-    constexpr int QB = rank_queries(H, CMPL);
-    static_assert(QB >= 8 && QB <= 32, "threads 0 .. QB - 1 stage the links, threads 0 .. 2 QB - 1 hand their sums over");
-    const int64_t blocks_y = (L + QB - 1) / QB;
-    int64_t blocks_x = (kTopkGrid + blocks_y - 1) / blocks_y;
-    const int64_t need_x = (N + kTopkRows - 1) / kTopkRows;
-    if (blocks_x > need_x) blocks_x = need_x;
-    hipLaunchKernelGGL((rank_score_scan_kernel<H, CMPL>), dim3((unsigned)blocks_x, (unsigned)blocks_y), dim3(256), 0, stream, links, thr, L, N,
-                       tabs, P, M, cards, cards_stride, prm, flags, degrees, head, reinterpret_cast<unsigned long long *>(counts), err);
-}
-
-template <int H>
-void dispatch_rank_score_scan(const int64_t *links, const float *thr, int L, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                              int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
-                              int64_t *counts, int32_t *err, hipStream_t stream)
-{
-#define SS_RANK_HEAD(CMPL) \
-    launch_rank_score_scan<H, CMPL>(links, thr, L, N, tabs, P, M, cards, cards_stride, prm, flags, degrees, head, counts, err, stream)
-    if (!is_fast_pair_shape(P, M)) SS_RANK_HEAD(0);
-    else if (P == 64) SS_RANK_HEAD(1);
-    else if (P == 128) SS_RANK_HEAD(2);
-    else if (P == 192) SS_RANK_HEAD(3);
-    else SS_RANK_HEAD(4);
-#undef SS_RANK_HEAD
-}
-
 }  // namespace ss
 
 extern "C" int ss_rank_score_scan(const int64_t *links, const float *thr, int32_t L, int64_t N, int32_t h, const uint32_t *const *mh,
@@ -259,23 +217,17 @@ extern "C" int ss_rank_score_scan(const int64_t *links, const float *thr, int32_
                                   void *stream)
 {
     using namespace ss;
-    const int rc = check_pair_query_args(h, true, prm, P);
-    if (rc != SS_OK) return rc;
-    if (L < 0 || N <= 0 || N >= ((int64_t)1 << 32)) return SS_ERR_INVALID_ARG;  // (a workgroup's sums are 32-bit words)
-    if (L == 0) return SS_OK;
-    if (!links || !thr || !mh || !hll || !cards || !counts || cards_stride < h) return SS_ERR_INVALID_ARG;
-    HeadArgs args;
-    if (!make_head_args(head, h, degrees, args)) return SS_ERR_INVALID_ARG;
+    HeadArgs args;  // (N_end: a workgroup's sums are 32-bit words)
+    const int rc = check_head_scan_args(L, N, (int64_t)1 << 32, links && thr && counts, h, mh, hll, P, cards, cards_stride, prm, degrees, head, args);
+    if (rc != SS_OK || L == 0) return rc;
     HopTables tabs;
-    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
-    if (((int64_t)L + 7) / 8 > 65535) return SS_ERR_INVALID_ARG;  // (grid.y, at the smallest block of links)
+    if (!fill_head_scan_tables(mh, hll, h, L, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
-    hipStream_t s = (hipStream_t)stream;
-    switch (h) {
-        case 1: dispatch_rank_score_scan<1>(links, thr, (int)L, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, counts, err_flag, s); break;
-        case 2: dispatch_rank_score_scan<2>(links, thr, (int)L, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, counts, err_flag, s); break;
-        default: dispatch_rank_score_scan<3>(links, thr, (int)L, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, counts, err_flag, s); break;
-    }
+    dispatch_head_scan(h, P, M, [&](auto H, auto CMPL) {
+        hipLaunchKernelGGL((rank_score_scan_kernel<H(), CMPL()>), head_scan_grid(L, rank_queries(H(), CMPL()), N), dim3(256), 0,
+                           (hipStream_t)stream, links, thr, (int)L, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args,
+                           reinterpret_cast<unsigned long long *>(counts), err_flag);
+    }, std::make_integer_sequence<int, 5 * SS_MAX_HOPS>{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

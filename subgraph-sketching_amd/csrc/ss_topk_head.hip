@@ -18,8 +18,10 @@
 //
 // Sources per workgroup (kernel parameter SB, topk_head_sources()): as many of {32, 16, 8} as leave TWO workgroups per CU
 // (2 x 80 KiB of the 160 KiB LDS) next to the estimator and head tables -- a source costs 256 * CMPL + 576 bytes per hop.
+// The budget behind it, the launch geometry, the (h, CMPL) dispatch and the shared entry checks: ss_head_scan.hpp.  The kernel body is
+// written out here and in ss_rank.hip: one source for both was measured and dropped (DESIGN_EXPERIMENTS 3.13).
 #include "ss_feature_algebra.hpp"
-#include "ss_head.hpp"
+#include "ss_head_scan.hpp"
 #include "ss_pair_math.hpp"
 #include "ss_topk_key.hpp"
 
@@ -27,21 +29,8 @@ extern "C" size_t ss_topk_workspace_bytes(int64_t N, int32_t S);
 
 namespace ss {
 
-constexpr int kTopkHeadLds = 80 * 1024;  // LDS a workgroup may take: two per CU
-
-// bytes of LDS per staged source: its id, cards, degree and, on the fast shapes, h rows of MinHash chunks and HLL digests
-constexpr int topk_head_source_bytes(int H, int CMPL)
-{
-    return 8 + 4 * H + 4 + (CMPL > 0 ? H * (CMPL * kRow * 16 + kRow * (16 + 16 + 4)) : 0);
-}
-
-constexpr int topk_head_sources(int H, int CMPL)
-{
-    const int fixed = (int)sizeof(EstimatorLds) + (int)sizeof(HeadLds) + 64;  // (64: alignment between the arrays)
-    for (int sb = 32; sb > 8; sb >>= 1)
-        if (fixed + sb * topk_head_source_bytes(H, CMPL) <= kTopkHeadLds) return sb;
-    return 8;
-}
+// sources per workgroup: a source stages nothing of its own next to the entry of ss_head_scan.hpp
+constexpr int topk_head_sources(int H, int CMPL) { return head_scan_entries(H, CMPL, 0); }
 
 // CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape (the sources' rows are read from global memory)
 template <int H, int CMPL>
@@ -186,36 +175,6 @@ __global__ __launch_bounds__(256) void topk_score_scan_kernel(const int64_t *__r
     }
 }
 
-template <int H, int CMPL>
-void launch_topk_score_scan(const int64_t *sources, int S, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                            int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
-                            int64_t *keys, int32_t *err, hipStream_t stream)
-{
-    constexpr int SB = topk_head_sources(H, CMPL);
-    static_assert(SB >= 8 && SB <= 32, "threads 0 .. SB - 1 stage the source ids");
-    const int64_t blocks_y = (S + SB - 1) / SB;
-    int64_t blocks_x = (kTopkGrid + blocks_y - 1) / blocks_y;
-    const int64_t need_x = (N + kTopkRows - 1) / kTopkRows;
-    if (blocks_x > need_x) blocks_x = need_x;
-    hipLaunchKernelGGL((topk_score_scan_kernel<H, CMPL>), dim3((unsigned)blocks_x, (unsigned)blocks_y), dim3(256), 0, stream, sources, S, N, tabs,
-                       P, M, cards, cards_stride, prm, flags, degrees, head, keys, err);
-}
-
-template <int H>
-void dispatch_topk_score_scan(const int64_t *sources, int S, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                              int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, const float *degrees, const HeadArgs &head,
-                              int64_t *keys, int32_t *err, hipStream_t stream)
-{
-#define SS_TOPK_HEAD(CMPL) \
-    launch_topk_score_scan<H, CMPL>(sources, S, N, tabs, P, M, cards, cards_stride, prm, flags, degrees, head, keys, err, stream)
-    if (!is_fast_pair_shape(P, M)) SS_TOPK_HEAD(0);
-    else if (P == 64) SS_TOPK_HEAD(1);
-    else if (P == 128) SS_TOPK_HEAD(2);
-    else if (P == 192) SS_TOPK_HEAD(3);
-    else SS_TOPK_HEAD(4);
-#undef SS_TOPK_HEAD
-}
-
 }  // namespace ss
 
 extern "C" int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, int32_t h, const uint32_t *const *mh, const uint8_t *const *hll,
@@ -224,24 +183,17 @@ extern "C" int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, 
                                   void *stream)
 {
     using namespace ss;
-    const int rc = check_pair_query_args(h, true, prm, P);
-    if (rc != SS_OK) return rc;
-    if (S < 0 || N <= 0 || N >= ((int64_t)1 << 32) - 1) return SS_ERR_INVALID_ARG;  // (the key's low word holds 0xFFFFFFFF - v)
-    if (S == 0) return SS_OK;
-    if (!sources || !mh || !hll || !cards || !keys || cards_stride < h) return SS_ERR_INVALID_ARG;
-    HeadArgs args;
-    if (!make_head_args(head, h, degrees, args)) return SS_ERR_INVALID_ARG;
+    HeadArgs args;  // (N_end: the key's low word holds 0xFFFFFFFF - v)
+    const int rc = check_head_scan_args(S, N, ((int64_t)1 << 32) - 1, sources && keys, h, mh, hll, P, cards, cards_stride, prm, degrees, head, args);
+    if (rc != SS_OK || S == 0) return rc;
     if (keys_bytes < ss_topk_workspace_bytes(N, S)) return SS_ERR_WORKSPACE;
     HopTables tabs;
-    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
-    if (((int64_t)S + 7) / 8 > 65535) return SS_ERR_INVALID_ARG;  // (grid.y, at the smallest block of sources)
+    if (!fill_head_scan_tables(mh, hll, h, S, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
-    hipStream_t s = (hipStream_t)stream;
-    switch (h) {
-        case 1: dispatch_topk_score_scan<1>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
-        case 2: dispatch_topk_score_scan<2>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
-        default: dispatch_topk_score_scan<3>(sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag, s); break;
-    }
+    dispatch_head_scan(h, P, M, [&](auto H, auto CMPL) {
+        hipLaunchKernelGGL((topk_score_scan_kernel<H(), CMPL()>), head_scan_grid(S, topk_head_sources(H(), CMPL()), N), dim3(256), 0,
+                           (hipStream_t)stream, sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag);
+    }, std::make_integer_sequence<int, 5 * SS_MAX_HOPS>{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

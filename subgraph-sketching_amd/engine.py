@@ -50,6 +50,21 @@ def _table_shape(hash_table, hop):
         raise ValueError(f'hop {hop} MinHash table must be 2-D, got {tuple(t.shape)}')
     return int(t.shape[0]), int(t.shape[1])
 
+
+def _table_ptrs(mh, hll):
+    """the two pointer arrays (one entry per hop) the link entry points take for packed MinHash / HLL tables"""
+    return tuple((c_void_p * len(ts))(*[t.data_ptr() for t in ts]) for ts in (mh, hll))
+
+
+def _exclude_csr(ex, N, device, strict, err):
+    """(CSR with row u = {v : u -> v} of an exclude edge_index or None, negative ids wrapped; the error flag of the launches behind it)"""
+    csr = None
+    if ex is not None:
+        ex = ex.to(device=device, dtype=torch.int64)
+        ex = torch.where(ex < 0, ex + N, ex)  # (ids below -N stay negative: out of range)
+        csr = build_csr(ex.flip(0), N, device, check=strict, err_flag=None if strict else err)
+    return csr, (_error_flag(device) if strict else err)
+
 class ElphHashes(object):
     """class to store hashes and retrieve subgraph features (mirror of reference hashing.py:48-323)"""
     HUB_HINT_SHAPES = 256  # graph shapes that get a hub hint word (one pinned int32 each, kept for the engine's lifetime)
@@ -458,6 +473,20 @@ class ElphHashes(object):
         if degrees is not None and not head.normalised:
             raise ValueError(f'degrees given but head.dim = {head.dim} has no columns for the normalised copy (normalised=False)')
 
+    def _flags(self, floor_sf=None):
+        """the SS_FLAG_* word of a query; floor_sf: instead of self.floor_sf (DeviceFeatureStore records HashDataset's post-hoc floor)"""
+        floor = self.floor_sf if floor_sf is None else floor_sf
+        return (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if floor else 0)
+
+    def _send_home(self, home, *results):
+        """device results on the caller's device.  A copy has waited for the launches: a deferred report is final behind it"""
+        if all(r.device == home for r in results):
+            return results
+        results = tuple(r.to(home) for r in results)
+        if self.strict_bounds == 'deferred':
+            self._deferred.raise_if_set()
+        return results
+
     def _query_inputs(self, links, hash_table, cards, degrees, floor_sf, out, out_width, what):
         """what every launch of the pair kernel takes, resolved once per call (the feature query and score_links share it);
         out_width: columns per link of a caller-supplied `out` (None: one float per link, a 1-D tensor)"""
@@ -473,10 +502,8 @@ class ElphHashes(object):
         shape = (B,) if out_width is None else (B, out_width)
         if out is not None and (out.device != device or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
             raise ValueError(f'out must be a contiguous float32 {list(shape)} tensor on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}')
-        mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
-        hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
-        floor = self.floor_sf if floor_sf is None else floor_sf  # DeviceFeatureStore records HashDataset's post-hoc floor
-        flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if floor else 0)
+        mh_ptrs, hll_ptrs = _table_ptrs(mh, hll)
+        flags = self._flags(floor_sf)
         strict, err = self._bounds(device, f'{what}({B} links, num_nodes={N})')
         if strict:
             err = _error_flag(device)  # (non-strict launches never touch the shared flag)
@@ -638,12 +665,7 @@ class ElphHashes(object):
         else:
             scores = torch.cat([self._score_kernel(links[s:s + batch_size], hash_table, cards, head, degrees=degrees)
                                 for s in range(0, n, batch_size)], dim=0)
-        if scores.device == links.device or out is not None:
-            return scores
-        res = scores.to(links.device)
-        if self.strict_bounds == 'deferred':  # the copy back has waited for the launches: the report is final (as get_subgraph_features)
-            self._deferred.raise_if_set()
-        return res
+        return scores if out is not None else self._send_home(links.device, scores)[0]
 
     def _get_intersections(self, edge_list, hash_table):
         """set-intersection estimates jaccard * union for every (k1, k2) (reference :167-189).
@@ -717,13 +739,7 @@ class ElphHashes(object):
             extra = (self._device_cards(cards, N, device), self._device_degrees(degrees, N, device))
         lk = src.to(device=device, dtype=torch.int64).contiguous()
         strict, err = self._bounds(device, f'{what}({S} sources, num_nodes={N})')
-        csr = None
-        if ex is not None:
-            ex = ex.to(device=device, dtype=torch.int64)
-            ex = torch.where(ex < 0, ex + N, ex)  # (ids below -N stay negative: out of range)
-            csr = build_csr(ex.flip(0), N, device, check=strict, err_flag=None if strict else err)  # row u = {v : u -> v}
-        if strict:
-            err = _error_flag(device)
+        csr, err = _exclude_csr(ex, N, device, strict, err)
         ids = torch.empty((S, k), dtype=torch.int64, device=device)
         scores = torch.empty((S, k), dtype=torch.float32, device=device)
         blk = max(1, min(S, _TOPK_KEY_BYTES // (8 * N)))
@@ -745,12 +761,7 @@ class ElphHashes(object):
                 ids[b0:b0 + nb], scores[b0:b0 + nb] = _decode_topk_keys(top)
         if strict and S and _take_error(device):
             raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
-        if home == device:
-            return ids, scores
-        ids, scores = ids.to(home), scores.to(home)
-        if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
-            self._deferred.raise_if_set()
-        return ids, scores
+        return self._send_home(home, ids, scores)
 
     def topk_links(self, sources, hash_table, cards, k, head, degrees=None, exclude=None):
         """the k link partners a trained model's structure head ranks highest for every source: topk_candidates' one-vs-all scan with
@@ -773,12 +784,11 @@ class ElphHashes(object):
             raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
         src, ex, N, P = self._topk_arguments(sources, hash_table, k, exclude)
         h = self.max_hops
-        flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if self.floor_sf else 0)
+        flags = self._flags()
 
         def scan(lib, sb, nb, N, P, mh, hll, params, keys, nbytes, err, stream, cd, dg):
             hd = head._device(keys.device)
-            mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
-            hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
+            mh_ptrs, hll_ptrs = _table_ptrs(mh, hll)
             _native.check(lib.ss_topk_score_scan(sb, nb, N, h, mh_ptrs, hll_ptrs, P, _ptr(cd), cd.stride(0), byref(params.struct), flags,
                                                  _ptr(dg), byref(hd.struct), _ptr(keys), nbytes, _ptr(err), stream), 'ss_topk_score_scan')
 
@@ -828,18 +838,11 @@ class ElphHashes(object):
         params = self._params(device)
         cd, dg, hd = self._device_cards(cards, N, device), self._device_degrees(degrees, N, device), head._device(device)
         h = self.max_hops
-        mh_ptrs = (c_void_p * h)(*[t.data_ptr() for t in mh])
-        hll_ptrs = (c_void_p * h)(*[t.data_ptr() for t in hll])
-        flags = (_native.SS_FLAG_USE_ZERO_ONE if self.use_zero_one else 0) | (_native.SS_FLAG_FLOOR_SF if self.floor_sf else 0)
+        mh_ptrs, hll_ptrs = _table_ptrs(mh, hll)
+        flags = self._flags()
         lk = lk.to(device=device, dtype=torch.int64).contiguous()
         strict, err = self._bounds(device, f'rank_links({L} links, num_nodes={N})')
-        csr = None
-        if ex is not None:
-            ex = ex.to(device=device, dtype=torch.int64)
-            ex = torch.where(ex < 0, ex + N, ex)  # (ids below -N stay negative: out of range)
-            csr = build_csr(ex.flip(0), N, device, check=strict, err_flag=None if strict else err)  # row u = {v : u -> v}
-        if strict:
-            err = _error_flag(device)
+        csr, err = _exclude_csr(ex, N, device, strict, err)
         lib = _native.lib()
 
         def scores(pairs, out):
@@ -867,13 +870,7 @@ class ElphHashes(object):
         counts.masked_fill_(bad.unsqueeze(1), -1)
         if strict and _take_error(device):
             raise IndexError(f'links refer to nodes outside [-{N}, {N})')
-        greater, equal = counts[:, 0].contiguous(), counts[:, 1].contiguous()
-        if home == device:
-            return greater, equal
-        greater, equal = greater.to(home), equal.to(home)
-        if self.strict_bounds == 'deferred':  # (the copies have waited for the launches: the report is final)
-            self._deferred.raise_if_set()
-        return greater, equal
+        return self._send_home(home, counts[:, 0].contiguous(), counts[:, 1].contiguous())
 
     @staticmethod
     def _rank_exclusion(counts, links, bad, thr, csr, N, scores):

@@ -259,7 +259,7 @@ def test_sketch_shapes(ssa, dev, P, p):
             _assert_same(eh.rank_links(_t(links, dev), table, cards, head, degrees=dg, exclude=_t(excl, dev)), _want(rows, links, N, excl))
 
 
-@pytest.mark.parametrize('h', [1, 3])
+@pytest.mark.parametrize('h', [1, 2, 3])
 @pytest.mark.parametrize('P', [64, 192, 256])
 def test_fast_shapes_at_the_other_hop_counts(ssa, dev, h, P):
     """every (h, P) instantiation stages another number of links per workgroup: 45 links cross a block boundary in each"""

@@ -224,7 +224,7 @@ def test_sketch_shapes(ssa, dev, P, p):
             _assert_same(got, _rank(sc, sources, 10, N, excl))
 
 
-@pytest.mark.parametrize('h', [1, 3])
+@pytest.mark.parametrize('h', [1, 2, 3])
 @pytest.mark.parametrize('P', [64, 192, 256])
 def test_fast_shapes_at_the_other_hop_counts(ssa, dev, h, P):
     """every (h, P) instantiation stages another number of sources per workgroup: 40 sources cross a block boundary in each"""
