@@ -391,6 +391,28 @@ int ss_rank_score_scan(const int64_t *links, const float *thr, int32_t L, int64_
                        uint32_t flags, const float *degrees, const ss_structure_head *head, int64_t *counts, int32_t *err_flag,
                        void *stream);
 
+/* Locality-sensitive hashing by banding over ONE hop's packed MinHash table mh [N, P]: sub-linear link candidates for the workloads
+ * that ask "who are the best partners of u" for many sources (hard-negative mining -- the reference's sample_hard_negatives,
+ * src/data.py:262-304 --, candidate generation, a kNN graph), where the one-vs-all scans above score all N nodes per source.
+ * Band j of node v is mh[v][j * rows .. (j + 1) * rows), j < bands, rows * bands <= P; the bucket of (j, v) is the set of nodes whose
+ * band-j slice equals v's value for value.  N < 2^31, P a multiple of 4 in [4, 2048], 1 <= key_bits <= 64.
+ *   ss_lsh_band_keys  keys [bands, N] int64: keys[j][v] = a 64-bit mix of band j of v, its low key_bits bits kept (64: all; fewer
+ *                     only makes false matches, for tests).  The caller sorts every band (signed int64 order) and keeps the sorted
+ *                     keys and the permutation perm [bands, N] int32 (perm[j][i] = the node at place i of band j).
+ *   ss_lsh_count      counts [S * bands] int32: counts[s * bands + j] = the nodes v != u that share band j with u = sources[s]
+ *                     (device int64 [S], torch-style negative ids wrapped; an id outside [-N, N) sets err_flag, nullable, and counts
+ *                     nothing): the equal range of u's key in the sorted keys of band j by binary search; a range longer than
+ *                     max_bucket is dropped whole; else every member's `rows` values are compared with u's own, so the result does
+ *                     not depend on the mix or on key_bits.
+ *   ss_lsh_fill       the same walk with the same arguments, writing the entries s * N + v (int64) of item s * bands + j from
+ *                     out[offsets[s * bands + j]] on, offsets = the exclusive scan of ss_lsh_count's counts (device int64), in no
+ *                     particular order inside an item; a node sharing several bands with u is listed once per band. */
+int ss_lsh_band_keys(const uint32_t *mh, int64_t N, int32_t P, int32_t rows, int32_t bands, int32_t key_bits, int64_t *keys, void *stream);
+int ss_lsh_count(const int64_t *sources, int32_t S, int64_t N, const uint32_t *mh, int32_t P, int32_t rows, int32_t bands, int32_t key_bits,
+                 const int64_t *keys, const int32_t *perm, int32_t max_bucket, int32_t *counts, int32_t *err_flag, void *stream);
+int ss_lsh_fill(const int64_t *sources, int32_t S, int64_t N, const uint32_t *mh, int32_t P, int32_t rows, int32_t bands, int32_t key_bits,
+                const int64_t *keys, const int32_t *perm, int32_t max_bucket, const int64_t *offsets, int64_t *out, void *stream);
+
 /* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
  * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
  * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,

@@ -7,7 +7,7 @@ from .hashing import (LABEL_LOOKUP, ElphHashes, HllPropagation, HopSketch, Minha
                       build_csr, load_sketches, pack_minhash, save_sketches, unpack_minhash)
 from .feature_store import DeviceFeatureStore
 from .head import StructureHead
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh
 
 __all__ = ['LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
-           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline']
+           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh']

@@ -111,6 +111,11 @@ SIGNATURES = {
     'ss_rank_score_scan': (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, POINTER(c_void_p), POINTER(c_void_p), c_int32, c_void_p,
                                      c_int64, POINTER(HllParams), c_uint32, c_void_p, POINTER(StructureHeadStruct), c_void_p, c_void_p,
                                      c_void_p]),
+    'ss_lsh_band_keys': (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'ss_lsh_count': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                               c_void_p, c_void_p, c_void_p]),
+    'ss_lsh_fill': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                              c_void_p, c_void_p, c_void_p]),
     'ss_exact_workspace_bytes': (c_size_t, [c_int64]),
     'ss_exact_slot_bytes': (c_size_t, [c_int64]),
     'ss_exact_pairs': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_int32, c_void_p, c_void_p,

@@ -42,6 +42,29 @@ def _decode_topk_keys(keys):
     return (0xFFFFFFFF - lo).masked_fill(pad, -1), scores.masked_fill(pad, float('-inf'))
 
 
+def _encode_topk_keys(scores, ids):
+    """the key ss_topk_key.hpp forms of (score float32, id int64), in torch (topk_links_lsh ranks scores of ss_pair_scores by it):
+    signed int64 order == (score descending, id ascending), -0.0 folded into +0.0; _decode_topk_keys is its inverse"""
+    bits = scores.view(torch.int32).to(torch.int64)
+    bits = bits.masked_fill(bits == -(1 << 31), 0)
+    hi = torch.where(bits >= 0, bits, -(1 << 31) - 1 - bits)
+    return (hi << 32) | (0xFFFFFFFF - ids)
+
+
+def _csr_row_keys(csr, rows, N):
+    """sorted unique keys i * N + v over every v in row rows[i] of a CSR (rows: int64 ids in [0, N), duplicates allowed; the CSR's
+    rows hold duplicates, unordered), or None when those rows are empty.  One host read (the size of the gather)."""
+    deg = csr.rowptr[rows + 1] - csr.rowptr[rows]
+    ends = torch.cumsum(deg, 0)
+    total = int(ends[-1].item()) if rows.numel() else 0
+    if total == 0:
+        return None
+    e = torch.arange(total, dtype=torch.int64, device=rows.device)
+    s = torch.searchsorted(ends, e, right=True)
+    v = csr.col[csr.rowptr[rows[s]] + (e - (ends[s] - deg[s]))].to(torch.int64)
+    return torch.unique(s * N + v)
+
+
 def _table_shape(hash_table, hop):
     """(N, P) of a hop's MinHash table without touching a device"""
     entry = hash_table[hop]
@@ -844,15 +867,7 @@ class ElphHashes(object):
         strict, err = self._bounds(device, f'rank_links({L} links, num_nodes={N})')
         csr, err = _exclude_csr(ex, N, device, strict, err)
         lib = _native.lib()
-
-        def scores(pairs, out):
-            """the ONE form of s(u, v): the launch behind score_links, for the thresholds and for the excluded pairs"""
-            with _Span('pair_scores', device):
-                _native.check(lib.ss_pair_scores(_ptr(pairs), None, pairs.size(0), N, h, mh_ptrs, P, hll_ptrs, _ptr(cd), cd.stride(0),
-                                                 byref(params.struct), flags, _ptr(dg), byref(hd.struct), _ptr(out), _ptr(err),
-                                                 _stream(device)), 'ss_pair_scores')
-            return out
-
+        scores = self._pair_scores(device, N, P, mh_ptrs, hll_ptrs, cd, params, dg, hd, err)
         thr = scores(lk, torch.empty((L,), dtype=torch.float32, device=device))
         counts = torch.zeros((L, 2), dtype=torch.int64, device=device)
         for s0 in range(0, L, _RANK_LAUNCH_LINKS):
@@ -872,6 +887,20 @@ class ElphHashes(object):
             raise IndexError(f'links refer to nodes outside [-{N}, {N})')
         return self._send_home(home, counts[:, 0].contiguous(), counts[:, 1].contiguous())
 
+    def _pair_scores(self, device, N, P, mh_ptrs, hll_ptrs, cd, params, dg, hd, err):
+        """the ONE form of s(u, v): the launch behind score_links as scores(pairs int64 [n, 2], out float32 [n]) -> out, for
+        rank_links' thresholds and excluded pairs and for topk_links_lsh's candidates"""
+        lib, h, flags = _native.lib(), self.max_hops, self._flags()
+
+        def scores(pairs, out):
+            with _Span('pair_scores', device):
+                _native.check(lib.ss_pair_scores(_ptr(pairs), None, pairs.size(0), N, h, mh_ptrs, P, hll_ptrs, _ptr(cd), cd.stride(0),
+                                                 byref(params.struct), flags, _ptr(dg), byref(hd.struct), _ptr(out), _ptr(err),
+                                                 _stream(device)), 'ss_pair_scores')
+            return out
+
+        return scores
+
     @staticmethod
     def _rank_exclusion(counts, links, bad, thr, csr, N, scores):
         """the scan has counted every v != u, t; the excluded partners of each link's source are taken back out of counts [L, 2]:
@@ -881,15 +910,9 @@ class ElphHashes(object):
         u = links[:, 0].masked_fill(bad, 0)
         # the rows of the DISTINCT sources, each partner once: sorted keys source * N + v (the CSR's rows hold duplicates, unordered)
         us, of_link = torch.unique(u, return_inverse=True)
-        deg = csr.rowptr[us + 1] - csr.rowptr[us]
-        ends = torch.cumsum(deg, 0)
-        total = int(ends[-1].item())
-        if total == 0:
+        keys = _csr_row_keys(csr, us, N)
+        if keys is None:
             return
-        e = torch.arange(total, dtype=torch.int64, device=device)
-        s = torch.searchsorted(ends, e, right=True)
-        v = csr.col[csr.rowptr[us[s]] + (e - (ends[s] - deg[s]))].to(torch.int64)
-        keys = torch.unique(s * N + v)
         row = torch.searchsorted(keys, torch.arange(us.numel() + 1, dtype=torch.int64, device=device) * N)
         # per link the extent of its source's row in `keys`; the pairs (link, partner) are walked flat, _RANK_EXCLUDE_PAIRS at a time
         n_q = (row[of_link + 1] - row[of_link]).masked_fill(bad, 0)
@@ -903,6 +926,48 @@ class ElphHashes(object):
             candidate = (v != links[q, 0]) & (v != links[q, 1])
             hit = torch.stack([(sc > thr[q]) & candidate, (sc == thr[q]) & candidate], dim=1).to(torch.int64)
             counts.index_add_(0, q, -hit)
+
+    def build_lsh_index(self, hash_table, hop=1, rows=4, bands=None, max_bucket=1024, _key_bits=64):
+        """an LSH index by banding over the stored hop-`hop` MinHash rows (lsh.py, csrc/ss_lsh.hip): what lsh_candidates
+        and topk_links_lsh look partners up in instead of scanning all N nodes per source, for the workloads that ask for many sources
+        (hard-negative mining by the model's own score, candidate generation, a kNN graph).  Band j of node v is the slice
+        M_hop[v][j * rows : (j + 1) * rows] of its row (`HopSketch.mh_u32`); the bucket of (j, v) is the set of nodes whose band-j slice
+        equals v's, value for value.  Two nodes whose hop-`hop` neighbourhoods have Jaccard J share a band with probability about
+        J^rows and one of `bands` bands with about 1 - (1 - J^rows)^bands.
+        @param hash_table: anything get_subgraph_features accepts;  @param hop: 1 <= hop <= max_hash_hops
+        @param rows: MinHash values per band, >= 1;  @param bands: rows * bands <= P, default P // rows
+        @param max_bucket: a bucket with more members is skipped: it yields no candidates for any of its members in that band (rows
+               shared by many nodes -- nodes without edges and self loop, an empty graph -- would make the query quadratic)
+        @return: an `LshIndex` resident on the compute device (hop, rows, bands, num_nodes, num_perm, max_bucket, skipped_buckets int64
+                 [bands], nbytes).  It keeps a view of the hop's packed table to verify slices against: after update_hash_tables (or any
+                 other change of the table) it is STALE and must be rebuilt.
+        Out of scope: several hops in one index (build two, merge the candidates), saving / loading, dist sharding, incremental update."""
+        from . import lsh
+        return lsh.build_lsh_index(self, hash_table, hop, rows, bands, max_bucket, _key_bits)
+
+    def lsh_candidates(self, sources, index, exclude=None, min_bands=1):
+        """the nodes that share a bucket of `index` with each source: v is a candidate of u iff v != u, (u -> v) is not in `exclude`
+        and u, v share a non-skipped bucket in at least `min_bands` bands (exact slice equality: the index's sort key never decides).
+        @param sources: int [S] node ids as topk_links takes them (torch-style negative ids wrapped, duplicates allowed, CPU or device,
+               S = 0 fine; ids outside [-N, N) are reported as topk_links reports them and have no candidates)
+        @param exclude: optional int [2, E] edge_index read as a set of directed pairs u -> v (duplicates, self loops, negative ids fine)
+        @return: (rowptr int64 [S + 1], ids int64 [T], bands int32 [T]) on sources.device: row s is ids[rowptr[s] : rowptr[s + 1]],
+                 ascending and unique, bands = in how many bands the pair shares a bucket.  A row depends on its own source only.
+        The masked query and dist sharding are out of scope."""
+        from . import lsh
+        return lsh.lsh_candidates(self, sources, index, exclude, min_bands)
+
+    def topk_links_lsh(self, sources, hash_table, cards, k, head, index, degrees=None, exclude=None, min_bands=1):
+        """topk_links restricted to the candidates lsh_candidates(sources, index, exclude, min_bands) lists: the k of them the structure
+        head ranks highest per source, scored pair by pair through the launch behind score_links -- no scan of all N nodes, no feature
+        row and no [S, N] array.  Approximate by design: a partner that shares no bucket with u is never seen (tools/probe_lsh.py
+        measures the recall against topk_links).
+        @param sources, hash_table, cards, k, head, degrees, exclude: as topk_links takes them;  @param index: build_lsh_index(hash_table, ...)
+        @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows with
+                 fewer than k candidates end in id -1 / score -inf.  Scores are bit-identical to score_links([[u, v]], ...) (-0.0 comes
+                 back as +0.0).  A row depends on its own source only.  Ids outside [-N, N) are reported as topk_links reports them."""
+        from . import lsh
+        return lsh.topk_links_lsh(self, sources, hash_table, cards, k, head, index, degrees, exclude, min_bands)
 
     def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, mask_target=False):
         """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph

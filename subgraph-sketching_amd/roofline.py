@@ -171,6 +171,13 @@ def rank_links_bytes(N, L, h, P, M):
     return blocks_y * N * h * R + blocks_x * L * (h * R + 20) + 16 * L
 
 
+def lsh_band_keys_bytes(N, P, rows, bands):
+    """algorithmic bytes of one ss_lsh_band_keys launch (ElphHashes.build_lsh_index): the hop's MinHash table read once,
+    N P 4 bytes (only the 16-byte chunks that hold the rows * bands values in use), one int64 key per node and band written.  The
+    sort of the bands that follows is torch's and not in it."""
+    return N * 16 * -(-rows * bands // 4) + 8 * N * bands
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
