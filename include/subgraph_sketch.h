@@ -413,6 +413,34 @@ int ss_lsh_count(const int64_t *sources, int32_t S, int64_t N, const uint32_t *m
 int ss_lsh_fill(const int64_t *sources, int32_t S, int64_t N, const uint32_t *mh, int32_t P, int32_t rows, int32_t bands, int32_t key_bits,
                 const int64_t *keys, const int32_t *perm, int32_t max_bucket, const int64_t *offsets, int64_t *out, void *stream);
 
+/* Negative links drawn on the device, O(1) per negative, fresh per seed: what the reference takes once, on the CPU, from PyG's
+ * negative_sampling (src/data.py:199-217) and get_same_source_negs (src/utils.py:88-99, unfiltered there), and what its unfinished
+ * sample_hard_negatives (src/data.py:262-304: non-edges with a common neighbour) wanted.
+ * rowptr [N + 1] int64 / col int32: row u = {v : u -> v}, every row SORTED ascending (ss_csr_sort_rows), duplicates kept; ex_rowptr /
+ * ex_col: a second such CSR of pairs that must not come back either (both null: none).  N < 2^31.
+ * Slot t < n_slots of the call is slot q = first_slot + t of the whole job and belongs to positive q / num_neg; sources (device int64,
+ * element stride source_stride, torch-style negative ids wrapped) points at the source of the positive of slot first_slot, null for
+ * any-source sampling (SS_NEG_UNIFORM only).  Attempt a = 0 .. max_tries - 1 (max_tries in [1, SS_NEG_MAX_TRIES]) of slot q draws
+ *     r_c = hash(hash(seed ^ hash(q + 1)) + 0x9E3779B97F4A7C15 * (2 a + c + 1)),  c = 0, 1   (hash: the splitmix64 finaliser, mod 2^64)
+ * and proposes, with hi(r n) the high 64 bits of r * n:
+ *     SS_NEG_UNIFORM      u = the source, or hi(r_0 N) without sources;  v = hi(r_1 N)
+ *     SS_NEG_SAME_SOURCE  u = the source;                                v = hi(r_1 N)
+ *     SS_NEG_WEDGE        u = the source;  w = row_u[hi(r_0 deg u)];  v = row_w[hi(r_1 deg w)]   (deg u == 0: no attempt is made;
+ *                         deg w == 0: the attempt is rejected) -- v is proposed with probability sum_w 1 / (deg u * deg w) over the
+ *                         paths u -> w -> v, multiplicities counted: proportional to the resource-allocation score of (u, v)
+ * The first attempt with v != u and u -> v in neither CSR gives out[t] = (u, v); none: (u, -1) (any-source: the u of the last attempt),
+ * and *unsampled (device int32, nullable, NOT cleared by the call) counts the slot -- one atomic per wavefront.  A source outside
+ * [-N, N) sets err_flag (nullable), leaves (the id as given, -1) and is counted too.  out: device int64 [n_slots, 2], 16-byte aligned.
+ * A slot depends on (seed, q) and the two CSRs only: a job split into calls by first_slot reproduces the unsplit one; different slots
+ * may return the same pair.  Argument errors (SS_ERR_INVALID_ARG) are detected before any launch; n_slots == 0: SS_OK, no launch. */
+#define SS_NEG_UNIFORM 0
+#define SS_NEG_SAME_SOURCE 1
+#define SS_NEG_WEDGE 2
+#define SS_NEG_MAX_TRIES 64
+int ss_sample_negatives(const int64_t *rowptr, const int32_t *col, const int64_t *ex_rowptr, const int32_t *ex_col, int64_t N,
+                        const int64_t *sources, int64_t source_stride, int64_t n_slots, int32_t num_neg, int32_t mode, uint64_t seed,
+                        int32_t max_tries, int64_t first_slot, int64_t *out, int32_t *unsampled, int32_t *err_flag, void *stream);
+
 /* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
  * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
  * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,

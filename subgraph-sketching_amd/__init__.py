@@ -7,7 +7,8 @@ from .hashing import (LABEL_LOOKUP, ElphHashes, HllPropagation, HopSketch, Minha
                       build_csr, load_sketches, pack_minhash, save_sketches, unpack_minhash)
 from .feature_store import DeviceFeatureStore
 from .head import StructureHead
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh
+from .negatives import NegativeSampler, sample_negatives
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives
 
 __all__ = ['LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
-           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh']
+           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives']

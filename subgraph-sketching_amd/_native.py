@@ -5,7 +5,7 @@ object has not been built (run `python __graft_entry__.py` or `subgraph-sketchin
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SS_LIB: measurement hook -- tools/ablate_fused.sh loads deliberately incomplete builds of the library to time what is left)
@@ -51,6 +51,8 @@ PPR_SEGMENT, PPR_MAX_COLUMNS = 256, 4096  # SS_PPR_SEGMENT / SS_PPR_MAX_COLUMNS 
 ABI_VERSION = 129  # ss_version() of the library this module's struct mirrors and signatures describe
 PROF_MINHASH_HOP, PROF_HLL_HOP, PROF_FIRST_HOP_MH, PROF_FIRST_HOP_HLL, PROF_PAIRS, PROF_CSR, PROF_HUB, PROF_FUSED, PROF_MINHASH_ROWS = range(9)  # SS_PROF_* tags
 MEGA_DESC_WORDS = 8  # SS_MEGA_DESC_WORDS
+NEG_MODES = {'uniform': 0, 'same_source': 1, 'wedge': 2}  # SS_NEG_*
+NEG_MAX_TRIES = 64  # SS_NEG_MAX_TRIES
 MEGA_SLICE, MEGA_SLOT_BYTES, CSR_FINGERPRINT_BYTES, MAX_MIRRORS = 1024, 1280, 8448, 7  # SS_MEGA_SLICE / SS_MEGA_SLOT_BYTES of include/subgraph_sketch.h
 
 
@@ -116,6 +118,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p]),
     'ss_lsh_fill': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                               c_void_p, c_void_p, c_void_p]),
+    'ss_sample_negatives': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_uint64,
+                                      c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ss_exact_workspace_bytes': (c_size_t, [c_int64]),
     'ss_exact_slot_bytes': (c_size_t, [c_int64]),
     'ss_exact_pairs': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_int32, c_void_p, c_void_p,
