@@ -441,6 +441,27 @@ int ss_sample_negatives(const int64_t *rowptr, const int32_t *col, const int64_t
                         const int64_t *sources, int64_t source_stride, int64_t n_slots, int32_t num_neg, int32_t mode, uint64_t seed,
                         int32_t max_tries, int64_t first_slot, int64_t *out, int32_t *unsampled, int32_t *err_flag, void *stream);
 
+/* Exact two-hop link candidates: the rows `sources` of A * A with integer walk counts, over the same sorted CSR (row u = {v : u -> v},
+ * duplicates kept, N < 2^31).  A walk of u is u -> w -> v, w in row u, v in row w, every copy of a repeated edge its own walk;
+ * W(u) = the sum of deg(w) over w in row u.  sources: device int64 [S], torch-style negative ids wrapped, S < 2^31.
+ *   ss_wedge_walks  walks[s] = W(sources[s]) (device int64 [S]); an id outside [-N, N) sets err_flag (nullable) and has 0 walks.
+ *   ss_wedge_fold   the LDS tier: every source with 0 < 2 * walks[s] <= slots (a power of two <= SS_WEDGE_MAX_SLOTS) writes its D
+ *                   distinct endpoints as keys[offsets[s] + i] = s * N + v, counts[..] = the walks that end in v, i < D, in no
+ *                   particular order, and pads the places D .. walks[s] - 1 of its slot with key INT64_MAX / count 0.
+ *   ss_wedge_emit   the large tier: every source with 2 * walks[s] > slots writes the endpoint s * N + v of each of its walks to
+ *                   keys[offsets[s] .. offsets[s] + walks[s]) (w ascending in row u, then v ascending in row w); `slices` in [1, 64]
+ *                   workgroups share a source's row.  Counts are not written: one walk each.
+ * walks: what ss_wedge_walks returned with the sources to leave out set to 0; offsets: its exclusive scan (device int64 [S]); keys
+ * int64 / counts int32 hold sum(walks) entries.  The two launches cover every source with walks > 0 exactly once, and no store leaves
+ * a source's slot.  Argument errors (SS_ERR_INVALID_ARG) are detected before any launch; S == 0: SS_OK, no launch. */
+#define SS_WEDGE_MAX_SLOTS 4096
+int ss_wedge_walks(const int64_t *rowptr, const int32_t *col, int64_t N, const int64_t *sources, int64_t S, int64_t *walks, int32_t *err_flag,
+                   void *stream);
+int ss_wedge_fold(const int64_t *rowptr, const int32_t *col, int64_t N, const int64_t *sources, int64_t S, const int64_t *walks,
+                  const int64_t *offsets, int32_t slots, int64_t *keys, int32_t *counts, void *stream);
+int ss_wedge_emit(const int64_t *rowptr, const int32_t *col, int64_t N, const int64_t *sources, int64_t S, const int64_t *walks,
+                  const int64_t *offsets, int32_t slots, int32_t slices, int64_t *keys, void *stream);
+
 /* Exact subgraph features: what get_subgraph_features (reference hashing.py:258-323) would return if its estimators were exact.
  * The ball B_k(x) of G' -- the graph build_hash_tables propagates over (hashing.py:139-165: the edges of the CSR, flow source ->
  * target, plus a self loop at every x < n_self, the graph's n_self_loops / n_self_loops_dev, i.e. add_self_loops without num_nodes,

@@ -53,6 +53,7 @@ PROF_MINHASH_HOP, PROF_HLL_HOP, PROF_FIRST_HOP_MH, PROF_FIRST_HOP_HLL, PROF_PAIR
 MEGA_DESC_WORDS = 8  # SS_MEGA_DESC_WORDS
 NEG_MODES = {'uniform': 0, 'same_source': 1, 'wedge': 2}  # SS_NEG_*
 NEG_MAX_TRIES = 64  # SS_NEG_MAX_TRIES
+WEDGE_MAX_SLOTS, WEDGE_MAX_SLICES = 4096, 64  # SS_WEDGE_MAX_SLOTS; the slices ss_wedge_emit takes at most
 MEGA_SLICE, MEGA_SLOT_BYTES, CSR_FINGERPRINT_BYTES, MAX_MIRRORS = 1024, 1280, 8448, 7  # SS_MEGA_SLICE / SS_MEGA_SLOT_BYTES of include/subgraph_sketch.h
 
 
@@ -120,6 +121,9 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p]),
     'ss_sample_negatives': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_uint64,
                                       c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_wedge_walks': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'ss_wedge_fold': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    'ss_wedge_emit': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'ss_exact_workspace_bytes': (c_size_t, [c_int64]),
     'ss_exact_slot_bytes': (c_size_t, [c_int64]),
     'ss_exact_pairs': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_int32, c_void_p, c_void_p,

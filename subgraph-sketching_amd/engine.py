@@ -969,6 +969,22 @@ class ElphHashes(object):
         from . import lsh
         return lsh.topk_links_lsh(self, sources, hash_table, cards, k, head, index, degrees, exclude, min_bands)
 
+    def topk_links_wedge(self, sources, hash_table, cards, k, head, graph, degrees=None, exclude=None, min_common=1, max_walks=None,
+                         _lds_slots=None):
+        """topk_links restricted to the EXACT two-hop candidates graph.candidates(sources, exclude, min_common, max_walks) lists -- the
+        nodes that share at least min_common neighbours with the source (wedge.py, csrc/ss_wedge.hip): the k of them the
+        structure head ranks highest per source, scored pair by pair through the launch behind score_links -- no scan of all N nodes,
+        no feature row and no [S, N] array.  Exact on its set: unlike topk_links_lsh nothing depends on a tuning of rows / bands; a
+        partner without a common neighbour is never seen.
+        @param sources, hash_table, cards, k, head, degrees, exclude: as topk_links takes them
+        @param graph: WedgeGraph(num_nodes, edge_index) of the tables' num_nodes;  @param min_common, max_walks: as .candidates
+        @return: (ids int64 [S, k], scores float32 [S, k]) on sources.device, ordered by score descending then id ascending; rows with
+                 fewer than k candidates (a skipped source: none) end in id -1 / score -inf.  Scores are bit-identical to
+                 score_links([[u, v]], ...) (-0.0 comes back as +0.0).  A row depends on its own source only.  Ids outside [-N, N)
+                 are reported as topk_links reports them."""
+        from . import wedge
+        return wedge.topk_links_wedge(self, sources, hash_table, cards, k, head, graph, degrees, exclude, min_common, max_walks, _lds_slots)
+
     def exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=11000000, return_counts=False, mask_target=False):
         """the features get_subgraph_features would return if every estimator were exact: with the k-hop balls B_k of the graph
         build_hash_tables(num_nodes, edge_index) propagates over (its edges, flow source -> target, plus a self loop at every node

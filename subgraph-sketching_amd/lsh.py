@@ -174,6 +174,22 @@ def _row_starts(keys, n, N):
     return torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int64, device=keys.device) * N)
 
 
+def _select_rows(keys, sc, n, N, k):
+    """the k best pairs of each of a block's n sources: keys = the block's sorted unique s * N + v, sc their float32 scores ->
+    (ids int64 [n, k], scores float32 [n, k]) by (score desc, id asc), tails -1 / -inf (topk_links_lsh and topk_links_wedge)"""
+    device = keys.device
+    s = keys // N
+    rank = _encode_topk_keys(sc, keys - s * N)
+    by_key = torch.argsort(rank, descending=True)                  # unique inside a source: (score desc, id asc)
+    order = by_key[torch.sort(s[by_key], stable=True).indices]     # ... grouped by source again
+    s_o = s[order]
+    place = torch.arange(keys.numel(), dtype=torch.int64, device=device) - _row_starts(keys, n, N)[s_o]
+    take = place < k
+    top = torch.full((n, k), TOPK_SENTINEL, dtype=torch.int64, device=device)
+    top[s_o[take], place[take]] = rank[order][take]
+    return _decode_topk_keys(top)
+
+
 def lsh_candidates(eh, sources, index, exclude, min_bands):
     src, ex, min_bands = _arguments(eh, sources, index, exclude, min_bands)
     home, S, N = src.device, src.numel(), index.num_nodes
@@ -217,15 +233,7 @@ def topk_links_lsh(eh, sources, hash_table, cards, k, head, index, degrees, excl
         v = keys - s * N
         sc = score(torch.stack([u[s], v], dim=1).contiguous(), torch.empty((keys.numel(),), dtype=torch.float32, device=device))
         with _Span('lsh_select', device):
-            rank = _encode_topk_keys(sc, v)
-            by_key = torch.argsort(rank, descending=True)                  # unique inside a source: (score desc, id asc)
-            order = by_key[torch.sort(s[by_key], stable=True).indices]     # ... grouped by source again
-            s_o = s[order]
-            place = torch.arange(keys.numel(), dtype=torch.int64, device=device) - _row_starts(keys, n, N)[s_o]
-            take = place < k
-            top = torch.full((n, k), TOPK_SENTINEL, dtype=torch.int64, device=device)
-            top[s_o[take], place[take]] = rank[order][take]
-            ids[b0:b0 + n], scores[b0:b0 + n] = _decode_topk_keys(top)
+            ids[b0:b0 + n], scores[b0:b0 + n] = _select_rows(keys, sc, n, N, k)
 
     _walk(eh, 'topk_links_lsh', src, ex, index, min_bands, consume)
     return eh._send_home(home, ids, scores)

@@ -178,6 +178,15 @@ def lsh_band_keys_bytes(N, P, rows, bands):
     return N * 16 * -(-rows * bands // 4) + 8 * N * bands
 
 
+def wedge_bytes(sources, neighbours, walks, candidates):
+    """algorithmic bytes of WedgeGraph.candidates' expansion (ss_wedge_walks + ss_wedge_fold / ss_wedge_emit) over
+    `sources` sources with `neighbours` = sum deg(u), `walks` = sum W(u) and `candidates` listed pairs: per source its id, two row
+    pointers and W(u); row u is read twice (the walks launch, the expansion), with two row pointers per neighbour each time; every
+    walk reads one col entry; the output is 8 + 4 bytes per listed pair.  What the large tier writes and the sort moves on top of
+    that -- 8 bytes per walk, several times -- is the price of that tier and not in the model."""
+    return sources * (8 + 16 + 8) + 2 * neighbours * (4 + 16) + 4 * walks + 12 * candidates
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
