@@ -491,6 +491,27 @@ int ss_exact_large(const ss_csr_graph *graph, const int64_t *links, int64_t B, i
                    int32_t *balls, float *feats, void *workspace, size_t workspace_bytes, int32_t slots, void *arena, size_t arena_bytes,
                    void *stream);
 
+/* Exact subgraph node lists: per pair (u, v) every node x of B_h(u) | B_h(v), ascending by id and once each, with the distance bytes
+ * (d_u(x), d_v(x)) -- the balls, the graph, the links and SS_FLAG_MASK_TARGET as for ss_exact_pairs / ss_exact_large, with ONE
+ * difference: a root is always in its own ball at distance 0 (n_self is not consulted), so no union is empty.  A distance is in
+ * [0, h]; h + 1 stands for "not within h" and is no distance.  Rows vary in length, so every batch is walked twice with the same
+ * workspace (ss_exact_workspace_bytes(B)), arena (ss_exact_slot_bytes(N) per slot; its distance bytes all zero before and after every call, its visit lists scratch) and stream:
+ *   count pass (rowptr == NULL)  ss_exact_nodes_pairs writes counts[q] = the size of the union for every pair within lds_max_nodes
+ *                                and lists the others in the workspace; ss_exact_nodes_large then counts those.  counts: int32 [B].
+ *   fill pass (rowptr != NULL)   rowptr: int64 [B + 1], ascending offsets into ids (int64) / dist (uint8 [.., 2]) made by the caller
+ *                                from the counts: rowptr[q + 1] - rowptr[q] is counts[q], or 0 for a pair that is to be left out.
+ *                                ss_exact_nodes_pairs writes the rows of length 1 .. lds_max_nodes (the same value as in the count
+ *                                pass), ss_exact_nodes_large those of the workspace's list; neither stores outside
+ *                                [rowptr[q], rowptr[q + 1]).
+ * Return codes and argument checks as ss_exact_pairs / ss_exact_large (B == 0: SS_OK before any launch); counts (count pass) or ids
+ * and dist (fill pass) must not be null. */
+int ss_exact_nodes_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags,
+                         int32_t lds_max_nodes, int32_t *counts, const int64_t *rowptr, int64_t *ids, uint8_t *dist, int32_t *err_flag,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int ss_exact_nodes_large(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags, int32_t *counts,
+                         const int64_t *rowptr, int64_t *ids, uint8_t *dist, void *workspace, size_t workspace_bytes, int32_t slots,
+                         void *arena, size_t arena_bytes, void *stream);
+
 /* out = A * x for a row-grouped CSR with fp32 values -- the node-feature propagation of
  * HashDataset._generate_sign_features (reference datasets/elph.py:87-110: gcn_norm, then torch_sparse.spmm = multiply
  * and scatter-add in edge order).  Every output element is accumulated by one lane in CSR order, product and sum rounded

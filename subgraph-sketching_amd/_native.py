@@ -130,6 +130,10 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_exact_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
+    'ss_exact_nodes_pairs': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ss_exact_nodes_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
     'ss_update_workspace_bytes': (c_size_t, [c_int64, c_int32]),
     'ss_update_mark': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),

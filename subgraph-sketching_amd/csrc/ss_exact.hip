@@ -22,19 +22,11 @@
 //                      whole workgroup instead of one 16-lane group.
 // Both tiers then count a (h + 2) x (h + 2) histogram of (d_u, d_v) (h + 1 = not within h) over the visited nodes; I and the two
 // ball sizes are its prefix sums.  Integer counts: the result does not depend on the order of anything.
+// The tables and the BFS of both tiers live in ss_exact_bfs.hpp (ss_exact_nodes.hip lists the visited nodes with the same walk).
+#include "ss_exact_bfs.hpp"
 #include "ss_feature_algebra.hpp"
 
 namespace ss {
-
-constexpr int kExactThreads = 256;
-constexpr int kExactGroups = kExactThreads / kRow;   // 16-lane groups per workgroup (one frontier node each)
-constexpr int kExactSlotsLog = 12;
-constexpr int kExactSlots = 1 << kExactSlotsLog;      // LDS table entries
-constexpr int kExactMaxNodes = kExactSlots / 2;       // node limit of the LDS tier (load factor <= 1/2 + one insert per lane)
-constexpr int kExactGrid = 256 * 4;                   // LDS-tier workgroups (4 per CU: 32.1 KiB of LDS each, ExactLds)
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kBigDegree = 512;                       // large tier: frontier nodes with more in-edges are walked by the whole workgroup
-constexpr int kBigList = 64;
 
 struct ExactOut {
     int32_t *I;      // [B, H, H]  (nullable)
@@ -42,21 +34,6 @@ struct ExactOut {
     float *feats;    // [B, H(H+2)]
     int32_t *err;    // (nullable) set for ids outside [-N, N)
 };
-
-// workspace of one call: int32 {overflow count, large-tier cursor, pad, pad}, then int32 overflow list [B]
-struct ExactWs {
-    int32_t count, cursor, pad0, pad1;
-};
-
-__device__ __forceinline__ int64_t exact_n_self(const ss_csr_graph &g)
-{
-    return g.n_self_loops_dev ? *g.n_self_loops_dev : g.n_self_loops;
-}
-
-// SS_FLAG_MASK_TARGET: the balls are those of the graph without the edges u -> v and v -> u.  Level 1 expands the root alone, so the
-// root's expansion leaves the partner out (-1: nothing is left out -- no node id is negative); when the partner is reached another
-// way and expanded, it finds the root visited already, so its own removed in-edge needs nothing.
-__device__ __forceinline__ int32_t exact_skip(uint32_t flags, int64_t partner) { return (flags & SS_FLAG_MASK_TARGET) ? (int32_t)partner : -1; }
 
 // (d_u, d_v) bucket of a node from its two side bytes: the lowest level bit, H + 1 when unreached
 template <int H>
@@ -133,52 +110,6 @@ __device__ void exact_bad(int64_t q, const ExactOut &o)
 }
 
 // ---- on-chip tier ---------------------------------------------------------------------------------------------------------------
-// the value of slot i is the 16-bit half (i & 1) of val[i >> 1] (two side bytes; only ds_or_b32 exists, so halves share a word)
-struct ExactLds {
-    uint32_t key[kExactSlots];
-    uint32_t val[kExactSlots / 2];
-    uint16_t list[2][kExactMaxNodes];  // slots in the order each side first reached them (level ranges = frontiers)
-    int hist[25];
-    int n_nodes, ovf;
-    int cnt[2];
-};
-
-// slot of node x (inserted if new; -1: the pair has passed its node limit)
-__device__ __forceinline__ int lds_slot(ExactLds &s, uint32_t x, int limit)
-{
-    uint32_t i = (x * 2654435761u) >> (32 - kExactSlotsLog);
-    for (int probe = 0; probe < kExactSlots; ++probe) {
-        const uint32_t k = s.key[i];
-        if (k == x) return (int)i;
-        if (k == kEmpty) {
-            const uint32_t old = atomicCAS(&s.key[i], kEmpty, x);
-            if (old == kEmpty) {
-                if (atomicAdd(&s.n_nodes, 1) >= limit) {
-                    s.ovf = 1;
-                    return -1;
-                }
-                return (int)i;
-            }
-            if (old == x) return (int)i;
-        }
-        i = (i + 1) & (kExactSlots - 1);
-    }
-    s.ovf = 1;  // (unreachable: at most limit + one key per lane are ever inserted)
-    return -1;
-}
-
-__device__ __forceinline__ void lds_visit(ExactLds &s, uint32_t x, int side, int level, int limit)
-{
-    const int i = lds_slot(s, x, limit);
-    if (i < 0) return;
-    const int sh = 16 * (i & 1) + 8 * side;
-    const uint32_t old = atomicOr(&s.val[i >> 1], (1u << level) << sh);
-    if (((old >> sh) & 0xFFu) == 0) {
-        const int at = atomicAdd(&s.cnt[side], 1);
-        if (at < kExactMaxNodes) s.list[side][at] = (uint16_t)i;
-    }
-}
-
 template <int H>
 __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g, const int64_t *__restrict__ links, int64_t B,
                                                                    int64_t N, int limit, uint32_t flags, ExactOut o,
@@ -186,7 +117,6 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
 {
     __shared__ ExactLds s;
     const int t = threadIdx.x;
-    const int grp = t / kRow, lane = t & (kRow - 1);
     const int64_t n_self = exact_n_self(g);
     for (int i = t; i < kExactSlots; i += kExactThreads) {
         s.key[i] = kEmpty;
@@ -206,35 +136,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
             if (t == 0) exact_bad<H>(q, o);
             continue;  // (nothing was inserted; the next pair's barrier keeps the counters in step)
         }
-        // `ovf` is the workgroup's copy of s.ovf, read only between a barrier that follows every write of a phase and the barrier
-        // before the next phase's writes (the next root insert, the next level's appends): every wave takes the same branches
-        bool ovf = limit <= 0;
-        for (int side = 0; side < 2 && !ovf; ++side) {
-            const int64_t root = side ? v : u;
-            const int32_t skip = exact_skip(flags, side ? u : v);
-            if (root < n_self && t == 0) lds_visit(s, (uint32_t)root, side, 0, limit);
-            __syncthreads();
-            int lo = 0, hi = s.cnt[side];
-            ovf = s.ovf;
-            for (int d = 1; d <= H && lo < hi && !ovf; ++d) {
-                __syncthreads();  // every thread has read hi before the level appends
-                for (int f = lo + grp; f < hi; f += kExactGroups) {
-                    const int64_t y = s.key[s.list[side][f]];
-                    const int64_t e1 = g.rowptr[y + 1];
-                    for (int64_t e = g.rowptr[y] + lane; e < e1; e += kRow) {
-                        if (s.ovf) break;
-                        const int32_t x = g.col[e];
-                        if (d == 1 && x == skip) continue;  // SS_FLAG_MASK_TARGET: the root's expansion leaves the partner out
-                        lds_visit(s, (uint32_t)x, side, d, limit);  // (the self loop of y: y is in the list already)
-                    }
-                }
-                __syncthreads();
-                lo = hi;
-                hi = s.cnt[side] < kExactMaxNodes ? s.cnt[side] : kExactMaxNodes;
-                ovf = s.ovf;
-            }
-            __syncthreads();  // every thread has read s.ovf / s.cnt before the next side's root insert
-        }
+        const bool ovf = exact_lds_bfs<H>(s, g, u, v, n_self, flags, limit);
         if (ovf) {
             if (t == 0) overflow[atomicAdd(&ws->count, 1)] = (int32_t)q;
             __syncthreads();
@@ -263,31 +165,6 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
 }
 
 // ---- large tier -----------------------------------------------------------------------------------------------------------------
-// slot arena: uint32 dist[ceil(N / 4)] (one byte per node: bits 0-3 side u, 4-7 side v), int32 list_u[N], int32 list_v[N]
-__host__ __device__ __forceinline__ int64_t exact_dist_words(int64_t N) { return (N + 3) / 4; }
-__host__ __device__ __forceinline__ int64_t exact_slot_words(int64_t N) { return (exact_dist_words(N) + 2 * N + 3) & ~(int64_t)3; }
-
-struct ExactSlot {
-    uint32_t *dist;
-    int32_t *list[2];
-};
-
-// first reach of x on `side` at `level`?  (the byte's bits are all the information: every access is an agent-scope atomic)
-__device__ __forceinline__ bool slot_reach(const ExactSlot &sl, int32_t x, int side, int level)
-{
-    const int sh = 8 * (x & 3);
-    const uint32_t bit = ((1u << level) << (4 * side)) << sh;
-    const uint32_t old = atomicOr(&sl.dist[x >> 2], bit);
-    return ((old >> sh) & (0xFu << (4 * side))) == 0;
-}
-
-__device__ __forceinline__ uint32_t slot_byte(const ExactSlot &sl, int32_t x)
-{
-    const uint32_t w = __hip_atomic_load(&sl.dist[x >> 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t b = (w >> (8 * (x & 3))) & 0xFFu;
-    return (b & 0xFu) | ((b >> 4) << 8);  // -> the LDS tier's layout for exact_bucket
-}
-
 template <int H>
 __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph g, const int64_t *__restrict__ links, int64_t N,
                                                                      uint32_t flags, ExactOut o, ExactWs *__restrict__ ws,
@@ -299,11 +176,8 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
     __shared__ int n_big;
     __shared__ int64_t next_q;
     const int t = threadIdx.x;
-    const int grp = t / kRow, lane = t & (kRow - 1);
     const int64_t n_self = exact_n_self(g);
-    uint32_t *base = arena + (int64_t)blockIdx.x * exact_slot_words(N);
-    const ExactSlot sl = {base, {reinterpret_cast<int32_t *>(base + exact_dist_words(N)),
-                                 reinterpret_cast<int32_t *>(base + exact_dist_words(N)) + N}};
+    const ExactSlot sl = exact_slot(arena, N);
     const int total = ws->count;
     for (;;) {
         if (t == 0) {
@@ -321,50 +195,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
             __syncthreads();
             continue;
         }
-        for (int side = 0; side < 2; ++side) {
-            const int64_t root = side ? v : u;
-            const int32_t skip = exact_skip(flags, side ? u : v);
-            if (root < n_self && t == 0 && slot_reach(sl, (int32_t)root, side, 0)) sl.list[side][cnt[side]++] = (int32_t)root;
-            __syncthreads();
-            int64_t lo = 0, hi = cnt[side];
-            for (int d = 1; d <= H && lo < hi; ++d) {
-                __syncthreads();
-                for (int64_t f = lo + grp; f < hi; f += kExactGroups) {
-                    const int32_t y = sl.list[side][f];
-                    const int64_t e0 = g.rowptr[y], e1 = g.rowptr[y + 1];
-                    if (e1 - e0 > kBigDegree) {  // walked by the whole workgroup below (or here, if the big list is full)
-                        int at = kBigList;
-                        if (lane == 0) at = atomicAdd(&n_big, 1);
-                        at = __shfl(at, (t & (kWave - 1)) & ~(kRow - 1));
-                        if (at < kBigList) {
-                            if (lane == 0) big[at] = y;
-                            continue;
-                        }
-                    }
-                    for (int64_t e = e0 + lane; e < e1; e += kRow) {
-                        const int32_t x = g.col[e];
-                        if (d == 1 && x == skip) continue;
-                        if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
-                    }
-                }
-                __syncthreads();
-                const int nb = n_big < kBigList ? n_big : kBigList;
-                for (int b = 0; b < nb; ++b) {
-                    const int32_t y = big[b];
-                    const int64_t e1 = g.rowptr[y + 1];
-                    for (int64_t e = g.rowptr[y] + t; e < e1; e += kExactThreads) {
-                        const int32_t x = g.col[e];
-                        if (d == 1 && x == skip) continue;
-                        if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
-                    }
-                }
-                __syncthreads();
-                if (t == 0) n_big = 0;
-                lo = hi;
-                hi = cnt[side];
-            }
-            __syncthreads();
-        }
+        exact_slot_bfs<H>(sl, g, u, v, n_self, flags, cnt, big, &n_big);
         const int64_t cu = cnt[0], cv = cnt[1];
         for (int64_t i = t; i < cu + cv; i += kExactThreads) {
             const int32_t x = i < cu ? sl.list[0][i] : sl.list[1][i - cu];

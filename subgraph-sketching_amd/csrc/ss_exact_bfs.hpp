@@ -1,0 +1,209 @@
+// ss_exact_bfs.hpp -- the two-sided BFS of one link, shared by the exact counts (ss_exact.hip) and the exact node lists
+// (ss_exact_nodes.hip): the on-chip tier's LDS hash table and the large tier's slot of device memory, each with the walk that fills it.
+// What a kernel does with the visited nodes afterwards (a histogram, a sorted list) is its own; see ss_exact.hip for the tiers.
+#pragma once
+#include "ss_common.hpp"
+
+namespace ss {
+
+constexpr int kExactThreads = 256;
+constexpr int kExactGroups = kExactThreads / kRow;   // 16-lane groups per workgroup (one frontier node each)
+constexpr int kExactSlotsLog = 12;
+constexpr int kExactSlots = 1 << kExactSlotsLog;      // LDS table entries
+constexpr int kExactMaxNodes = kExactSlots / 2;       // node limit of the LDS tier (load factor <= 1/2 + one insert per lane)
+constexpr int kExactGrid = 256 * 4;                   // LDS-tier workgroups (4 per CU: 32.1 KiB of LDS each, ExactLds)
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+constexpr int kBigDegree = 512;                       // large tier: frontier nodes with more in-edges are walked by the whole workgroup
+constexpr int kBigList = 64;
+
+// workspace of one call: int32 {overflow count, large-tier cursor, pad, pad}, then int32 overflow list [B]
+struct ExactWs {
+    int32_t count, cursor, pad0, pad1;
+};
+
+__device__ __forceinline__ int64_t exact_n_self(const ss_csr_graph &g)
+{
+    return g.n_self_loops_dev ? *g.n_self_loops_dev : g.n_self_loops;
+}
+
+// SS_FLAG_MASK_TARGET: the balls are those of the graph without the edges u -> v and v -> u.  Level 1 expands the root alone, so the
+// root's expansion leaves the partner out (-1: nothing is left out -- no node id is negative); when the partner is reached another
+// way and expanded, it finds the root visited already, so its own removed in-edge needs nothing.
+__device__ __forceinline__ int32_t exact_skip(uint32_t flags, int64_t partner) { return (flags & SS_FLAG_MASK_TARGET) ? (int32_t)partner : -1; }
+
+// ---- on-chip tier ---------------------------------------------------------------------------------------------------------------
+// the value of slot i is the 16-bit half (i & 1) of val[i >> 1] (two side bytes; only ds_or_b32 exists, so halves share a word)
+struct ExactLds {
+    uint32_t key[kExactSlots];
+    uint32_t val[kExactSlots / 2];
+    uint16_t list[2][kExactMaxNodes];  // slots in the order each side first reached them (level ranges = frontiers)
+    int hist[25];
+    int n_nodes, ovf;
+    int cnt[2];
+};
+
+// slot of node x (inserted if new; -1: the pair has passed its node limit)
+__device__ __forceinline__ int lds_slot(ExactLds &s, uint32_t x, int limit)
+{
+    uint32_t i = (x * 2654435761u) >> (32 - kExactSlotsLog);
+    for (int probe = 0; probe < kExactSlots; ++probe) {
+        const uint32_t k = s.key[i];
+        if (k == x) return (int)i;
+        if (k == kEmpty) {
+            const uint32_t old = atomicCAS(&s.key[i], kEmpty, x);
+            if (old == kEmpty) {
+                if (atomicAdd(&s.n_nodes, 1) >= limit) {
+                    s.ovf = 1;
+                    return -1;
+                }
+                return (int)i;
+            }
+            if (old == x) return (int)i;
+        }
+        i = (i + 1) & (kExactSlots - 1);
+    }
+    s.ovf = 1;  // (unreachable: at most limit + one key per lane are ever inserted)
+    return -1;
+}
+
+__device__ __forceinline__ void lds_visit(ExactLds &s, uint32_t x, int side, int level, int limit)
+{
+    const int i = lds_slot(s, x, limit);
+    if (i < 0) return;
+    const int sh = 16 * (i & 1) + 8 * side;
+    const uint32_t old = atomicOr(&s.val[i >> 1], (1u << level) << sh);
+    if (((old >> sh) & 0xFFu) == 0) {
+        const int at = atomicAdd(&s.cnt[side], 1);
+        if (at < kExactMaxNodes) s.list[side][at] = (uint16_t)i;
+    }
+}
+
+// both BFSs of the pair (u, v) into the workgroup's table (whole workgroup; a root at or above n_self is not visited).  The caller
+// has emptied the table, zeroed s.n_nodes and s.cnt, set s.ovf = (limit <= 0) and passed a barrier since.  -> the pair passed the
+// node limit (workgroup-uniform); every thread has passed a barrier after the last write when this returns
+template <int H>
+__device__ __forceinline__ bool exact_lds_bfs(ExactLds &s, const ss_csr_graph &g, int64_t u, int64_t v, int64_t n_self, uint32_t flags,
+                                              int limit)
+{
+    const int t = threadIdx.x;
+    const int grp = t / kRow, lane = t & (kRow - 1);
+    // `ovf` is the workgroup's copy of s.ovf, read only between a barrier that follows every write of a phase and the barrier
+    // before the next phase's writes (the next root insert, the next level's appends): every wave takes the same branches
+    bool ovf = limit <= 0;
+    for (int side = 0; side < 2 && !ovf; ++side) {
+        const int64_t root = side ? v : u;
+        const int32_t skip = exact_skip(flags, side ? u : v);
+        if (root < n_self && t == 0) lds_visit(s, (uint32_t)root, side, 0, limit);
+        __syncthreads();
+        int lo = 0, hi = s.cnt[side];
+        ovf = s.ovf;
+        for (int d = 1; d <= H && lo < hi && !ovf; ++d) {
+            __syncthreads();  // every thread has read hi before the level appends
+            for (int f = lo + grp; f < hi; f += kExactGroups) {
+                const int64_t y = s.key[s.list[side][f]];
+                const int64_t e1 = g.rowptr[y + 1];
+                for (int64_t e = g.rowptr[y] + lane; e < e1; e += kRow) {
+                    if (s.ovf) break;
+                    const int32_t x = g.col[e];
+                    if (d == 1 && x == skip) continue;  // SS_FLAG_MASK_TARGET: the root's expansion leaves the partner out
+                    lds_visit(s, (uint32_t)x, side, d, limit);  // (the self loop of y: y is in the list already)
+                }
+            }
+            __syncthreads();
+            lo = hi;
+            hi = s.cnt[side] < kExactMaxNodes ? s.cnt[side] : kExactMaxNodes;
+            ovf = s.ovf;
+        }
+        __syncthreads();  // every thread has read s.ovf / s.cnt before the next side's root insert
+    }
+    return ovf;
+}
+
+// ---- large tier -----------------------------------------------------------------------------------------------------------------
+// slot arena: uint32 dist[ceil(N / 4)] (one byte per node: bits 0-3 side u, 4-7 side v), int32 list_u[N], int32 list_v[N]
+__host__ __device__ __forceinline__ int64_t exact_dist_words(int64_t N) { return (N + 3) / 4; }
+__host__ __device__ __forceinline__ int64_t exact_slot_words(int64_t N) { return (exact_dist_words(N) + 2 * N + 3) & ~(int64_t)3; }
+
+struct ExactSlot {
+    uint32_t *dist;
+    int32_t *list[2];
+};
+
+__device__ __forceinline__ ExactSlot exact_slot(uint32_t *arena, int64_t N)
+{
+    uint32_t *base = arena + (int64_t)blockIdx.x * exact_slot_words(N);
+    return {base, {reinterpret_cast<int32_t *>(base + exact_dist_words(N)), reinterpret_cast<int32_t *>(base + exact_dist_words(N)) + N}};
+}
+
+// first reach of x on `side` at `level`?  (the byte's bits are all the information: every access is an agent-scope atomic)
+__device__ __forceinline__ bool slot_reach(const ExactSlot &sl, int32_t x, int side, int level)
+{
+    const int sh = 8 * (x & 3);
+    const uint32_t bit = ((1u << level) << (4 * side)) << sh;
+    const uint32_t old = atomicOr(&sl.dist[x >> 2], bit);
+    return ((old >> sh) & (0xFu << (4 * side))) == 0;
+}
+
+__device__ __forceinline__ uint32_t slot_byte(const ExactSlot &sl, int32_t x)
+{
+    const uint32_t w = __hip_atomic_load(&sl.dist[x >> 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t b = (w >> (8 * (x & 3))) & 0xFFu;
+    return (b & 0xFu) | ((b >> 4) << 8);  // -> the LDS tier's layout for exact_bucket
+}
+
+// both BFSs of the pair (u, v) into the slot (whole workgroup).  cnt[2], big[kBigList] and *n_big are the workgroup's LDS; the caller
+// has zeroed cnt and *n_big and passed a barrier since.  Afterwards sl.list[side][0 .. cnt[side]) are the nodes of side's ball; every
+// thread has passed a barrier after the last write when this returns
+template <int H>
+__device__ __forceinline__ void exact_slot_bfs(const ExactSlot &sl, const ss_csr_graph &g, int64_t u, int64_t v, int64_t n_self,
+                                               uint32_t flags, int *cnt, int *big, int *n_big)
+{
+    const int t = threadIdx.x;
+    const int grp = t / kRow, lane = t & (kRow - 1);
+    for (int side = 0; side < 2; ++side) {
+        const int64_t root = side ? v : u;
+        const int32_t skip = exact_skip(flags, side ? u : v);
+        if (root < n_self && t == 0 && slot_reach(sl, (int32_t)root, side, 0)) sl.list[side][cnt[side]++] = (int32_t)root;
+        __syncthreads();
+        int64_t lo = 0, hi = cnt[side];
+        for (int d = 1; d <= H && lo < hi; ++d) {
+            __syncthreads();
+            for (int64_t f = lo + grp; f < hi; f += kExactGroups) {
+                const int32_t y = sl.list[side][f];
+                const int64_t e0 = g.rowptr[y], e1 = g.rowptr[y + 1];
+                if (e1 - e0 > kBigDegree) {  // walked by the whole workgroup below (or here, if the big list is full)
+                    int at = kBigList;
+                    if (lane == 0) at = atomicAdd(n_big, 1);
+                    at = __shfl(at, (t & (kWave - 1)) & ~(kRow - 1));
+                    if (at < kBigList) {
+                        if (lane == 0) big[at] = y;
+                        continue;
+                    }
+                }
+                for (int64_t e = e0 + lane; e < e1; e += kRow) {
+                    const int32_t x = g.col[e];
+                    if (d == 1 && x == skip) continue;
+                    if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
+                }
+            }
+            __syncthreads();
+            const int nb = *n_big < kBigList ? *n_big : kBigList;
+            for (int b = 0; b < nb; ++b) {
+                const int32_t y = big[b];
+                const int64_t e1 = g.rowptr[y + 1];
+                for (int64_t e = g.rowptr[y] + t; e < e1; e += kExactThreads) {
+                    const int32_t x = g.col[e];
+                    if (d == 1 && x == skip) continue;
+                    if (slot_reach(sl, x, side, d)) sl.list[side][atomicAdd(&cnt[side], 1)] = x;
+                }
+            }
+            __syncthreads();
+            if (t == 0) *n_big = 0;
+            lo = hi;
+            hi = cnt[side];
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace ss

@@ -1000,6 +1000,32 @@ class ElphHashes(object):
         return exact.exact_subgraph_features(self, links, num_nodes, edge_index, batch_size=batch_size, return_counts=return_counts,
                                              mask_target=mask_target)
 
+    def exact_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=11000000, mask_target=False, max_nodes=None, return_info=False):
+        """WHICH nodes exact_subgraph_features counts: per link (u, v) every node x of B_h(u) | B_h(v), h = max_hash_hops, with the
+        distance pair (d_u(x), d_v(x)) -- the node set of the link's enclosing subgraph with its distance-encoding labels.  The graph,
+        the balls (in-edge hops; on a symmetric edge_index: hops) and the arguments are those of exact_subgraph_features, except that
+        a root is always in its own ball at distance 0, also a node at or above max(edge_index) + 1, whose sketch ball is empty.  BFS
+        on the GPU (exact_nodes.py, csrc/ss_exact_nodes.hip).
+        @param links: int tensor [L, 2] (or [2]), torch-style negative ids wrapped; CPU or device; L = 0 fine
+        @param num_nodes, edge_index: as given to build_hash_tables; duplicate edges and self-loop edges change nothing; E = 0 fine
+        @param batch_size: pairs per launch (rows do not depend on it)
+        @param mask_target: True lists every link in the graph without its own edge (every copy of u -> v and of v -> u), as
+               exact_subgraph_features(mask_target=True) counts it
+        @param max_nodes: None = no cap; otherwise a link whose union holds more than max_nodes nodes gets an EMPTY row and is
+               reported in info['truncated'] (the rule max_walks is for WedgeGraph.candidates, applied to hub links)
+        @return: (rowptr int64 [L + 1], ids int64 [T], dist uint8 [T, 2]) on links.device, T = rowptr[L]: row q is
+                 ids[rowptr[q] : rowptr[q + 1]], ascending and unique, dist[:, 0] = d_u, dist[:, 1] = d_v.  A distance of 0 .. h is the
+                 graph distance (within the ball it equals the distance in the induced subgraph).  h + 1 is a SENTINEL, not a
+                 distance: it says "farther than h, or unreachable", so labels computed on the induced subgraph may differ beyond h.
+                 u == v gives one ball with d_u == d_v.  A row is a function of the graph, the link and mask_target only: not of
+                 the kernel tier, batch_size or the other links.  The counts of exact_subgraph_features(return_counts=True) are
+                 histograms of dist: I[q, k1, k2] = #{d_u <= k1 + 1 and d_v <= k2 + 1} (for roots below max(edge_index) + 1).
+                 With return_info also {'truncated': int64 indices of the capped links, 'lds_links' / 'large_links': how many links
+                 each kernel tier counted}.  Argument errors as exact_subgraph_features, before any launch.  No CPU fallback."""
+        from . import exact_nodes
+        return exact_nodes.exact_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=batch_size, mask_target=mask_target,
+                                                max_nodes=max_nodes, return_info=return_info)
+
     def update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
         """the tables of build_hash_tables(num_nodes, old_edge_index) brought up to date with a changed edge list WITHOUT a rebuild: a
         hop-k row depends only on the closed in-neighbourhood of its node, so hop k recomputes exactly the rows within k hops downstream
