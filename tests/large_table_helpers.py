@@ -6,6 +6,9 @@ import torch
 
 ATOL = 1e-4
 GB = 1 << 30
+# free device memory asked for around ONE [8 650 752, 128] four-byte table (4.43 GB) and what is made from it: the measured peak of
+# the spmm case + 10 % (profiles/large_tables_tests.txt)
+NEEDS_ONE_TABLE = int(1.1 * 9886710784)
 
 
 class Big(object):
@@ -32,6 +35,14 @@ def release_all(dev):
     del LIVE[:]
     torch.cuda.synchronize(dev)
     torch.cuda.empty_cache()
+
+
+def require_free_memory(dev, need, what):
+    """skip the calling test, with the byte counts, when the device has less than `need` bytes free"""
+    import pytest
+    free = torch.cuda.mem_get_info(dev)[0]
+    if free < need:
+        pytest.skip(f'{what} needs {need} bytes of free device memory, {free} are free')
 
 
 def wrap(ids, n):

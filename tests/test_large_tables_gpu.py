@@ -22,8 +22,8 @@ import torch
 
 from conftest import oracle_params
 import large_table_restatement as R
-from large_table_helpers import ATOL, GB, LIVE as _LIVE, Big as _Big, boundary_links as _boundary_links, compacted_oracle as _compacted_oracle, \
-    feature_tol as _feature_tol, release_all as _release_all
+from large_table_helpers import ATOL, GB, LIVE as _LIVE, NEEDS_ONE_TABLE, Big as _Big, boundary_links as _boundary_links, \
+    compacted_oracle as _compacted_oracle, feature_tol as _feature_tol, release_all as _release_all, require_free_memory as _require_free_memory
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +31,7 @@ RTOL = 1e-5
 LC_RTOL = 3e-7
 SHAPES = {'A': ((1 << 23) + (1 << 18), [1 << 22, 1 << 23]), 'B': ((1 << 24) + (1 << 18), [1 << 22, 1 << 23, 1 << 24])}
 # free device memory a fixture asks for: the measured peak of its tests + 10 % (profiles/large_tables_tests.txt)
-NEEDS = {'A': int(1.1 * 52526602240), 'B': int(1.1 * 83686005760), 'spmm': int(1.1 * 9886710784)}
+NEEDS = {'A': int(1.1 * 52526602240), 'B': int(1.1 * 83686005760), 'spmm': NEEDS_ONE_TABLE}
 LOW_HUB_THRESHOLD = 16   # below the ~40 in-edges of a window row, far above the background's (Poisson, mean 2)
 
 
@@ -57,9 +57,7 @@ def _eh(ssa, **kw):
 def _make(ssa, dev, name):
     _release_all(dev)
     n, bounds = SHAPES[name]
-    free = torch.cuda.mem_get_info(dev)[0]
-    if free < NEEDS[name]:
-        pytest.skip(f'fixture {name} needs {NEEDS[name]} bytes of free device memory, {free} are free')
+    _require_free_memory(dev, NEEDS[name], f'fixture {name}')
     torch.cuda.reset_peak_memory_stats(dev)
     big = _Big()
     big.name, big.n, big.bounds = name, n, bounds
@@ -389,10 +387,7 @@ def test_spmm_operand_above_4_gib(ssa, dev):
     from subgraph_sketching_amd import sign
     _release_all(dev)
     n, bounds = SHAPES['A']
-    need = NEEDS['spmm']
-    free = torch.cuda.mem_get_info(dev)[0]
-    if free < need:
-        pytest.skip(f'needs {need} bytes of free device memory, {free} are free')
+    _require_free_memory(dev, NEEDS['spmm'], 'the spmm operand and result')
     torch.cuda.reset_peak_memory_stats(dev)
     g = R.boundary_graph(n, bounds, dev, seed=31)
     ei = g.edge_index

@@ -24,7 +24,7 @@ import large_table_restatement as R
 import masked_restatement as mr
 import rank_restatement as rr
 import update_restatement as ur
-from large_table_helpers import LIVE, Big, boundary_links, compacted_oracle, feature_tol, release_all, wrap
+from large_table_helpers import LIVE, Big, boundary_links, compacted_oracle, feature_tol, release_all, require_free_memory, wrap
 from ppr_restatement import pagerank_power
 from score_restatement import e_fp, raw_head
 
@@ -80,9 +80,7 @@ def _near_head(ssa):
 def _make(ssa, dev, name):
     release_all(dev)
     P, p, n, bounds = SHAPES[name]
-    free = torch.cuda.mem_get_info(dev)[0]
-    if free < NEEDS[name]:
-        pytest.skip(f'fixture {name} needs {NEEDS[name]} bytes of free device memory, {free} are free')
+    require_free_memory(dev, NEEDS[name], f'fixture {name}')
     torch.cuda.reset_peak_memory_stats(dev)
     big = Big()
     big.name, big.n, big.bounds, big.P, big.M = name, n, bounds, P, 1 << p

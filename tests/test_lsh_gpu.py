@@ -6,7 +6,8 @@ topk_links_lsh against the brute-force composition (score_links over the restate
 The (graph, P, hop, rows, bands) cases were chosen on the CPU from oracle tables so that the restatement alone is non-trivial (at least
 half the sources have a candidate, none has all N - 1); every test asserts that again on the tables it is given.
 
-Written, not yet run on an MI355X (the host walk was rehearsed on the CPU with numpy stand-ins for the three launches)."""
+Written, not yet run on an MI355X (the host walk was rehearsed on the CPU with numpy stand-ins for the three launches); the kernels'
+first runs there are those of test_lsh_planted_gpu.py (profiles/lsh_planted_tests.txt)."""
 from argparse import Namespace
 
 import numpy as np

@@ -12,6 +12,7 @@ import torch
 
 from conftest import REPO, load_golden, oracle_params
 from score_restatement import raw_head
+import lsh_planted as planted
 import lsh_restatement as restated
 
 
@@ -206,3 +207,147 @@ def test_argument_errors_of_the_library_are_reported_without_a_gpu():
     assert lib.ss_lsh_count(None, 0, 30, None, 128, 4, 32, 64, None, None, 8, None, None, None) == 0      # no sources
     assert lib.ss_lsh_fill(fake, 2, 30, fake, 128, 4, 32, 64, fake, fake, 8, None, fake, None) == -1      # no offsets
     assert lib.ss_lsh_fill(fake, -1, 30, fake, 128, 4, 32, 64, fake, fake, 8, fake, fake, None) == -1
+
+
+# ---- planted tables (lsh_planted.py): the generator and expected() pinned on the restatement for every small case of --------------
+# ---- test_lsh_planted_gpu.py, and the non-triviality conditions those tests assert -------------------------------------------------
+
+def _pin(N, P, rows, bands, groups, sources, caps=(1024,), trivial_ok=False, near=()):
+    """expected() == the restatement on the generated table for every max_bucket of `caps`, with exclude and min_bands on the first;
+    background rows have no partner; the noise words change nothing.  -> the table"""
+    b = planted.resolve_bands(P, rows, bands)
+    table = planted.planted_table(N, P, rows, bands, groups, seed=N + P, near=near)
+    assert table.shape == (N, P) and table.dtype == np.int64 and table.min() >= 0 and table.max() < (1 << 32)
+    members = set(v for m, J in groups if J for v in m)
+    for j, (group, sizes) in enumerate(restated.band_groups(table, rows, b)):
+        in_band = set(v for m, J in groups if j in J for v in m)
+        assert all(sizes[group[v]] == 1 for v in range(N) if v not in in_band), 'a background row has a partner'
+    everyone = np.arange(N, dtype=np.int64)
+    alone = restated.lsh_candidates(table, everyone, rows, b)
+    assert all(alone[0][v] == alone[0][v + 1] for v in range(N) if v not in members)
+    for i, cap in enumerate(caps):
+        want, skipped = planted.expected(N, rows, b, groups, sources, cap)
+        _assert_same(want, restated.lsh_candidates(table, sources, rows, b, max_bucket=cap))
+        np.testing.assert_array_equal(skipped, restated.skipped_buckets(table, rows, b, max_bucket=cap))
+        if i == 0 and not trivial_ok:
+            assert planted.nontrivial(want[0], N), 'a trivial expectation checks nothing'
+    if P > rows * b:
+        other = planted.planted_table(N, P, rows, bands, groups, seed=N + P, noise_seed=977, near=near)
+        assert np.array_equal(other[:, :rows * b], table[:, :rows * b]) and (other[:, rows * b:] != table[:, rows * b:]).mean() > 0.9
+        _assert_same(restated.lsh_candidates(other, sources, rows, b), restated.lsh_candidates(table, sources, rows, b))
+        np.testing.assert_array_equal(planted.band_keys(other, rows, b), planted.band_keys(table, rows, b))
+    k = min(6, len(sources), len(alone[1]))  # pairs that exist among them, by positive and by negative id
+    exclude = np.stack([np.tile(sources[:k], 2), np.concatenate([alone[1][:k], alone[1][:k] - N])])
+    _assert_same(planted.expected(N, rows, b, groups, sources, caps[0], exclude=exclude)[0],
+                 restated.lsh_candidates(table, sources, rows, b, max_bucket=caps[0], exclude=exclude))
+    _assert_same(planted.expected(N, rows, b, groups, sources, caps[0], min_bands=2)[0],
+                 restated.lsh_candidates(table, sources, rows, b, max_bucket=caps[0], min_bands=2))
+    twin = planted.planted_table_torch(N, P, rows, bands, groups, seed=N + P, device='cpu', block=7, near=near)
+    assert twin.dtype == torch.int64 and np.array_equal(twin.numpy(), table)
+    packed = planted.planted_table_torch(N, P, rows, bands, groups, seed=N + P, device='cpu', dtype=torch.int32, near=near)
+    assert np.array_equal(packed.numpy().view(np.uint32).astype(np.int64), table)
+    return table
+
+
+@pytest.mark.parametrize('P,rows,bands', planted.TILE_CASES)
+def test_planted_tile_cases(P, rows, bands):
+    T = planted.tile_rows(P)
+    assert T == min(64, 8192 // P) and planted.tile_sizes(P) == [T, T + 1, 2 * T - 1, 3 * T + 5]
+    for N in planted.tile_sizes(P):
+        groups, sources = planted.tile_plan(P, rows, bands, N)
+        members = set(v for m, _ in groups for v in m)
+        assert {0, N - 1} <= members and all({k - 1, k} <= members for k in range(T, N, T))
+        assert {0, N - 1} <= set(int(u) % N for u in sources)
+        _pin(N, P, rows, bands, groups, sources)
+
+
+def test_planted_one_and_two_node_tables():
+    _pin(1, 12, 1, 5, [], np.array([0, -1, 0], dtype=np.int64), trivial_ok=True)
+    want, _ = planted.expected(2, 4, 32, [([1, 0], [0, 31])], np.array([0, 1, -1], dtype=np.int64), 1024)
+    assert want[1].tolist() == [1, 0, 0] and want[2].tolist() == [2, 2, 2]
+    _pin(2, 128, 4, None, [([1, 0], [0, 31])], np.array([0, 1, -1], dtype=np.int64), trivial_ok=True)
+
+
+def test_planted_round_case():
+    N, P, rows = planted.ROUND_N, planted.ROUND_P, planted.ROUND_ROWS
+    groups, by_size = planted.round_plan()
+    sources = planted.round_sources(groups)
+    caps = [1024] + [c for m in planted.ROUND_SIZES for c in (m, m - 1)]
+    near = planted.round_near(groups)
+    table = _pin(N, P, rows, None, groups, sources, caps=caps, near=near)
+    one_bit = planted.band_keys(table, rows, None, 1)
+    for w in (rows - 1, 0, 1):  # a near miss of every kind meets its leader in one range of a one-bit key: only the slices tell them apart
+        assert any(one_bit[j][v] == one_bit[j][leader] for v, leader, j, miss in near if miss == w)
+    for v, leader, j, w in near:
+        differ = np.nonzero(table[v, j * rows:(j + 1) * rows] != table[leader, j * rows:(j + 1) * rows])[0]
+        assert differ.tolist() == [w]
+    assert set(planted.ROUND_SIZES) <= planted.bucket_sizes(N, 32, groups, sources)
+    want = planted.expected(N, rows, 32, groups, sources, 1024)[0]
+    assert set(want[2].tolist()) >= {1, 3, 4, 5, 32}
+    for m, (members, band) in by_size.items():   # max_bucket = m lists the group, m - 1 skips it
+        row = lambda cap: np.diff(planted.expected(N, rows, 32, groups, members[:1], cap)[0][0])[0]
+        assert row(m) == m - 1 and row(m - 1) == 0
+        skipped = lambda cap: planted.expected(N, rows, 32, groups, sources, cap)[1][band] - (3 > cap)  # (the group of three is in every band)
+        assert skipped(m - 1) == 1 and skipped(m) == 0
+    # the six-bit key: a planted group that fits max_bucket is dropped because its key range does not, another is listed through a
+    # range with false matches; both sit inside their band's order with more than max_bucket + 1 entries from their range's start on
+    cap = planted.SIX_BIT_MAX_BUCKET
+    keys = planted.band_keys(table, rows, None, 6)
+    runs = planted.key_run_lengths(keys)
+    assert keys.min() >= 0 and keys.max() < 64
+    dropped = listed = False
+    for m, (members, band) in by_size.items():
+        u = members[0]
+        inside = (keys[band] < keys[band][u]).sum() > 0 and (keys[band] >= keys[band][u]).sum() > cap + 1
+        dropped |= bool(m <= cap < runs[band][u] and inside)
+        listed |= bool(m < runs[band][u] <= cap and inside)
+    assert dropped and listed
+    six = planted.six_bit_sources(groups)
+    got, skipped = planted.candidates_under_keys(table, six, rows, None, cap, 6)
+    full = restated.lsh_candidates(table, six, rows, None, max_bucket=cap)
+    assert planted.nontrivial(got[0], N) and 0 < got[1].size < full[1].size and skipped.sum() > 0
+    pairs = lambda r: set(zip(np.repeat(np.arange(len(six)), np.diff(r[0])).tolist(), r[1].tolist(), r[2].tolist()))
+    assert set((s, v) for s, v, _ in pairs(got)) <= set((s, v) for s, v, _ in pairs(full))
+    # with all 64 bits the key ranges are the buckets, and the short-key restatement is the restatement
+    _assert_same(planted.candidates_under_keys(table, sources, rows, None, 1024, 64)[0], restated.lsh_candidates(table, sources, rows))
+
+
+@pytest.mark.parametrize('b', planted.WAVE_BANDS)
+def test_planted_wave_case(b):
+    N, P, rows = planted.WAVE_N, planted.WAVE_P, planted.WAVE_ROWS
+    groups, good = planted.wave_plan(b)
+    assert len(good) >= 17 and len(set(good)) == len(good)
+    _pin(N, P, rows, b, groups, np.array(good, dtype=np.int64))
+    for S in (1, 2, 3, 17):
+        want = planted.expected(N, rows, b, groups, good[:S], 1024)[0]
+        assert planted.nontrivial(want[0], N)
+    assert [S * b % 16 for S in (1, 2, 3, 17) for b in planted.WAVE_BANDS].count(0) == 0
+
+
+def test_planted_large_plan_and_the_band_key():
+    groups, sources = planted.large_plan()
+    N, b = planted.LARGE_N, planted.LARGE_BANDS
+    planted.check_plan(N, b, groups)
+    assert N * planted.LARGE_P * 4 > (1 << 32) and len(groups) == 12
+    for bound in planted.LARGE_BOUNDS:
+        assert any(min(m) < bound <= max(m) for m, _ in groups) and {bound - 1, bound} <= set(sources.tolist())
+    assert any(N - 1 in m for m, _ in groups)
+    want, skipped = planted.expected(N, planted.LARGE_ROWS, b, groups, sources, 1024)
+    assert planted.nontrivial(want[0], N) and skipped.sum() == 0 and {17, 33} <= planted.bucket_sizes(N, b, groups, sources)
+    # band_key: r = 1 is one round of the splitmix64 finaliser from the state r ^ x, plus the golden ratio; wrapping in 64 bits
+    def h(x):
+        x ^= x >> 30
+        x = x * 0xBF58476D1CE4E5B9 & planted.M64
+        x ^= x >> 27
+        x = x * 0x94D049BB133111EB & planted.M64
+        return x ^ (x >> 31)
+    t = np.array([[0, 1, (1 << 32) - 1, 12345], [7, 7, 7, 7]], dtype=np.int64)
+    for rows, bands in ((1, 4), (2, 2), (4, 1), (3, 1)):
+        for bits in (64, 6, 1):
+            keys = planted.band_keys(t, rows, bands, bits).view(np.uint64)
+            for j in range(bands):
+                for v in range(2):
+                    k = rows
+                    for x in t[v, j * rows:(j + 1) * rows].tolist():
+                        k = (h(k ^ x) + planted.GOLDEN) & planted.M64
+                    assert int(keys[j, v]) == k & ((1 << bits) - 1)
