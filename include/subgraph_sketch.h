@@ -612,6 +612,43 @@ int ss_masked_pair_features(const ss_csr_graph *graph, const int64_t *links, int
                             int32_t *dbg_zero, int32_t *dbg_row_zeros, uint8_t *dbg_masked, int32_t *err_flag, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* Exact enclosing subgraphs: the induced adjacency and the node labels of the node rows of ss_exact_nodes_pairs / ss_exact_nodes_large
+ * (rowptr int64 [B + 1], ids int64 [T], T = rowptr[B]; listed node t of link q has the LOCAL index t - rowptr[q]) -- what the reference
+ * builds per link in Python: k_hop_subgraph's A[nodes, :][:, nodes] with the target link zeroed (src/datasets/seal.py:291-348), the
+ * edge list and weights of construct_pyg_graph (:351-389) and drnl / de / de+ (src/labelling_tricks.py:11-27, 63-134).
+ *   ss_subgraph_adj     csr_rowptr / csr_col: the destination-grouped CSR of the graph (row x = the sources j of the arcs j -> x) with
+ *                       every row ASCENDING (ss_csr_sort_rows), N < 2^31 nodes; links: int64 [B, 2] (negative ids wrapped).  The
+ *                       adjacency row of listed node t (id x, link (u, v)) holds every distinct j != x of the link's id row with an
+ *                       arc j -> x, as local indices, ascending, with the number of copies of the arc; flags & SS_FLAG_MASK_TARGET and
+ *                       u != v: without (x = u, j = v) and (x = v, j = u).
+ *                         count pass (adj_ptr == NULL)  counts[t] (int32 [T]) = the length of t's adjacency row
+ *                         fill pass  (adj_ptr != NULL)  adj_ptr: int64 [T + 1], the caller's cumulative sum of counts; writes nbr and
+ *                                                       weight (int32 [adj_ptr[T]]) inside [adj_ptr[t], adj_ptr[t + 1]) and
+ *                                                       roots[q] (int32 [B, 2]) = the local indices of u and v for every link with a
+ *                                                       non-empty row (the caller presets the others)
+ *                       switch_ratio >= 0: a node with more than switch_ratio * (row length) in-arcs walks the id row and searches its
+ *                       CSR row, every other node walks its arcs and searches the id row; the rows do not depend on it.
+ *   ss_subgraph_labels  z from two BFSs per link over that adjacency (depth from u, depth from v; unreachable = max_dist; all clipped
+ *                       to max_dist in [1, SS_SUBGRAPH_MAX_DIST]):  SS_SUBGRAPH_LABEL_DE  z: int64 [T, 2] = (d_u, d_v);
+ *                       SS_SUBGRAPH_LABEL_DE_PLUS  the same with v removed for d_u and u removed for d_v, the removed root's entry 1;
+ *                       SS_SUBGRAPH_LABEL_DRNL  z: int64 [T], those two distances with the removed root's entry 0 through
+ *                       1 + min(d_u, d_v) + (d / 2)(d / 2 + d % 2 - 1), d = d_u + d_v, and 1 where either is 0.  u == v: one root,
+ *                       nothing removed, d_u == d_v.  Rows of at most min(lds_max_nodes, 2048) nodes are labelled on chip; row q of the
+ *                       others uses workspace[4 ws_ptr[q] .. 4 ws_ptr[q + 1]) (int32), ws_ptr: int64 [B + 1] = the cumulative sum of
+ *                       the lengths of exactly those rows (workspace may be null when there is none).
+ * Both return SS_OK for B == 0 (ss_subgraph_adj: or T == 0) before any launch, SS_ERR_INVALID_ARG for negative sizes, null pointers,
+ * a max_dist out of range; ss_subgraph_labels returns SS_ERR_UNSUPPORTED for an unknown label mode. */
+#define SS_SUBGRAPH_LABEL_DRNL 0
+#define SS_SUBGRAPH_LABEL_DE 1
+#define SS_SUBGRAPH_LABEL_DE_PLUS 2
+#define SS_SUBGRAPH_MAX_DIST (1 << 20)
+int ss_subgraph_adj(const int64_t *csr_rowptr, const int32_t *csr_col, int64_t N, const int64_t *links, int64_t B, const int64_t *rowptr,
+                    const int64_t *ids, int64_t T, uint32_t flags, int32_t switch_ratio, int32_t *counts, const int64_t *adj_ptr,
+                    int32_t *nbr, int32_t *weight, int32_t *roots, void *stream);
+int ss_subgraph_labels(const int64_t *rowptr, int64_t B, const int32_t *roots, const int64_t *adj_ptr, const int32_t *nbr,
+                       int32_t label_mode, int64_t max_dist, int32_t lds_max_nodes, const int64_t *ws_ptr, int32_t *workspace, int64_t *z,
+                       void *stream);
+
 /* Measurement-only entry points (launch-duration probes used by bench.py and tools/) are declared in
  * subgraph_sketch_debug.h; they are not part of the drop-in boundary. */
 

@@ -9,7 +9,8 @@ from .feature_store import DeviceFeatureStore
 from .head import StructureHead
 from .negatives import NegativeSampler, sample_negatives
 from .wedge import WedgeGraph
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge
+from .subgraphs import ExactSubgraphs
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs
 
 __all__ = ['LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
-           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives', 'wedge', 'WedgeGraph']
+           'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives', 'wedge', 'WedgeGraph', 'subgraphs', 'ExactSubgraphs']

@@ -53,6 +53,8 @@ PROF_MINHASH_HOP, PROF_HLL_HOP, PROF_FIRST_HOP_MH, PROF_FIRST_HOP_HLL, PROF_PAIR
 MEGA_DESC_WORDS = 8  # SS_MEGA_DESC_WORDS
 NEG_MODES = {'uniform': 0, 'same_source': 1, 'wedge': 2}  # SS_NEG_*
 NEG_MAX_TRIES = 64  # SS_NEG_MAX_TRIES
+SUBGRAPH_LABELS = {'drnl': 0, 'de': 1, 'de+': 2}  # SS_SUBGRAPH_LABEL_*: the labels ss_subgraph_labels computes
+SUBGRAPH_MAX_DIST = 1 << 20  # SS_SUBGRAPH_MAX_DIST
 WEDGE_MAX_SLOTS, WEDGE_MAX_SLICES = 4096, 64  # SS_WEDGE_MAX_SLOTS; the slices ss_wedge_emit takes at most
 MEGA_SLICE, MEGA_SLOT_BYTES, CSR_FINGERPRINT_BYTES, MAX_MIRRORS = 1024, 1280, 8448, 7  # SS_MEGA_SLICE / SS_MEGA_SLOT_BYTES of include/subgraph_sketch.h
 
@@ -134,6 +136,10 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_exact_nodes_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
+    'ss_subgraph_adj': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_uint32, c_int32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_subgraph_labels': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
     'ss_update_workspace_bytes': (c_size_t, [c_int64, c_int32]),
     'ss_update_mark': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),

@@ -109,6 +109,7 @@ class ElphHashes(object):
         self.minhash_seed = 1
         self.num_perm = args.minhash_num_perm
         self._csr_cache = _CsrCache(self._bounds, self._prop_hub_hint)
+        self._sorted_rows_cache = None  # exact_subgraphs: the cached CSR's columns with every row sorted (subgraphs._SortedRowsCache)
         self.minhash_prop = MinhashPropagation(self._csr_cache, self._report_after_host_copy, defer_first_hop, defer_table_hop)
         # hll params (reference hashing.py:65-81)
         self.p = args.hll_p
@@ -147,6 +148,7 @@ class ElphHashes(object):
         state = dict(self.__dict__)
         state['_dev_params'], state['_dev_perms'] = {}, {}
         state['_csr_cache'], state['_deferred'] = None, None
+        state['_sorted_rows_cache'] = None
         state['_hub_words'], state['_hub_arena'] = {}, None
         state.pop('_tables_id', None)
         state['minhash_prop'], state['hll_prop'] = None, None
@@ -1025,6 +1027,34 @@ class ElphHashes(object):
         from . import exact_nodes
         return exact_nodes.exact_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=batch_size, mask_target=mask_target,
                                                 max_nodes=max_nodes, return_info=return_info)
+
+    def exact_subgraphs(self, links, num_nodes, edge_index, batch_size=11000000, mask_target=True, max_nodes=None, node_label='drnl',
+                        max_dist=1000, return_info=False):
+        """the labelled enclosing subgraph of every link as one disjoint-union batch: the node rows of exact_subgraph_nodes, the
+        adjacency they induce and the SEAL node labels computed INSIDE each subgraph -- the object the reference's SEAL path builds
+        per link in Python (k_hop_subgraph + construct_pyg_graph + labelling_tricks.py, src/datasets/seal.py:291-389), here from HIP
+        kernels (subgraphs.py, csrc/ss_subgraph.hip).
+        @param links, num_nodes, edge_index, batch_size, max_nodes: as exact_subgraph_nodes takes them (same checks, before any launch)
+        @param mask_target: True (default, as SEAL always does) removes the link's own edge: the distance bytes are those of
+               exact_subgraph_nodes(mask_target=True) and the adjacency rows of u and v do not list each other.  The node SET does
+               not depend on it.  It changes nothing for a link that is no edge, or with u == v
+        @param node_label: 'drnl', 'de', 'de+' (labelling_tricks.py bit for bit), 'hop' (min of the two ball distances), 'zo'
+               (hop == 0) or None.  'de': z = (d_u, d_v), the BFS depths in the induced subgraph clipped to max_dist, unreachable =
+               max_dist.  'de+': d_u with v removed, d_v with u removed, the removed root's own entry 1.  'drnl': those two distances
+               with the removed root's entry 0, z = 1 + min(d_u, d_v) + (d // 2)(d // 2 + d % 2 - 1), d = d_u + d_v, and 1 where
+               either is 0.  These depths can exceed h + 1 and differ from the ball sentinel: that is why they are computed.
+               u == v is outside the reference's domain and defined here: one root, nothing removed, d_u == d_v, 'drnl' gives the
+               root 1
+        @param max_dist: integer in [1, 2^20]
+        @return: subgraphs.ExactSubgraphs on links.device: rowptr / ids / dist (exactly exact_subgraph_nodes' result), roots int32 [L, 2]
+                 (local indices of u and v; (-1, -1) for a row emptied by max_nodes), adj_ptr int64 [T + 1], nbr int32 [A] (per listed
+                 node the local indices of the distinct nodes of its row with an arc INTO it, ascending; self loops dropped), weight
+                 int32 [A] (copies of that arc in edge_index), z (int64 [T], [T, 2] or None); helpers .edge_index(), .batch(),
+                 .link(q).  With return_info .info is exact_subgraph_nodes' info.  A link's rows depend on the graph, the link,
+                 mask_target, node_label and max_dist only.  No CPU fallback."""
+        from . import subgraphs
+        return subgraphs.exact_subgraphs(self, links, num_nodes, edge_index, batch_size=batch_size, mask_target=mask_target,
+                                         max_nodes=max_nodes, node_label=node_label, max_dist=max_dist, return_info=return_info)
 
     def update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
         """the tables of build_hash_tables(num_nodes, old_edge_index) brought up to date with a changed edge list WITHOUT a rebuild: a

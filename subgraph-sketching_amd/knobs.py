@@ -73,3 +73,9 @@ EXACT_LDS_MAX_NODES = int(os.environ.get('SS_EXACT_LDS_NODES', '2048'))
 # persistent workgroups ("slots") of the large tier, each owning N distance bytes + 2N int32 of visit lists (26 MB at ogbl-citation2
 # size); fewer when a quarter of the free device memory does not hold them.  The arena is allocated zeroed once per (device, stream, N)
 EXACT_LARGE_SLOTS = int(os.environ.get('SS_EXACT_SLOTS', '256'))
+# exact_subgraphs (csrc/ss_subgraph.hip): the adjacency row of a listed node is the intersection of its sorted CSR row (deg arcs) with
+# the link's sorted id row (n nodes), walked from the shorter side.  A node with deg > SUBGRAPH_ADJ_SWITCH * n walks the id row and takes
+# two bounds in its CSR row per id (2 n log deg probes), every other node walks its arcs and searches the id row (deg log n probes): the
+# costs cross near deg = 2 n, and the CSR row's probes miss the caches where the id row's hit, hence 4.  0 = always the id row,
+# 2^31 - 1 = always the arcs (tests force both).  Results do not depend on it.
+SUBGRAPH_ADJ_SWITCH = int(os.environ.get('SS_SUBGRAPH_ADJ_SWITCH', '4'))

@@ -287,3 +287,27 @@ def masked_query_bytes(links, edge_links, mean_in_degree, P=128, p=8, h=2, two_h
     if h >= 3:
         per_edge += 2 * (two_hop_walks + d) * (R + 4) + 2 * d * 16
     return int(plain + classify + edge_links * per_edge)
+
+
+def subgraph_bytes(links, nodes, arcs, csr_arcs, node_label='drnl', offchip_nodes=0):
+    """algorithmic bytes of the two kernel families ElphHashes.exact_subgraphs adds to the node list (csrc/ss_subgraph.hip).
+    nodes: listed nodes T; arcs: emitted adjacency entries A; csr_arcs: the in-arcs of the listed nodes that the intersection walks
+    (sum over listed nodes of min(deg x, the probes of the id-row walk): for graphs without hubs the sum of the in-degrees);
+    offchip_nodes: nodes of the rows the label kernel keeps in its device workspace.
+      'adj_count'  per listed node its id (8), two CSR row pointer words (16) and 4 bytes written; 4 per walked in-arc.  The binary
+                   searches (the link of a node in rowptr, an arc's source in the id row) probe arrays that the same workgroup has
+                   just read: cache hits, not counted.  16 per link (its ids), once.
+      'adj_fill'   the same reads + two adj_ptr words per node (8 distinct) and 8 written per emitted arc (nbr + weight), 8 per link
+                   (roots)
+      'labels'     per side of the BFS: two adj_ptr words per expanded node (8 distinct) and 4 per arc; 8 (drnl) or 16 (de, de+) bytes
+                   of z per node, written once; an off-chip row also writes its 16 workspace bytes per node once and claims each
+                   node once per side with a 4-byte atomic.  'hop' / 'zo' / None run no kernel (a torch reduction over dist: 2 read,
+                   8 written per node)."""
+    count = 28 * nodes + 4 * csr_arcs + 16 * links
+    fill = 32 * nodes + 4 * csr_arcs + 8 * arcs + 24 * links
+    if node_label in ('drnl', 'de', 'de+'):
+        z = 8 if node_label == 'drnl' else 16
+        labels = 2 * (8 * nodes + 4 * arcs) + z * nodes + 24 * offchip_nodes + 24 * links
+    else:
+        labels = 0 if node_label is None else 10 * nodes
+    return {'adj_count': count, 'adj_fill': fill, 'labels': labels}
