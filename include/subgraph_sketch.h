@@ -512,6 +512,31 @@ int ss_exact_nodes_large(const ss_csr_graph *graph, const int64_t *links, int64_
                          const int64_t *rowptr, int64_t *ids, uint8_t *dist, void *workspace, size_t workspace_bytes, int32_t slots,
                          void *arena, size_t arena_bytes, void *stream);
 
+/* Per-hop sampled subgraph node lists: the node row of the reference's k_hop_subgraph with its sample_ratio / max_nodes_per_hop
+ * (src/datasets/seal.py:291-348), deterministic in a seed.  ONE joint walk from {u, v} over the in-arcs of the CSR (the target link is
+ * not removed; self loops and repeated arcs change nothing; n_self is not consulted):
+ *   visited = kept_0 = {u, v} (one root for u == v);  for hop = 1 .. h:
+ *     fringe = in-neighbours(kept_{hop-1}) - visited;  visited |= fringe (the WHOLE fringe: a rejected node never comes back);
+ *     F = |fringe|;  m = F for ratio_per_hop == 1.0, else (int64)(ratio_per_hop * (double)F);  max_nodes_per_hop > 0: m = min(m, it);
+ *     kept_hop = the m fringe nodes with the smallest (key, id);  stop when m == 0
+ *   key(x) = H(H(K + 0x9E3779B97F4A7C15 * hop) ^ (x + 1)),  K = H(seed ^ H(((u << 32) | v) + 1)),  H = the splitmix64 finaliser of
+ *   ss_minhash_init's node hash, all in wrapping 64-bit words, u and v after the negative-id wrap.
+ * The row of a link is the union of the kept, ascending by id and once each, with hop[x] = the hop x was kept at (0 for the roots): a
+ * function of (graph, u, v, h, max_nodes_per_hop, ratio_per_hop, seed) alone.  Passes, tiers, workspace, arena (all level bytes zero
+ * before and after every call) and stream as for ss_exact_nodes_pairs / ss_exact_nodes_large, with hop (uint8 [T]) for dist and one
+ * more array for both passes: state int32 [B], written by the count pass and read by the fill pass (bit 0: some hop of the link
+ * dropped a node; bit 1: the link is the slot tier's -- its VISITED set passed lds_max_nodes; counts[q] is the number of kept nodes).
+ * Return codes and argument checks as ss_exact_nodes_pairs / ss_exact_nodes_large, and SS_ERR_INVALID_ARG for max_nodes_per_hop < 0
+ * (0 = no cap), a ratio_per_hop outside (0, 1] or a seed of 2^63 or more, checked first. */
+int ss_sampled_nodes_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, int32_t max_nodes_per_hop,
+                           double ratio_per_hop, uint64_t seed, int32_t lds_max_nodes, int32_t *counts, int32_t *state,
+                           const int64_t *rowptr, int64_t *ids, uint8_t *hop, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int ss_sampled_nodes_large(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, int32_t max_nodes_per_hop,
+                           double ratio_per_hop, uint64_t seed, int32_t *counts, int32_t *state, const int64_t *rowptr, int64_t *ids,
+                           uint8_t *hop, void *workspace, size_t workspace_bytes, int32_t slots, void *arena, size_t arena_bytes,
+                           void *stream);
+
 /* out = A * x for a row-grouped CSR with fp32 values -- the node-feature propagation of
  * HashDataset._generate_sign_features (reference datasets/elph.py:87-110: gcn_norm, then torch_sparse.spmm = multiply
  * and scatter-add in edge order).  Every output element is accumulated by one lane in CSR order, product and sum rounded

@@ -136,6 +136,10 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_exact_nodes_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_uint32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
+    'ss_sampled_nodes_pairs': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_int32, c_double, c_uint64, c_int32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ss_sampled_nodes_large': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_int64, c_int32, c_int32, c_double, c_uint64, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p, c_size_t, c_void_p]),
     'ss_subgraph_adj': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_uint32, c_int32, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ss_subgraph_labels': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p,

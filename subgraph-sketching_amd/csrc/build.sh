@@ -5,14 +5,14 @@ set -e
 cd "$(dirname "$0")"
 OUT=../libsubgraph_sketch.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I ../../include $SS_EXTRA_FLAGS"
-UNITS="ss_init ss_digest ss_csr ss_propagate ss_first_hop ss_fused_hop ss_update ss_count ss_pairs ss_masked ss_topk ss_topk_head ss_rank ss_lsh ss_negatives ss_wedge ss_exact ss_exact_nodes ss_subgraph ss_heuristics ss_ppr ss_spmm ss_api ss_debug"
+UNITS="ss_init ss_digest ss_csr ss_propagate ss_first_hop ss_fused_hop ss_update ss_count ss_pairs ss_masked ss_topk ss_topk_head ss_rank ss_lsh ss_negatives ss_wedge ss_exact ss_exact_nodes ss_sampled_nodes ss_subgraph ss_heuristics ss_ppr ss_spmm ss_api ss_debug"
 OBJS=""
 PIDS=""
 mkdir -p build
 for f in $UNITS; do
   stale=0
   [ -f build/$f.o ] || stale=1
-  for dep in $f.hip ss_common.hpp ss_pair_math.hpp ss_topk_key.hpp ss_head.hpp ss_head_scan.hpp ss_feature_algebra.hpp ss_walks.hpp ss_hub.hpp ss_negatives.hpp ss_wedge.hpp ss_exact_bfs.hpp ../../include/subgraph_sketch.h ../../include/subgraph_sketch_debug.h build.sh; do
+  for dep in $f.hip ss_common.hpp ss_pair_math.hpp ss_topk_key.hpp ss_head.hpp ss_head_scan.hpp ss_feature_algebra.hpp ss_walks.hpp ss_hub.hpp ss_negatives.hpp ss_wedge.hpp ss_exact_bfs.hpp ss_sampled.hpp ../../include/subgraph_sketch.h ../../include/subgraph_sketch_debug.h build.sh; do
     [ -e $dep ] && [ $dep -nt build/$f.o ] && stale=1
   done
   if [ $stale = 1 ]; then

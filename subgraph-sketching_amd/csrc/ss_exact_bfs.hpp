@@ -1,6 +1,8 @@
 // ss_exact_bfs.hpp -- the two-sided BFS of one link, shared by the exact counts (ss_exact.hip) and the exact node lists
 // (ss_exact_nodes.hip): the on-chip tier's LDS hash table and the large tier's slot of device memory, each with the walk that fills it.
-// What a kernel does with the visited nodes afterwards (a histogram, a sorted list) is its own; see ss_exact.hip for the tiers.
+// What a kernel does with the visited nodes afterwards (a histogram, a sorted list) is its own; see ss_exact.hip for the tiers.  The two
+// ways a row is put in id order -- the on-chip sort and the ordered scan of a slot's bytes -- are here too, shared by the node lists
+// and the sampled node lists (ss_sampled_nodes.hip), which walks in its own way and uses the tables, the slots and these two.
 #pragma once
 #include "ss_common.hpp"
 
@@ -119,6 +121,27 @@ __device__ __forceinline__ bool exact_lds_bfs(ExactLds &s, const ss_csr_graph &g
     return ovf;
 }
 
+// ascending bitonic sort of sorted[0 .. P) in LDS, P a power of two (whole workgroup; the caller has passed a barrier since the array
+// was written, and every thread has passed one after the last exchange when this returns)
+__device__ __forceinline__ void lds_bitonic_sort(uint32_t *sorted, int P)
+{
+    const int t = threadIdx.x;
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < P; i += kExactThreads) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const uint32_t a = sorted[i], b = sorted[p];
+                    if ((a > b) == ((i & k) == 0)) {
+                        sorted[i] = b;
+                        sorted[p] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+}
+
 // ---- large tier -----------------------------------------------------------------------------------------------------------------
 // slot arena: uint32 dist[ceil(N / 4)] (one byte per node: bits 0-3 side u, 4-7 side v), int32 list_u[N], int32 list_v[N]
 __host__ __device__ __forceinline__ int64_t exact_dist_words(int64_t N) { return (N + 3) / 4; }
@@ -203,6 +226,64 @@ __device__ __forceinline__ void exact_slot_bfs(const ExactSlot &sl, const ss_csr
             hi = cnt[side];
         }
         __syncthreads();
+    }
+}
+
+constexpr int kScanWords = 4;                        // slot bytes as words (16 nodes) per thread and step of the ordered scan
+constexpr int kScanWaves = kExactThreads / kWave;
+
+// the ordered scan of a slot's bytes (whole workgroup): emit(place, id, byte) for every node with a non-zero byte, in id order -- place
+// counts them from 0 -- and every word is zero afterwards.  Thread t owns words [w0 + kScanWords * t, + kScanWords) of each step, so
+// ids ascend with (step, t, word, byte); a workgroup prefix sum over the non-zero counts gives the places.  wave_sum: the workgroup's
+// LDS; the caller has passed a barrier since its last use and since the last write of a byte
+template <class Emit>
+__device__ __forceinline__ void slot_ordered_scan(const ExactSlot &sl, int64_t N, int (*wave_sum)[kScanWaves], Emit emit)
+{
+    const int t = threadIdx.x;
+    const int64_t W = exact_dist_words(N);
+    const int wave = t / kWave, wl = t & (kWave - 1);
+    int64_t done = 0;
+    int buf = 0;
+    for (int64_t w0 = 0; w0 < W; w0 += kScanWords * kExactThreads, buf ^= 1) {
+        const int64_t w = w0 + kScanWords * t;
+        uint32_t word[kScanWords];
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < kScanWords; ++k) {
+            word[k] = w + k < W ? __hip_atomic_load(&sl.dist[w + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c += ((word[k] >> (8 * j)) & 0xFFu) != 0;
+        }
+        int inc = c;  // inclusive prefix sum within the wave
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int y = __shfl_up(inc, d);
+            if (wl >= d) inc += y;
+        }
+        if (wl == kWave - 1) wave_sum[buf][wave] = inc;
+        __syncthreads();  // (one barrier per step: the next step writes the other buffer)
+        int before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < kScanWaves; ++k) {
+            const int sum = wave_sum[buf][k];
+            before += k < wave ? sum : 0;
+            all += sum;
+        }
+        if (c) {
+            int64_t at = done + before + inc - c;
+#pragma unroll
+            for (int k = 0; k < kScanWords; ++k) {
+                if (word[k] == 0) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t b = (word[k] >> (8 * j)) & 0xFFu;
+                    if (b) emit(at, 4 * (w + k) + j, b);
+                    at += b != 0;
+                }
+                __hip_atomic_store(&sl.dist[w + k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all zero for the next pair
+            }
+        }
+        done += all;
     }
 }
 

@@ -97,20 +97,7 @@ __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g
             while (P < n) P <<= 1;
             for (int i = n + t; i < P; i += kExactThreads) sorted[i] = kEmpty;  // (no node id is 2^32 - 1: N < 2^31)
             __syncthreads();
-            for (int k = 2; k <= P; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int i = t; i < P; i += kExactThreads) {
-                        const int p = i ^ j;
-                        if (p > i) {
-                            const uint32_t a = sorted[i], b = sorted[p];
-                            if ((a > b) == ((i & k) == 0)) {
-                                sorted[i] = b;
-                                sorted[p] = a;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
+            lds_bitonic_sort(sorted, P);
             const int m = n < len ? n : (int)len;  // (n == len; a store never leaves the row)
             for (int i = t; i < m; i += kExactThreads) {
                 const uint32_t x = sorted[i];
@@ -134,8 +121,6 @@ __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g
 
 // ---- large tier -----------------------------------------------------------------------------------------------------------------
 constexpr int kNodesFillGrid = 256 * 3;                    // on-chip fill workgroups (3 per CU: 40.1 KiB of LDS each with the sort array)
-constexpr int kScanWords = 4;                              // distance words (16 nodes) per thread and step of the ordered scan
-constexpr int kScanWaves = kExactThreads / kWave;
 
 template <int H, bool FILL>
 __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph g, const int64_t *__restrict__ links, int64_t N,
@@ -189,56 +174,14 @@ __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph
             __syncthreads();
             continue;
         }
-        // the ordered scan: thread t owns words [w0 + kScanWords * t, + kScanWords) of each step, so ids ascend with (step, t, word, byte)
-        const int64_t W = exact_dist_words(N);
-        const int wave = t / kWave, wl = t & (kWave - 1);
-        int64_t done = 0;
-        int buf = 0;
-        for (int64_t w0 = 0; w0 < W; w0 += kScanWords * kExactThreads, buf ^= 1) {
-            const int64_t w = w0 + kScanWords * t;
-            uint32_t word[kScanWords];
-            int c = 0;
-#pragma unroll
-            for (int k = 0; k < kScanWords; ++k) {
-                word[k] = w + k < W ? __hip_atomic_load(&sl.dist[w + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) c += ((word[k] >> (8 * j)) & 0xFFu) != 0;
+        // the row holds exactly the non-zero bytes (a store never leaves it); the scan leaves them all zero for the next pair
+        slot_ordered_scan(sl, N, wave_sum, [&](int64_t at, int64_t x, uint32_t b) {
+            if (at < len) {
+                o.ids[row + at] = x;
+                o.dist[2 * (row + at)] = nodes_distance<H>(b & 0xFu);
+                o.dist[2 * (row + at) + 1] = nodes_distance<H>(b >> 4);
             }
-            int inc = c;  // inclusive prefix sum within the wave
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int y = __shfl_up(inc, d);
-                if (wl >= d) inc += y;
-            }
-            if (wl == kWave - 1) wave_sum[buf][wave] = inc;
-            __syncthreads();  // (one barrier per step: the next step writes the other buffer)
-            int before = 0, all = 0;
-#pragma unroll
-            for (int k = 0; k < kScanWaves; ++k) {
-                const int sum = wave_sum[buf][k];
-                before += k < wave ? sum : 0;
-                all += sum;
-            }
-            if (c) {
-                int64_t at = done + before + inc - c;
-#pragma unroll
-                for (int k = 0; k < kScanWords; ++k) {
-                    if (word[k] == 0) continue;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t b = (word[k] >> (8 * j)) & 0xFFu;
-                        if (b && at < len) {  // (the row holds exactly the non-zero bytes; a store never leaves it)
-                            o.ids[row + at] = 4 * (w + k) + j;
-                            o.dist[2 * (row + at)] = nodes_distance<H>(b & 0xFu);
-                            o.dist[2 * (row + at) + 1] = nodes_distance<H>(b >> 4);
-                        }
-                        at += b != 0;
-                    }
-                    __hip_atomic_store(&sl.dist[w + k], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all zero for the next pair
-                }
-            }
-            done += all;
-        }
+        });
         __syncthreads();
     }
 }

@@ -1028,8 +1028,41 @@ class ElphHashes(object):
         return exact_nodes.exact_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=batch_size, mask_target=mask_target,
                                                 max_nodes=max_nodes, return_info=return_info)
 
+    def sampled_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=11000000, max_nodes_per_hop=None, ratio_per_hop=1.0, seed=0,
+                               max_nodes=None, return_info=False):
+        """the node rows of the reference's SEAL path WITH its per-hop neighbour caps: k_hop_subgraph's sample_ratio and
+        max_nodes_per_hop (src/datasets/seal.py:291-348), restated deterministically and run for a whole batch of links on the GPU
+        (sampled_nodes.py, csrc/ss_sampled_nodes.hip).  Where exact_subgraph_nodes(max_nodes=...) EMPTIES the row of a
+        link near a hub, this keeps a uniform sample of every hop and expands only what it kept.  One joint walk from {u, v}, h =
+        max_hash_hops, over the in-arcs of edge_index (on a symmetric graph: the neighbours):
+            visited = kept_0 = {u, v} (u == v: one root);  for hop = 1 .. h:
+                fringe = in-neighbours(kept_{hop-1}) - visited;  visited |= fringe -- the WHOLE fringe: a node that is rejected never
+                    comes back at a later hop, as in the reference
+                F = |fringe|;  m = F if ratio_per_hop == 1.0 else int(ratio_per_hop * F);  with a cap m = min(m, max_nodes_per_hop)
+                kept_hop = the m fringe nodes with the smallest (key, id);  stop when m == 0
+            key(x) = hash_u64(hash_u64(K + 0x9E3779B97F4A7C15 * hop) ^ (x + 1)),  K = hash_u64(seed ^ hash_u64(((u << 32) | v) + 1)),
+            hash_u64 = the splitmix64 finaliser of the node hashes, 64-bit wrapping, u and v after the negative-id wrap
+        The target link is NOT removed during the walk (the reference walks the graph with it; removing it belongs to the adjacency,
+        exact_subgraphs(mask_target=True)).  The reference samples twice (ratio, then cap) with random.sample; a uniform sample of a
+        uniform sample is uniform, and so is one bottom-m selection by an independent key: the same law, one stage.
+        @param links, num_nodes, edge_index, batch_size: as exact_subgraph_nodes takes them (same checks, before any launch)
+        @param max_nodes_per_hop: None or an integer >= 1
+        @param ratio_per_hop: a real number in (0, 1]
+        @param seed: an integer in [0, 2^63)
+        @param max_nodes: None = no cap; otherwise a row longer than max_nodes is EMPTY and reported in info['truncated'].  With
+               max_nodes_per_hop a row never exceeds 2 + h * max_nodes_per_hop
+        @return: (rowptr int64 [L + 1], ids int64 [T], hop uint8 [T]) on links.device: row q ascending and unique, hop = the hop at
+                 which the node joined the walk (0 for the roots: the reference's `dists`).  A row is a function of (graph, u, v, h,
+                 max_nodes_per_hop, ratio_per_hop, seed) only: not of the link's position, batch_size, the kernel tier, the knobs or
+                 the other links; a link that appears twice gets the same row twice.  With return_info also {'truncated',
+                 'lds_links', 'large_links' (links whose VISITED set passed the on-chip table), 'sampled_links' (links where at least
+                 one hop dropped a node)}.  No CPU fallback."""
+        from . import sampled_nodes
+        return sampled_nodes.sampled_subgraph_nodes(self, links, num_nodes, edge_index, batch_size=batch_size, max_nodes_per_hop=max_nodes_per_hop,
+                                                    ratio_per_hop=ratio_per_hop, seed=seed, max_nodes=max_nodes, return_info=return_info)
+
     def exact_subgraphs(self, links, num_nodes, edge_index, batch_size=11000000, mask_target=True, max_nodes=None, node_label='drnl',
-                        max_dist=1000, return_info=False):
+                        max_dist=1000, return_info=False, *, max_nodes_per_hop=None, ratio_per_hop=1.0, seed=0):
         """the labelled enclosing subgraph of every link as one disjoint-union batch: the node rows of exact_subgraph_nodes, the
         adjacency they induce and the SEAL node labels computed INSIDE each subgraph -- the object the reference's SEAL path builds
         per link in Python (k_hop_subgraph + construct_pyg_graph + labelling_tricks.py, src/datasets/seal.py:291-389), here from HIP
@@ -1046,6 +1079,11 @@ class ElphHashes(object):
                u == v is outside the reference's domain and defined here: one root, nothing removed, d_u == d_v, 'drnl' gives the
                root 1
         @param max_dist: integer in [1, 2^20]
+        @param max_nodes_per_hop, ratio_per_hop, seed: (keyword only) as sampled_subgraph_nodes takes them.  With the defaults nothing
+               changes.  With a cap or a ratio < 1 the node rows are those of sampled_subgraph_nodes (the target link stays in the
+               WALK; mask_target still removes it from the adjacency) and the result is a subgraphs.SampledSubgraphs: hop uint8 [T] in
+               place of dist (dist is None), 'hop' and 'zo' read from it, everything else as below on those rows, info with
+               'sampled_links' too
         @return: subgraphs.ExactSubgraphs on links.device: rowptr / ids / dist (exactly exact_subgraph_nodes' result), roots int32 [L, 2]
                  (local indices of u and v; (-1, -1) for a row emptied by max_nodes), adj_ptr int64 [T + 1], nbr int32 [A] (per listed
                  node the local indices of the distinct nodes of its row with an arc INTO it, ascending; self loops dropped), weight
@@ -1054,7 +1092,8 @@ class ElphHashes(object):
                  mask_target, node_label and max_dist only.  No CPU fallback."""
         from . import subgraphs
         return subgraphs.exact_subgraphs(self, links, num_nodes, edge_index, batch_size=batch_size, mask_target=mask_target,
-                                         max_nodes=max_nodes, node_label=node_label, max_dist=max_dist, return_info=return_info)
+                                         max_nodes=max_nodes, node_label=node_label, max_dist=max_dist, return_info=return_info,
+                                         max_nodes_per_hop=max_nodes_per_hop, ratio_per_hop=ratio_per_hop, seed=seed)
 
     def update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
         """the tables of build_hash_tables(num_nodes, old_edge_index) brought up to date with a changed edge list WITHOUT a rebuild: a

@@ -311,3 +311,19 @@ def subgraph_bytes(links, nodes, arcs, csr_arcs, node_label='drnl', offchip_node
     else:
         labels = 0 if node_label is None else 10 * nodes
     return {'adj_count': count, 'adj_fill': fill, 'labels': labels}
+
+
+def sampled_nodes_bytes(links, kept, expanded, walked_arcs, num_nodes=0, slot_links=0, slot_visited=0, slot_selected=0, slot_kept=0):
+    """algorithmic bytes of the two passes of ElphHashes.sampled_subgraph_nodes (csrc/ss_sampled_nodes.hip).
+    kept: listed nodes T; expanded: the kept nodes of hops 0 .. h - 1 whose in-arcs a pass walks; walked_arcs: the sum of their
+    in-degrees (the measure of the walk: a fringe can be 1000 times what is kept, and every arc into it is read).  The on-chip tier
+    keeps visited, fringe and selection in LDS: beyond the walk it moves nothing.  The slot tier's links (slot_links of them, on a
+    graph of num_nodes nodes) add, per pass: slot_visited nodes reached for the first time (a 4-byte atomic on the level word and a
+    4-byte list entry each, and the same again to clear), slot_selected fringe nodes of the hops where a selection ran (read 9 times
+    as 4-byte ids: eight digit passes and the marking pass; the keys are recomputed, there is no key array) and slot_kept kept nodes
+    (a 4-byte atomic and a 4-byte list entry).
+      'count'  per link its ids (16) and counts + state written (8); per expanded node two CSR row pointer words (16); 4 per walked arc
+      'fill'   the same walk + two rowptr words (16) and the state (4) per link, 9 written per listed node (id + hop); a slot-tier link
+               scans its num_nodes level bytes once"""
+    walk = 16 * links + 16 * expanded + 4 * walked_arcs + 16 * slot_visited + 36 * slot_selected + 8 * slot_kept
+    return {'count': walk + 8 * links, 'fill': walk + 20 * links + 9 * kept + num_nodes * slot_links}

@@ -3,6 +3,9 @@ with the induced adjacency (local indices, arc multiplicities) and the SEAL node
 reference builds per link in Python (src/datasets/seal.py:291-389, src/labelling_tricks.py) as one disjoint-union batch.
 Design: DESIGN 3.18; numpy restatement: tests/subgraph_restatement.py.
 
+With max_nodes_per_hop or ratio_per_hop < 1 the node rows are those of the sampled walk instead (sampled_nodes.sampled_subgraph_nodes,
+DESIGN 3.19: the reference's per-hop neighbour caps) and the result is a SampledSubgraphs; the adjacency and the labels are the same calls.
+
 Host side only: argument checks, the node rows (exact_nodes.exact_subgraph_nodes, unchanged), the CSR with sorted rows (a copy of the
 engine's cached CSR columns, sorted once per edge_index), the count / fill walk of the adjacency with ONE host read between them (the
 number of arcs, together with the workspace nodes of the rows labelled off chip) and the label launch."""
@@ -10,7 +13,7 @@ import weakref
 
 import torch
 
-from . import _native, exact, exact_nodes, knobs
+from . import _native, exact, exact_nodes, knobs, sampled_nodes
 from ._runtime import _compute_device, _ptr, _stream, _Span
 
 NODE_LABELS = ('drnl', 'de', 'de+', 'hop', 'zo', None)
@@ -27,6 +30,8 @@ class ExactSubgraphs(object):
         edge_index holds (the edge_weight SEAL's csr_matrix sums)
     z      the node labels: int64 [T] ('drnl', 'hop', 'zo'), int64 [T, 2] ('de', 'de+') or None
     info   with return_info: the node list's {'truncated', 'lds_links', 'large_links'}"""
+
+    _per_node = 'dist'  # the field that holds what the node walk says of every listed node
 
     def __init__(self, rowptr, ids, dist, roots, adj_ptr, nbr, weight, z, node_label, info=None):
         self.rowptr, self.ids, self.dist, self.roots = rowptr, ids, dist, roots
@@ -51,17 +56,29 @@ class ExactSubgraphs(object):
         return torch.stack([source, target])
 
     def link(self, q):
-        """the views of link q: dict(ids, dist, roots, adj_ptr (local offsets, starting at 0), nbr, weight, z)"""
+        """the views of link q: dict(ids, dist (SampledSubgraphs: hop), roots, adj_ptr (local offsets, starting at 0), nbr, weight, z)"""
         a, b = int(self.rowptr[q]), int(self.rowptr[q + 1])
         e0, e1 = int(self.adj_ptr[a]), int(self.adj_ptr[b])
-        return {'ids': self.ids[a:b], 'dist': self.dist[a:b], 'roots': self.roots[q], 'adj_ptr': self.adj_ptr[a:b + 1] - e0,
+        return {'ids': self.ids[a:b], self._per_node: getattr(self, self._per_node)[a:b], 'roots': self.roots[q], 'adj_ptr': self.adj_ptr[a:b + 1] - e0,
                 'nbr': self.nbr[e0:e1], 'weight': self.weight[e0:e1], 'z': None if self.z is None else self.z[a:b]}
 
     def to(self, device):
         move = lambda t: t.to(device) if torch.is_tensor(t) else t
         info = None if self.info is None else {k: move(x) for k, x in self.info.items()}
-        return ExactSubgraphs(*[move(getattr(self, k)) for k in ('rowptr', 'ids', 'dist', 'roots', 'adj_ptr', 'nbr', 'weight', 'z')],
-                              self.node_label, info)
+        return type(self)(*[move(getattr(self, k)) for k in ('rowptr', 'ids', self._per_node, 'roots', 'adj_ptr', 'nbr', 'weight', 'z')],
+                          self.node_label, info)
+
+
+class SampledSubgraphs(ExactSubgraphs):
+    """the batch of exact_subgraphs(max_nodes_per_hop=..., ratio_per_hop=...): the node rows of sampled_subgraph_nodes, and on them what
+    ExactSubgraphs holds.  hop uint8 [T] (the hop at which the node joined the walk, 0 for the roots: the reference's `dists`) takes the
+    place of dist, which is None; link(q) returns 'hop'; info has 'sampled_links' too"""
+
+    _per_node = 'hop'
+
+    def __init__(self, rowptr, ids, hop, roots, adj_ptr, nbr, weight, z, node_label, info=None):
+        ExactSubgraphs.__init__(self, rowptr, ids, None, roots, adj_ptr, nbr, weight, z, node_label, info)
+        self.hop = hop
 
 
 class _SortedRowsCache(object):
@@ -96,7 +113,7 @@ def _label_arguments(node_label, max_dist):
 
 
 def exact_subgraphs(eh, links, num_nodes, edge_index, batch_size=11000000, mask_target=True, max_nodes=None, node_label='drnl',
-                    max_dist=1000, return_info=False, stats=None):
+                    max_dist=1000, return_info=False, stats=None, *, max_nodes_per_hop=None, ratio_per_hop=1.0, seed=0):
     """see ElphHashes.exact_subgraphs.  stats (measurement hook, tools/probe_subgraphs.py): a dict that receives the milliseconds of
     the node list's passes and of the adjacency count, the offsets with the host read, the adjacency fill and the labels"""
     h = eh.max_hops
@@ -104,19 +121,37 @@ def exact_subgraphs(eh, links, num_nodes, edge_index, batch_size=11000000, mask_
         raise ValueError(f'mask_target of the exact query is a bool (the links are masked in the edge_index given), got {type(mask_target).__name__}')
     exact_nodes._cap(max_nodes)
     node_label, max_dist = _label_arguments(node_label, max_dist)
+    cap_hop, ratio, seed = sampled_nodes.sampling_arguments(max_nodes_per_hop, ratio_per_hop, seed)
+    sampled = cap_hop > 0 or ratio < 1.0
     lk, ei, N, batch_size = exact.check_arguments(h, links, num_nodes, edge_index, batch_size)
     home, L = lk.device, lk.size(0)
+    if sampled:  # the node rows of the sampled walk (the target link stays in the walk: removing it belongs to the adjacency)
+        make = SampledSubgraphs
+        node_rows = lambda lk_, st: sampled_nodes.sampled_subgraph_nodes(eh, lk_, N, ei, batch_size, max_nodes_per_hop, ratio, seed, max_nodes,
+                                                                         True, stats=st)
+    else:  # the node list's own call (same kernels, same bits)
+        make = ExactSubgraphs
+        node_rows = lambda lk_, st: exact_nodes.exact_subgraph_nodes(eh, lk_, N, ei, batch_size, mask_target, max_nodes, True, stats=st)
     two = node_label in ('de', 'de+')
     if L == 0:
-        rowptr, ids, dist, info = exact_nodes.exact_subgraph_nodes(eh, lk, N, ei, batch_size, mask_target, max_nodes, True)
+        rowptr, ids, per_node, info = node_rows(lk, None)
         z = None if node_label is None else torch.empty((0, 2) if two else (0,), dtype=torch.int64, device=home)
-        return ExactSubgraphs(rowptr, ids, dist, torch.empty((0, 2), dtype=torch.int32, device=home), torch.zeros((1,), dtype=torch.int64, device=home),
-                              torch.empty((0,), dtype=torch.int32, device=home), torch.empty((0,), dtype=torch.int32, device=home), z,
-                              node_label, info if return_info else None)
+        return make(rowptr, ids, per_node, torch.empty((0, 2), dtype=torch.int32, device=home), torch.zeros((1,), dtype=torch.int64, device=home),
+                    torch.empty((0,), dtype=torch.int32, device=home), torch.empty((0,), dtype=torch.int32, device=home), z,
+                    node_label, info if return_info else None)
     device = _compute_device(lk, ei)
     lk = lk.to(device=device, dtype=torch.int64).contiguous()
-    # the node rows: the node list's own call (same kernels, same bits); it fills the engine's CSR cache for `ei`
-    rowptr, ids, dist, info = exact_nodes.exact_subgraph_nodes(eh, lk, N, ei, batch_size, mask_target, max_nodes, True, stats=stats)
+    rowptr, ids, per_node, info = node_rows(lk, stats)  # (fills the engine's CSR cache for `ei`)
+    out = make(rowptr, ids, per_node, *_adjacency_and_labels(eh, lk, ei, N, device, rowptr, ids, per_node, mask_target, node_label, max_dist, stats),
+               node_label, info if return_info else None)
+    return out.to(home) if home != device else out
+
+
+def _adjacency_and_labels(eh, lk, ei, N, device, rowptr, ids, per_node, mask_target, node_label, max_dist, stats):
+    """-> (roots, adj_ptr, nbr, weight, z) of node rows on the compute device, whichever walk made them: the induced adjacency (count,
+    ONE host read, fill) and the labels.  per_node: dist uint8 [T, 2] or hop uint8 [T], what 'hop' and 'zo' are read from"""
+    L = lk.size(0)
+    two = node_label in ('de', 'de+')
     csr = eh._csr_cache.get(ei, N, device)
     cache = eh.__dict__.get('_sorted_rows_cache')
     if cache is None:
@@ -164,7 +199,7 @@ def exact_subgraphs(eh, links, num_nodes, edge_index, batch_size=11000000, mask_
     elif node_label is None:
         z = None
     else:  # the two labels that are functions of the ball distances alone
-        z = dist.min(dim=1).values.to(torch.int64)
+        z = (per_node.min(dim=1).values if per_node.dim() == 2 else per_node).to(torch.int64)
         if node_label == 'zo':
             z = (z == 0).to(torch.int64)
     nbr, weight = nbr[:A], weight[:A]
@@ -174,5 +209,4 @@ def exact_subgraphs(eh, links, num_nodes, edge_index, batch_size=11000000, mask_
         for k, name in enumerate(('adj_count_ms', 'adj_ptr_ms', 'adj_fill_ms', 'labels_ms')):
             stats[name] = stats.get(name, 0.0) + ev[k].elapsed_time(ev[k + 1])
         stats['arcs'] = A
-    out = ExactSubgraphs(rowptr, ids, dist, roots, adj_ptr, nbr, weight, z, node_label, info if return_info else None)
-    return out.to(home) if home != device else out
+    return roots, adj_ptr, nbr, weight, z
