@@ -674,6 +674,47 @@ int ss_subgraph_labels(const int64_t *rowptr, int64_t B, const int32_t *roots, c
                        int32_t label_mode, int64_t max_dist, int32_t lds_max_nodes, const int64_t *ws_ptr, int32_t *workspace, int64_t *z,
                        void *stream);
 
+/* Connected components of an edge_index and the induced subgraph of a node set: what the reference does on the host with a Python set
+ * walk that scans `row` once per visited node and a per-edge `i in lcc` test (O(N E) interpreter work).  src / dst: the two rows of the
+ * edge list (device int64 [E], torch-style negative ids wrapped; an edge with an id outside [-N, N) sets err_flag (nullable) and is
+ * ignored).  An edge counts in both directions: the WEAK components of a directed list.  N < 2^31, E < 2^31.
+ *   ss_components_labels  label[x] (int32 [N]) = the smallest node id of x's component, by a lock-free union-find over the edges
+ *                         (parent: int32 [N] scratch; larger root hooked under the smaller by atomicCAS, path halving by atomicMin;
+ *                         no lane waits on another) and a flattening launch -- get_component, src/lcc.py:34-44.
+ *   ss_components_sizes   size[r] (int32 [N], cleared by the call) = the nodes labelled r, one aggregated atomic per wavefront and
+ *                         label; block_roots[b] (int32) = the roots (label[x] == x) among the nodes [b, b + 1) * SS_COMPONENTS_CHUNK.
+ *   ss_components_roots   block_incl: int64, the caller's INCLUSIVE cumulative sum of block_roots.  roots / sizes (int64 [C]): the
+ *                         roots ascending and their sizes; *best (uint64, preset to 0) = max over the roots of
+ *                         (size << 32) | (0xFFFFFFFF - root): the largest component, ties to the smallest root, which is what
+ *                         np.argmax picks from the discovery order of get_largest_connected_component, src/lcc.py:7-15.
+ *   ss_components_same    out[q] (uint8 [L]) = whether the two nodes of links[q] (int64 [L, 2], negative ids wrapped) carry one label;
+ *                         an id outside [-N, N) sets err_flag and gives 0.
+ *   ss_induced_select     the node set as mask (uint8 [N], non-zero = kept), or (mask null) as the component whose root is in *best
+ *                         (label and best as above).  Count pass (block_incl null): block_count[b] = the kept nodes of chunk b.  Fill
+ *                         pass (block_incl = the inclusive cumulative sum of those counts): nodes (int64) = the kept ids ascending,
+ *                         mapper[x] (int64 [N]) = the position of x in nodes, -1 outside -- get_node_mapper, src/lcc.py:18-24.
+ *   ss_induced_mapper     the node set as a list: mapper[x] = -1 everywhere, then mapper[nodes[i]] = i, i < n (negative ids wrapped;
+ *                         an id outside [-N, N) sets err_flag and is skipped; a node listed twice sets dup_flag).
+ *   ss_induced_edges      the edges with mapper >= 0 at both ends.  Count pass (block_incl null): block_count[b] = the kept edges of
+ *                         chunk b.  Fill pass: out_src / out_dst (int64 [E']) = mapper of the two ends, edge_ids (int64 [E']) = the
+ *                         position in the input, all in the input's order -- remap_edges, src/lcc.py:27-32, over the filter of
+ *                         use_lcc, src/data.py:241-249.
+ * Order inside every compacted output comes from ballot ranks and the caller's cumulative sum, never from an atomic.  Argument errors
+ * (SS_ERR_INVALID_ARG: a size out of range, a null pointer with a non-zero count) are detected before any launch; nothing to do (N == 0;
+ * ss_induced_edges: E == 0; ss_components_same: L == 0): SS_OK, no launch. */
+#define SS_COMPONENTS_CHUNK 2048 /* consecutive items per workgroup of the count / fill passes: the length of a block_* array is ceil(n / this) */
+int ss_components_labels(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int32_t *parent, int32_t *label, int32_t *err_flag,
+                         void *stream);
+int ss_components_sizes(const int32_t *label, int64_t N, int32_t *size, int32_t *block_roots, void *stream);
+int ss_components_roots(const int32_t *label, const int32_t *size, int64_t N, const int64_t *block_incl, int64_t *roots, int64_t *sizes,
+                        uint64_t *best, void *stream);
+int ss_components_same(const int32_t *label, int64_t N, const int64_t *links, int64_t L, uint8_t *out, int32_t *err_flag, void *stream);
+int ss_induced_select(const uint8_t *mask, const int32_t *label, const uint64_t *best, int64_t N, const int64_t *block_incl,
+                      int32_t *block_count, int64_t *nodes, int64_t *mapper, void *stream);
+int ss_induced_mapper(const int64_t *nodes, int64_t n, int64_t N, int64_t *mapper, int32_t *err_flag, int32_t *dup_flag, void *stream);
+int ss_induced_edges(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, const int64_t *mapper, const int64_t *block_incl,
+                     int32_t *block_count, int64_t *out_src, int64_t *out_dst, int64_t *edge_ids, int32_t *err_flag, void *stream);
+
 /* Measurement-only entry points (launch-duration probes used by bench.py and tools/) are declared in
  * subgraph_sketch_debug.h; they are not part of the drop-in boundary. */
 

@@ -10,7 +10,8 @@ from .head import StructureHead
 from .negatives import NegativeSampler, sample_negatives
 from .wedge import WedgeGraph
 from .subgraphs import ExactSubgraphs
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs
+from .components import Components, InducedSubgraph, connected_components, induced_subgraph, largest_component_subgraph
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs, components
 
-__all__ = ['LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
+__all__ = ['components', 'Components', 'InducedSubgraph', 'connected_components', 'induced_subgraph', 'largest_component_subgraph','LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
            'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives', 'wedge', 'WedgeGraph', 'subgraphs', 'ExactSubgraphs']

@@ -55,6 +55,7 @@ NEG_MODES = {'uniform': 0, 'same_source': 1, 'wedge': 2}  # SS_NEG_*
 NEG_MAX_TRIES = 64  # SS_NEG_MAX_TRIES
 SUBGRAPH_LABELS = {'drnl': 0, 'de': 1, 'de+': 2}  # SS_SUBGRAPH_LABEL_*: the labels ss_subgraph_labels computes
 SUBGRAPH_MAX_DIST = 1 << 20  # SS_SUBGRAPH_MAX_DIST
+COMPONENTS_CHUNK = 2048  # SS_COMPONENTS_CHUNK: items per workgroup of the count / fill passes of ss_components_* / ss_induced_*
 WEDGE_MAX_SLOTS, WEDGE_MAX_SLICES = 4096, 64  # SS_WEDGE_MAX_SLOTS; the slices ss_wedge_emit takes at most
 MEGA_SLICE, MEGA_SLOT_BYTES, CSR_FINGERPRINT_BYTES, MAX_MIRRORS = 1024, 1280, 8448, 7  # SS_MEGA_SLICE / SS_MEGA_SLOT_BYTES of include/subgraph_sketch.h
 
@@ -144,6 +145,14 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ss_subgraph_labels': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    'ss_components_labels': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_components_sizes': (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'ss_components_roots': (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_components_same': (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'ss_induced_select': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_induced_mapper': (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ss_induced_edges': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     'ss_update_workspace_bytes': (c_size_t, [c_int64, c_int32]),
     'ss_update_mark': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
