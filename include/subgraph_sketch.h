@@ -83,7 +83,7 @@ typedef struct ss_csr_graph {
     int64_t n_self_loops;             /* rows i < n_self_loops also receive their own row (implicit self loop)  */
     const int64_t *n_self_loops_dev;  /* device int64 (nullable): overrides n_self_loops, read by the kernels   */
     int32_t hub_threshold;            /* rows with more than this many in-edges are "hub rows" ...              */
-    int32_t reserved;
+    int32_t reserved;                 /* flags: SS_GRAPH_* bits below (0: none)                                 */
     const int32_t *hub_rows;          /* ... listed here (device int32[*hub_count], nullable) and processed by  */
     const int32_t *hub_count;         /* a 16-wave cooperative kernel instead of a single wavefront             */
     const int32_t *mega_rows;         /* device int32[4 * max]: {row, first_slice, n_slices, done} per "mega row" */
@@ -115,8 +115,22 @@ typedef struct ss_csr_graph {
     int32_t *hub_report;
     const int32_t *report_hub_count;
     const int32_t *report_mega_count;
+    /* Symmetry word (nullable): the device int32 ss_csr_build_symmetric left for THIS adjacency -- 1: for every stored edge j -> i */
+    /* the edge i -> j is stored as often.  With SS_GRAPH_HOP_TABLES the table-hop row kernels then leave out the implicit self row  */
+    /* of every row that has an in-edge (see SS_GRAPH_HOP_TABLES).                                                                  */
+    const int32_t *symmetric_dev;
 } ss_csr_graph;
 #define SS_MAX_MIRRORS 7
+/* ss_csr_graph.reserved (the flags word) bit 0, the caller's promise about ONE call of ss_propagate: the input tables of this call are hop-(k-1) tables,
+ * k - 1 >= 1, of this same graph, built with these same implicit self loops (n_self_loops_dev = the max(edge_index) + 1 ss_csr_build
+ * left: every node that occurs in an edge has one).  On a symmetric graph (*symmetric_dev != 0) the own row of a node with a
+ * neighbour then aggregates a subset of what its neighbours' rows aggregate -- each neighbour m is in its own row through m's self
+ * loop, the node itself is in every neighbour's row by symmetry -- and min / max are idempotent: the regular-row paths skip the
+ * gather of the own row, bit-identical results, N fewer row gathers per hop.  Never true of hop-0 inputs (rows that are functions of
+ * the node id alone) or of arbitrary tensors; without the bit, without the word or with n_self_loops_dev == NULL nothing changes.
+ * ss_fused_hop_stage, whose table hops read the hop-1 tables it has just built, applies the rule on its own.  SS_SELF_SKIP=0 in
+ * the environment (read at every launch) turns it off everywhere. */
+#define SS_GRAPH_HOP_TABLES 1
 
 /* CSR-by-destination of an edge list.  Replaces the message materialisation of
  * torch_geometric MessagePassing.propagate as used by hashing.py:34,44 (flow source -> target).
@@ -140,6 +154,15 @@ int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, i
                  int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
                  int32_t *mega_rows, int32_t *mega_count,
                  int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
+/* ss_csr_build (fingerprint == NULL) or ss_csr_build_cached (fingerprint given) with one more output: *symmetric_out (device int32,
+ * nullable) <- 1 iff the edge MULTISET is symmetric (as many copies of j -> i as of i -> j; self edges count for nothing) and no id was
+ * out of range, else 0; 0 for E == 0.  Decided on the device by the build's own launches from two independent 64-bit sums over
+ * the edges (a false 1 needs both to cancel: the 128-bit kind of content fingerprint ss_csr_build_cached rests on); a cached
+ * build that finds the content unchanged leaves the word of the build it keeps.  For ss_csr_graph.symmetric_dev. */
+int ss_csr_build_symmetric(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
+                           int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
+                           int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                           void *fingerprint, int32_t *symmetric_out, void *stream);
 /* Failure of a build that was launched (every entry point that runs the builder: ss_csr_build, ss_csr_build_cached,
  * ss_group_links_by_source, ss_csr_group_ids).  Buckets too dense for one workgroup are worked off in shares by several workgroups of
  * the finish launch; the one cross-workgroup wait of that protocol is bounded (~2 s: it can only end late when the process is

@@ -33,7 +33,12 @@ class CsrGraphStruct(ctypes.Structure):
                 ('hub_rows', c_void_p), ('hub_count', c_void_p), ('mega_rows', c_void_p), ('mega_count', c_void_p),
                 ('mega_scratch', c_void_p), ('row_begin', c_int64), ('row_end', c_int64),
                 ('n_mirrors', c_int32), ('reserved2', c_int32), ('mirror_mh', c_void_p * 7), ('mirror_hll', c_void_p * 7),
-                ('mirror_cards', c_void_p * 7), ('hub_report', c_void_p), ('report_hub_count', c_void_p), ('report_mega_count', c_void_p)]
+                ('mirror_cards', c_void_p * 7), ('hub_report', c_void_p), ('report_hub_count', c_void_p), ('report_mega_count', c_void_p),
+                ('symmetric_dev', c_void_p)]
+    # (`reserved` is the flags word: GRAPH_HOP_TABLES below)
+
+
+GRAPH_HOP_TABLES = 1  # SS_GRAPH_HOP_TABLES of include/subgraph_sketch.h
 
 
 class PprGraphStruct(ctypes.Structure):
@@ -71,6 +76,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ss_csr_build_cached': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'ss_csr_build_symmetric': (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     'ss_propagate': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                c_int32, c_void_p, c_int64, POINTER(HllParams), c_void_p]),
     'ss_minhash_hop_rows': (c_int32, [POINTER(CsrGraphStruct), c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),

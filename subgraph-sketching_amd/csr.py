@@ -35,11 +35,15 @@ class CsrGraph(object):
         self.fingerprint = None      # device buffer of ss_csr_build_cached (None: never reused)
         self.hub_report = None       # pinned host int32 the first-hop kernels report this graph's hub + mega row count into
         self.use_inferred_self_loops = False
+        # device int32[1] of ss_csr_build_symmetric: 1 iff every stored edge j -> i has its reverse stored as often (None: not asked)
+        self.symmetric = None
 
-    def struct(self, rows=None, mirrors=None):
+    def struct(self, rows=None, mirrors=None, hop_tables=False):
         """rows = (begin, end): only those destination rows are computed (multi-GPU destination-range sharding).
         mirrors = (mh_ptrs, hll_ptrs, cards_ptrs): lists of device addresses (0 / None = absent) of the OTHER ranks' tables that
-        receive every finished row as well (peer-write build, dist.PeerShard)"""
+        receive every finished row as well (peer-write build, dist.PeerShard)
+        hop_tables: the caller's promise that the input tables of the call this struct is for are hop-(k-1) tables, k - 1 >= 1, of
+        this graph with these self loops (SS_GRAPH_HOP_TABLES: on a symmetric graph the regular rows skip their own row)"""
         begin, end = (0, 0) if rows is None else rows
         if rows is not None and end == 0:  # (0, 0) would mean "all rows" to the library: express the empty range at N
             begin = end = self.num_nodes
@@ -58,7 +62,8 @@ class CsrGraph(object):
         return _native.CsrGraphStruct(**extra, rowptr=self.rowptr.data_ptr(), col=self.col.data_ptr(), num_nodes=self.num_nodes,
                                       n_self_loops=0,
                                       n_self_loops_dev=self.n_self_dev.data_ptr() if self.use_inferred_self_loops else None,
-                                      hub_threshold=self.hub_threshold, reserved=0,
+                                      hub_threshold=self.hub_threshold, reserved=_native.GRAPH_HOP_TABLES if hop_tables else 0,
+                                      symmetric_dev=self.symmetric.data_ptr() if self.symmetric is not None else None,
                                       hub_rows=self.hub_rows.data_ptr() if hubs else None,
                                       hub_count=self.hub_count.data_ptr() if hubs else None,
                                       mega_rows=self.mega_rows.data_ptr() if mega else None,
@@ -81,10 +86,11 @@ def _rebuild_csr_if_changed(csr, src, dst, err_flag):
     ws_bytes = lib.ss_csr_workspace_bytes(N, E)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     with _Span('csr_build', device):
-        _native.check(lib.ss_csr_build_cached(_ptr(src), _ptr(dst), E, N, _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.n_self_dev),
-                                              csr.hub_threshold, _ptr(csr.hub_rows), _ptr(csr.hub_count), _ptr(csr.mega_rows),
-                                              _ptr(csr.mega_count), _ptr(err_flag), _ptr(ws), ws_bytes, _ptr(csr.fingerprint),
-                                              _stream(device)), 'ss_csr_build_cached')
+        # (content unchanged: every kernel exits and the symmetry word of the build that is kept stays)
+        _native.check(lib.ss_csr_build_symmetric(_ptr(src), _ptr(dst), E, N, _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.n_self_dev),
+                                                 csr.hub_threshold, _ptr(csr.hub_rows), _ptr(csr.hub_count), _ptr(csr.mega_rows),
+                                                 _ptr(csr.mega_count), _ptr(err_flag), _ptr(ws), ws_bytes, _ptr(csr.fingerprint),
+                                                 _ptr(csr.symmetric), _stream(device)), 'ss_csr_build_cached')
     return csr
 
 
@@ -109,12 +115,14 @@ def build_csr(edge_index, num_nodes, device, check=True, hub_threshold=None, err
         return _rebuild_csr_if_changed(reuse, src, dst, err_flag)
     rowptr = torch.empty(num_nodes + 1, dtype=torch.int64, device=device)
     col = torch.empty(max(E, 1), dtype=torch.int32, device=device)
-    # one small block of device counters, all cleared by the kernels: int64 n_self | int32 hub rows, error | int32 mega rows, slices
-    flags = torch.empty(3, dtype=torch.int64, device=device)
+    # one small block of device counters, all cleared by the kernels: int64 n_self | int32 hub rows, error | int32 mega rows, slices |
+    # int32 symmetric, unused
+    flags = torch.empty(4, dtype=torch.int64, device=device)
     flags32 = flags.view(torch.int32)
     n_self_dev = flags[0:1]
     hub_count = flags32[2:3]
     mega_count = flags32[4:6]
+    symmetric = flags32[6:7]
     # strict mode reads its own flag together with the counters below; a non-strict build passes NO flag (a shared one
     # would stay set and make the next strict call raise for valid inputs)
     if err_flag is not None:
@@ -138,17 +146,15 @@ def build_csr(edge_index, num_nodes, device, check=True, hub_threshold=None, err
     if fingerprint and not check and E > 0 and num_nodes > 0:
         fp = torch.zeros(_native.CSR_FINGERPRINT_BYTES, dtype=torch.uint8, device=device)
     with _Span('csr_build', device):
-        if fp is not None:
-            _native.check(lib.ss_csr_build_cached(_ptr(src), _ptr(dst), E, num_nodes, _ptr(rowptr), _ptr(col), _ptr(n_self_dev),
-                                                  hub_threshold, _ptr(hub_rows), _ptr(hub_count), _ptr(mega_rows), _ptr(mega_count),
-                                                  _ptr(err), _ptr(ws), ws_bytes, _ptr(fp), _stream(device)), 'ss_csr_build_cached')
-        else:
-            _native.check(lib.ss_csr_build(_ptr(src), _ptr(dst), E, num_nodes, _ptr(rowptr), _ptr(col), _ptr(n_self_dev),
-                                           hub_threshold, _ptr(hub_rows), _ptr(hub_count), _ptr(mega_rows), _ptr(mega_count), _ptr(err),
-                                           _ptr(ws), ws_bytes, _stream(device)), 'ss_csr_build')
+        # (fp None: the plain build; either way the level-0 pass also decides whether the edge list is symmetric)
+        _native.check(lib.ss_csr_build_symmetric(_ptr(src), _ptr(dst), E, num_nodes, _ptr(rowptr), _ptr(col), _ptr(n_self_dev),
+                                                 hub_threshold, _ptr(hub_rows), _ptr(hub_count), _ptr(mega_rows), _ptr(mega_count),
+                                                 _ptr(err), _ptr(ws), ws_bytes, _ptr(fp), _ptr(symmetric), _stream(device)),
+                      'ss_csr_build_cached' if fp is not None else 'ss_csr_build')
     csr = CsrGraph(rowptr, col, num_nodes, n_self_dev, _error_flag(device), hub_rows, hub_count, hub_threshold,
                    mega=(mega_rows, mega_count, mega_scratch))
     csr.num_edges = E
+    csr.symmetric = symmetric
     csr.fingerprint = fp  # a later build_csr(..., reuse=csr) compares contents with these sums
     if check:
         # the one synchronising read of strict mode brings the hub / mega row counts along: a graph without such rows

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "subgraph_sketch.h"
 #include "subgraph_sketch_debug.h"
 
@@ -397,9 +398,26 @@ struct GraphArgs {  // device-side view of ss_csr_graph
     Mirrors mir = {};
     int32_t *hub_report = nullptr;  // ss_csr_graph.hub_report and the two device counters it is formed from
     const int32_t *report_hub_count = nullptr, *report_mega_count = nullptr;
+    // non-null: the regular rows of a table hop leave out their implicit self row when *skip_self != 0 and the row has an in-edge
+    // (ss_csr_graph.symmetric_dev under SS_GRAPH_HOP_TABLES, see self_skip_word)
+    const int32_t *skip_self = nullptr;
     __host__ __device__ int64_t rows() const { return row1 - row0; }
     __device__ bool owns(int64_t i) const { return i >= row0 && i < row1; }
 };
+
+// The symmetry word a table-hop launch may act on, or nullptr.  `promised`: the launch's input tables are hop-(k-1) tables, k - 1 >= 1,
+// of this graph with these self loops (SS_GRAPH_HOP_TABLES, or a stage that has just built them).  The self loops must be the inferred
+// ones (max(edge_index) + 1 on the device: every node of an edge has one).  SS_SELF_SKIP=0, read at every launch: never.
+inline const int32_t *self_skip_word(const ss_csr_graph &g, bool promised)
+{
+    if (!promised || !g.symmetric_dev || !g.n_self_loops_dev) return nullptr;
+    const char *env = getenv("SS_SELF_SKIP");
+    return (env && env[0] == '0' && env[1] == 0) ? nullptr : g.symmetric_dev;
+}
+
+// neighbours a regular row of a table hop folds: its in-edges and, as neighbour `deg`, its own row when i < n_self -- unless `skip`
+// (wave-uniform: *GraphArgs.skip_self) says the graph is symmetric and the row has an in-edge whose row covers it already
+__device__ __forceinline__ int table_hop_total(int deg, bool self, bool skip) { return deg + ((self && !(skip && deg > 0)) ? 1 : 0); }
 
 inline GraphArgs to_args(const ss_csr_graph &g)
 {
@@ -411,6 +429,7 @@ inline GraphArgs to_args(const ss_csr_graph &g)
     a.hub_report = g.report_hub_count ? g.hub_report : nullptr;
     a.report_hub_count = g.report_hub_count;
     a.report_mega_count = g.report_mega_count;
+    a.skip_self = self_skip_word(g, (g.reserved & SS_GRAPH_HOP_TABLES) != 0);
     a.mir.n = g.n_mirrors > 0 && g.n_mirrors <= SS_MAX_MIRRORS ? g.n_mirrors : 0;
     for (int m = 0; m < a.mir.n; ++m) {
         a.mir.mh[m] = g.mirror_mh[m];

@@ -234,6 +234,26 @@ __device__ unsigned long long csr_phase_ticks[16];
 // to node 0 (the query kernel itself reports them and writes their NaN rows: nothing may be dropped here), the "source" is the
 // pair's index.  The same with key_stride = 1 groups the entries of any id array (ss_csr_group_ids).
 // PACKED (the only level of a one-level plan whose ids fit): records are src | (dst & (2^shift - 1)) << src_bits, 4 bytes
+//
+// tile_sym (edge lists only, nullable): is the edge MULTISET symmetric -- as many copies of j -> i as of i -> j?  The pass that reads
+// every pair anyway adds up two 64-bit wrapping sums S_m = sum over the kept edges of H_m(src, dst) - H_m(dst, src), m = 0, 1, with
+// H_m(s, d) = [s < d] * sym_mix<m>(s << 32 | d): an edge below the diagonal adds the mix of its pair, its reverse takes it away again, a
+// self edge adds nothing -- ONE evaluation of each mixer per edge.  Symmetric multisets sum to zero in any order; anything else leaves
+// both sums non-zero unless two independent 64-bit mixes (bijections of the pair: the splitmix64 and the murmur3 finalisers, seeded)
+// cancel at once, the kind of 128-bit content fingerprint ss_csr_build_cached already rests on.  Per tile {S_0, S_1, bad id seen, 0}:
+// no atomics on global memory, nothing to zero; the finish launch's reducer adds the tiles up (finish_runs_kernel).
+__device__ __forceinline__ uint64_t sym_mix0(uint64_t x) { return hash_u64(x + 0x9E3779B97F4A7C15ULL); }
+__device__ __forceinline__ uint64_t sym_mix1(uint64_t x)
+{
+    x ^= 0xD6E8FEB86659FD93ULL;
+    x ^= x >> 33;
+    x *= 0xFF51AFD7ED558CCDULL;
+    x ^= x >> 33;
+    x *= 0xC4CEB9FE1A85EC53ULL;
+    x ^= x >> 33;
+    return x;
+}
+
 template <bool PACKED>
 __global__ __launch_bounds__(kSortThreads) void tile_sort_kernel(const int64_t *__restrict__ src, const int64_t *__restrict__ dst, int64_t E,
                                                                  int64_t N, int key_stride, int shift, int src_bits, int keys, int tiles,
@@ -242,11 +262,12 @@ __global__ __launch_bounds__(kSortThreads) void tile_sort_kernel(const int64_t *
                                                                  int32_t *__restrict__ err, int32_t *__restrict__ hub_count,
                                                                  int32_t *__restrict__ mega_count, int32_t *__restrict__ dense_count,
                                                                  DenseSync *__restrict__ dense_sync, int dense_cap,
-                                                                 const int32_t *__restrict__ skip, int32_t *__restrict__ bad_record)
+                                                                 const int32_t *__restrict__ skip, int32_t *__restrict__ bad_record,
+                                                                 unsigned long long *__restrict__ tile_sym)
 {
     __shared__ int2 sorted[kTile];
     __shared__ uint32_t tile_hist[kMaxKeys], tile_offs[kMaxKeys], wave_tot[kSortThreads / kWave];
-    __shared__ unsigned long long block_max;
+    __shared__ unsigned long long block_max, block_sym[3];
     SS_CSR_SKIP(skip);
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // outputs of the finish launch of this build are cleared here
         if (hub_count) *hub_count = 0;
@@ -260,6 +281,7 @@ __global__ __launch_bounds__(kSortThreads) void tile_sort_kernel(const int64_t *
         if (threadIdx.x < sizeof(DenseSync) / 4) reinterpret_cast<int32_t *>(dense_sync + d)[threadIdx.x] = 0;
     if (threadIdx.x < kMaxKeys) tile_hist[threadIdx.x] = 0;
     if (threadIdx.x == 0) block_max = 0;
+    if (threadIdx.x < 3) block_sym[threadIdx.x] = 0;
     __syncthreads();
     constexpr int PER = kTile / kSortThreads;  // 8 edges per thread
     const int64_t t0 = (int64_t)blockIdx.x * kTile;
@@ -323,6 +345,28 @@ __global__ __launch_bounds__(kSortThreads) void tile_sort_kernel(const int64_t *
             key[k] = (int)(d >> shift);
         }
     }
+    if (tile_sym) {  // (workgroup-uniform) the symmetry sums of the kept edges, see above
+        unsigned long long s0 = 0, s1 = 0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const uint32_t s = (uint32_t)ed[k].x, d = (uint32_t)ed[k].y;
+            const uint64_t x = s < d ? ((uint64_t)s << 32) | d : ((uint64_t)d << 32) | s;
+            const uint64_t f0 = sym_mix0(x), f1 = sym_mix1(x);
+            if (key[k] >= 0 && s != d) {
+                s0 += s < d ? f0 : 0 - f0;
+                s1 += s < d ? f1 : 0 - f1;
+            }
+        }
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            s0 += __shfl_xor(s0, off);
+            s1 += __shfl_xor(s1, off);
+        }
+        if ((threadIdx.x & (kWave - 1)) == 0) {
+            atomicAdd(&block_sym[0], s0);
+            atomicAdd(&block_sym[1], s1);
+        }
+        if (bad) block_sym[2] = 1;
+    }
 #pragma unroll
     for (int k = 0; k < PER; ++k) rank[k] = key[k] >= 0 ? atomicAdd(&tile_hist[key[k]], 1u) : 0u;
     __syncthreads();
@@ -360,6 +404,7 @@ __global__ __launch_bounds__(kSortThreads) void tile_sort_kernel(const int64_t *
     if (bad && bad_record) *bad_record = 1;
     __syncthreads();
     if (threadIdx.x == 0) tile_max[blockIdx.x] = block_max;
+    if (tile_sym && threadIdx.x < 3) tile_sym[4 * (int64_t)blockIdx.x + threadIdx.x] = block_sym[threadIdx.x];
 }
 
 // ---- levels >= 1 -------------------------------------------------------------------------------------------------------------------
@@ -691,6 +736,8 @@ struct RowOutputs {
     int32_t *fault_word;  // process-wide count of such waits in pinned host memory (nullable; ss_csr_protocol_faults reads it without synchronising)
     unsigned long long wait_ticks;  // bound of wait_until
     uint32_t walk_max;    // buckets of up to this many edges are finished by their own workgroup (kDenseMin: only what fits the image; kWalkMax)
+    int32_t *symmetric;   // (nullable) <- 1 iff the tile sort's symmetry sums are both zero and it met no id out of range (tile_sort_kernel)
+    const unsigned long long *tile_sym;  // [tiles0][4] {S_0, S_1, bad id seen, 0} per tile of level 0
 };
 
 // exclusive scan of the per-node edge counts cnt[0..nb) of the bucket that starts at node0 -> excl[0..nb]; with `publish` the
@@ -1514,6 +1561,36 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
         *n_self = mx;
         o.rowptr[N] = (int64_t)(base + n);  // the last bucket ends the edge list
     }
+    if (reducer && o.symmetric) {  // (workgroup-uniform) ... and decides whether the edge multiset is symmetric: the tiles' sums, added up
+        unsigned long long s0 = 0, s1 = 0, bd = 0;
+        for (int t = threadIdx.x; t < tiles0; t += kRunThreads) {
+            s0 += o.tile_sym[4 * (int64_t)t];
+            s1 += o.tile_sym[4 * (int64_t)t + 1];
+            bd |= o.tile_sym[4 * (int64_t)t + 2];
+        }
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            s0 += __shfl_xor(s0, off);
+            s1 += __shfl_xor(s1, off);
+            bd |= __shfl_xor(bd, off);
+        }
+        __syncthreads();  // (every thread has read the three arrays above)
+        if ((threadIdx.x & (kWave - 1)) == 0) {
+            red_base[threadIdx.x / kWave] = s0;
+            red_max[threadIdx.x / kWave] = s1;
+            red_n[threadIdx.x / kWave] = (uint32_t)bd;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s0 = s1 = 0, bd = 0;
+            for (int w = 0; w < kRunThreads / kWave; ++w) {
+                s0 += red_base[w];
+                s1 += red_max[w];
+                bd |= red_n[w];
+            }
+            *o.symmetric = (s0 == 0 && s1 == 0 && bd == 0) ? 1 : 0;
+        }
+        __syncthreads();
+    }
     dense.row0 = row0;
     dense.row1 = row1;
     dense.t_lo = c.t_lo;
@@ -1623,6 +1700,7 @@ struct Workspace {
     int2 *staged_a;                 // level 0 (tile j at j * kTile) and level 2
     void *staged_b;                 // level 1
     unsigned long long *tile_max;   // [tiles0]
+    unsigned long long *tile_sym;   // [tiles0][4]
     unsigned long long *scratch;    // [1] n_self when the caller does not want it
     int32_t *dense_count;           // [kDenseSyncInts]
     DenseRunBucket *dense_list;
@@ -1654,6 +1732,7 @@ inline Workspace carve(const LevelPlan &p, int64_t E, void *base)
     w.staged_a = reinterpret_cast<int2 *>(take((size_t)p.tmax[0] * kTile * 8));
     w.staged_b = take(p.levels >= 2 ? (size_t)(E > 0 ? E : 1) * 8 : 0);
     w.tile_max = reinterpret_cast<unsigned long long *>(take((size_t)p.tmax[0] * 8));
+    w.tile_sym = reinterpret_cast<unsigned long long *>(take((size_t)p.tmax[0] * 32));
     w.scratch = reinterpret_cast<unsigned long long *>(take(8));
     w.dense_count = reinterpret_cast<int32_t *>(take(4 * kDenseSyncInts));
     const int64_t db = max_dense_buckets(E), ds = max_dense_shares(E);
@@ -1908,10 +1987,12 @@ extern "C" int ss_csr_protocol_faults(void)
 static int csr_build_launch(const ss::LevelPlan &lp, const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
                             int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows,
                             int32_t *mega_count, int32_t *err_flag, void *workspace, hipStream_t stream, const int32_t *skip = nullptr,
-                            int32_t *bad_record = nullptr, int key_stride = 2)
+                            int32_t *bad_record = nullptr, int key_stride = 2, int32_t *symmetric_out = nullptr)
 {
     using namespace ss;
     if (N == 0 || E == 0) {
+        // (no edge: no row has a neighbour that could stand in for its self row -- the word says 0, "nothing to skip")
+        if (symmetric_out && hipMemsetAsync(symmetric_out, 0, 4, stream) != hipSuccess) return SS_ERR_LAUNCH;
         if (n_self_loops_out && hipMemsetAsync(n_self_loops_out, 0, 8, stream) != hipSuccess) return SS_ERR_LAUNCH;
         if (hub_count && hipMemsetAsync(hub_count, 0, 4, stream) != hipSuccess) return SS_ERR_LAUNCH;
         if (mega_count && hipMemsetAsync(mega_count, 0, 8, stream) != hipSuccess) return SS_ERR_LAUNCH;
@@ -1919,20 +2000,23 @@ static int csr_build_launch(const ss::LevelPlan &lp, const int64_t *src, const i
         return SS_OK;
     }
     ProfileSpan span(stream, SS_PROF_CSR);  // all launches of this build
-    const RowOutputs rows_out = {rowptr, (int)hub_threshold, hub_rows, hub_count, mega_rows, mega_count, skip, err_flag, protocol_fault_word(), protocol_wait_ticks(), finish_walk_max(lp.groups[lp.levels])};
     const Workspace w = carve(lp, E, workspace);
+    if (!src) symmetric_out = nullptr;  // (a link list / an id array has no symmetry to speak of)
+    unsigned long long *tile_sym = symmetric_out ? w.tile_sym : nullptr;
+    const RowOutputs rows_out = {rowptr, (int)hub_threshold, hub_rows, hub_count, mega_rows, mega_count, skip, err_flag, protocol_fault_word(), protocol_wait_ticks(), finish_walk_max(lp.groups[lp.levels]),
+                                symmetric_out, tile_sym};
     unsigned long long *n_self = n_self_loops_out ? reinterpret_cast<unsigned long long *>(n_self_loops_out) : w.scratch;
     const int tiles0 = (int)lp.tmax[0];
     const bool packed = lp.packed;  // records of the last level (read by the finish step) are 4 bytes
     if (lp.packed0)  // (two levels: 4-byte level-0 records, see make_plan)
         hipLaunchKernelGGL(tile_sort_kernel<true>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits0, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record);
+                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
     else if (packed && lp.levels == 1)
         hipLaunchKernelGGL(tile_sort_kernel<true>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record);
+                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
     else
         hipLaunchKernelGGL(tile_sort_kernel<false>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record);
+                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
     SS_LAUNCH_CHECK();
     ParentLevel par = {w.lv[0].off, nullptr, nullptr, nullptr, tiles0, tiles0, lp.keys[0], -1};
     const void *in = w.staged_a;
@@ -1980,17 +2064,25 @@ static int csr_build_launch(const ss::LevelPlan &lp, const int64_t *src, const i
     return SS_OK;
 }
 
-extern "C" int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
-                            int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
-                            int32_t *mega_rows, int32_t *mega_count,
-                            int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream_)
+static int csr_build_plain(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col, int64_t *n_self_loops_out,
+                           int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag,
+                           void *workspace, size_t workspace_bytes, int32_t *symmetric_out, void *stream_)
 {
     if (E > 0 && !src) return SS_ERR_INVALID_ARG;
     ss::LevelPlan lp;
     const int rc = csr_check(src, dst, E, N, rowptr, col, hub_rows, hub_count, mega_rows, mega_count, workspace, workspace_bytes, lp);
     if (rc != SS_OK) return rc;
     return csr_build_launch(lp, src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                            workspace, (hipStream_t)stream_);
+                            workspace, (hipStream_t)stream_, nullptr, nullptr, 2, symmetric_out);
+}
+
+extern "C" int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
+                            int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
+                            int32_t *mega_rows, int32_t *mega_count,
+                            int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return csr_build_plain(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag, workspace,
+                           workspace_bytes, nullptr, stream_);
 }
 
 // ss_csr_build that first compares a content fingerprint of (src, dst) with the one the previous call left in `fingerprint`
@@ -2001,10 +2093,9 @@ extern "C" int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, i
 // Every check that can fail without a launch runs BEFORE the fingerprint kernels (they declare the outputs valid for this edge
 // list); if a launch of the build itself fails after them, the fingerprint is invalidated on the stream before the error is
 // returned -- a later call with the same edges must not skip over a CSR that was never completed.
-extern "C" int ss_csr_build_cached(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
-                                   int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
-                                   int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
-                                   void *fingerprint, void *stream_)
+static int csr_build_cached(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col, int64_t *n_self_loops_out,
+                            int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag,
+                            void *workspace, size_t workspace_bytes, void *fingerprint, int32_t *symmetric_out, void *stream_)
 {
     using namespace ss;
     if (!fingerprint || E <= 0 || N <= 0 || !src || !dst) return SS_ERR_INVALID_ARG;
@@ -2019,9 +2110,33 @@ extern "C" int ss_csr_build_cached(const int64_t *src, const int64_t *dst, int64
     rc = hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_LAUNCH;
     if (rc == SS_OK)
         rc = csr_build_launch(lp, src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                              workspace, stream, &fp->skip, &fp->bad);
+                              workspace, stream, &fp->skip, &fp->bad, 2, symmetric_out);
     if (rc != SS_OK) (void)hipMemsetAsync(&fp->valid, 0, sizeof(fp->valid), stream);  // the outputs may be half-written
     return rc;
+}
+
+extern "C" int ss_csr_build_cached(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
+                                   int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
+                                   int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                                   void *fingerprint, void *stream_)
+{
+    return csr_build_cached(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag, workspace,
+                            workspace_bytes, fingerprint, nullptr, stream_);
+}
+
+// ss_csr_build (fingerprint == NULL) or ss_csr_build_cached with one more output: *symmetric_out (device int32, nullable) <- 1 iff the
+// edge multiset is symmetric and every id is in range (tile_sort_kernel; decided by the finish launch: no launch, no memset of its
+// own; 0 for E == 0).  A cached build that finds the content unchanged leaves the word of the build it keeps.
+extern "C" int ss_csr_build_symmetric(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
+                                      int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count,
+                                      int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                                      void *fingerprint, int32_t *symmetric_out, void *stream_)
+{
+    if (!fingerprint)
+        return csr_build_plain(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
+                               workspace, workspace_bytes, symmetric_out, stream_);
+    return csr_build_cached(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
+                            workspace, workspace_bytes, fingerprint, symmetric_out, stream_);
 }
 
 // The pairs of a query grouped by their first node (reference hashing.py:270-274 reads cards[u] / the rows of u once per PAIR;

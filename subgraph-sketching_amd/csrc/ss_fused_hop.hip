@@ -130,6 +130,7 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
     MinhashRows<PPL, R> m;
     m.setup(g, pa, pb, p, skip_hubs);
     const int lane = m.lane, grp = lane >> 4, c = lane & (kRow - 1);
+    const bool skip_self = g.skip_self && *g.skip_self != 0;  // HLL side only (one scalar load per wavefront); the first hop keeps its self loop
 
     auto chunk_rows = [&](int64_t q) -> int { return q < n_chunks ? (int)(g.row1 - (g.row0 + q * R) < R ? g.row1 - (g.row0 + q * R) : R) : 0; };
     auto load_bounds = [&](int64_t q) -> int64_t {  // lane l: rowptr[first row of chunk q + l]
@@ -175,7 +176,7 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
         h.deg = ok ? rel1 - rel0 : 0;
         const bool hub = skip_hubs && h.deg > g.hub_threshold;
         h.write = ok && !hub;
-        h.total = h.write ? h.deg + (h.i < m.n_self ? 1 : 0) : 0;
+        h.total = h.write ? table_hop_total(h.deg, h.i < m.n_self, skip_self) : 0;
         if constexpr (!(SS_FUSED_ABLATE & 2)) {
         hll_post<0>(h, hll_in, ids_cur.my_nb, c);              // HLL rows of chunk k
         hll_post_lds<kHllInFlight>(h, hll_in, ids_cur.my_nb, c, lds_wave);
@@ -248,8 +249,14 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
         p0 = *prm;
     }
     if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;
-    const GraphArgs g = to_args(*graph);
+    GraphArgs g = to_args(*graph);
     if (g.rows() == 0) return SS_OK;
+    // both table hops of this stage read hop-1 tables of `graph`: the MinHash one this stage computes from node ids, the HLL one it
+    // computes too unless it is the caller's (cards1_out == NULL) -- the promise of SS_GRAPH_HOP_TABLES, made here for the whole-graph,
+    // single-device build (a row range or mirrors: the sharded builds, left alone)
+    const bool whole = graph->row_begin == 0 && graph->row_end == 0 && g.mir.n == 0;
+    const int32_t *const skip_word = self_skip_word(*graph, whole);
+    g.skip_self = nullptr;
     hipStream_t s = (hipStream_t)stream;
     const bool hubs = g.hub_rows && g.hub_count;
     // hub units: `lead` leading workgroups of the HLL first-hop launch serve both hop-1 tables, of the MinHash table hop both hop-2
@@ -275,6 +282,7 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
     const int wg_per_cu = (wg_per_cu_env > 0 && wg_per_cu_env <= 4096) ? wg_per_cu_env  // (a bad value falls back to the default)
                           : (blocks > 256u * 128u ? 64 : 20);
     const unsigned grid = blocks < (unsigned)(256 * wg_per_cu) ? blocks : (unsigned)(256 * wg_per_cu);
+    g.skip_self = own_hop1 ? skip_word : nullptr;
     {
         ProfileSpan span(s, SS_PROF_FUSED, true);
         switch (P / kWave) {
@@ -285,6 +293,7 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
         }
     }
     SS_LAUNCH_CHECK();
+    g.skip_self = skip_word;  // (the MinHash table hop below; the hub launches do not look at it)
     // hub rows of the hop-1 MinHash table (from node ids): they must be in place before anything reads that table
     int rc = own_hop1 ? SS_OK : launch_first_hop_hub_only(g, a, b, P, mh1_out, p, nullptr, nullptr, 0, p0, s);
     if (rc != SS_OK) return rc;

@@ -8,7 +8,8 @@
 // sub-groups (SG = pow2 >= chunks per row, <= 64) that walk G neighbours concurrently
 // (P=128: 2 neighbours per step, M=256: 4), so every global load is a coalesced dwordx4 and a step
 // moves 1 KiB per wave.  Partial min / max are combined across sub-groups once per row with
-// cross-lane shuffles.  The implicit self loop (i < n_self) is one extra virtual neighbour.
+// cross-lane shuffles.  The implicit self loop (i < n_self) is one extra virtual neighbour -- left out, for rows that have an
+// in-edge, when the graph is symmetric and the inputs are hop tables of it (GraphArgs.skip_self, ss_common.hpp table_hop_total).
 //
 // Hub rows (in-degree > graph.hub_threshold, listed by ss_csr_build) would serialise tens of thousands of
 // dependent 1 KiB loads on one wavefront (power-law graphs: ogbl-ppa, ogbl-citation2).  The row wavefronts
@@ -69,7 +70,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void p
     const int deg = (int)(g.rowptr[i + 1] - rb);
     if (skip_hubs && deg > g.hub_threshold) return;  // a hub unit (ss_hub.hpp)
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
-    const int total = deg + (i < n_self ? 1 : 0);
+    const bool skip_self = g.skip_self && *g.skip_self != 0;  // (one scalar load per wavefront)
+    const int total = table_hop_total(deg, i < n_self, skip_self);
     const int32_t *nb = g.col + rb;
 
     // ---------------- MinHash: min over neighbours ----------------

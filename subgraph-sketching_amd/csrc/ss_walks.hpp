@@ -765,7 +765,8 @@ __device__ __forceinline__ void hll_hop_row16(const GraphArgs &g, int64_t row, b
     const int deg = (int)(g.rowptr[i + 1] - rb);
     const bool hub = skip_hubs && deg > g.hub_threshold;
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
-    const int total = (!ok || hub) ? 0 : deg + (i < n_self ? 1 : 0);
+    const bool skip_self = g.skip_self && *g.skip_self != 0;  // (one scalar load per wavefront)
+    const int total = (!ok || hub) ? 0 : table_hop_total(deg, i < n_self, skip_self);
     const int32_t *nb = g.col + rb;
     const u32x4 acc = hll_walk_first16(hll_in, nb, deg, total, i, c);
     hll_row16_finish(i, ok && !hub, nb, deg, total, acc, 16, hll_in, hll_out, cards_out, cards_stride, est, want_cards, c, g.mir);

@@ -360,9 +360,9 @@ class ElphHashes(object):
                 _native.check(_native.lib().ss_fused_hop_stage(byref(graph), _ptr(ab[0]), _ptr(ab[1]), self.num_perm, _ptr(mh[0]), _ptr(mh[1]),
                                                                self.p, _ptr(hll[0]), _ptr(cards), _ptr(hll[1]), _ptr(cards[:, 1]), h,
                                                                byref(params.struct), _stream(device)), 'ss_fused_hop_stage')
-            for k in range(3, h + 1):
+            for k in range(3, h + 1):  # (inputs: hop k - 1 >= 2 of this build -- on a symmetric graph the rows skip their own row)
                 _propagate(csr, mh[k - 2], hll[k - 2], device, cards_out=cards[:, k - 1], cards_stride=h, params=params,
-                           mh_out=mh[k - 1], hll_out=hll[k - 1])
+                           mh_out=mh[k - 1], hll_out=hll[k - 1], hop_tables=True)
         elif shard is None:
             # (inside the library each of these calls is one launch per sketch, each hosting its hub units: measured faster than
             # two-sketch kernels -- first hop 37 + 134 us vs 184, table hop 111 + 192 us vs 326 on the bench graph)
@@ -374,8 +374,9 @@ class ElphHashes(object):
                     _propagate(csr, None, hll_prev, device, cards_out=cards[:, 0], cards_stride=h, params=params, hll_out=hll[0])
                 else:
                     logger.info(f"Calculating hop {k} hashes")
+                    # (k >= 2: both inputs are hop k - 1 of this build; hop-0 rows are functions of the id alone: the self row stays)
                     _propagate(csr, mh_prev, hll_prev, device, cards_out=cards[:, k - 1], cards_stride=h, params=params,
-                               mh_out=mh[k - 1], hll_out=hll[k - 1])
+                               mh_out=mh[k - 1], hll_out=hll[k - 1], hop_tables=k >= 2)
                 mh_prev, hll_prev = mh[k - 1], hll[k - 1]
         elif peer:
             # peer-write: no exchange step -- the kernels store every finished row into all ranks' tables while they run

@@ -14,9 +14,11 @@ from .containers import LazyMinhash, _packed_hll_of, _packed_minhash_of, _tag, u
 from .csr import _default_csr_cache
 
 
-def _propagate(csr, mh_in, hll_in, device, cards_out=None, cards_stride=0, params=None, mh_out=None, hll_out=None, rows=None, mirrors=None):
+def _propagate(csr, mh_in, hll_in, device, cards_out=None, cards_stride=0, params=None, mh_out=None, hll_out=None, rows=None, mirrors=None,
+               hop_tables=False):
     """one hop; returns (mh_out or None, hll_out or None).  mh_in packed int32 [N,P], hll_in uint8 [N,M];
-    rows = (begin, end) restricts the destination rows written (inputs are always the full tables)"""
+    rows = (begin, end) restricts the destination rows written (inputs are always the full tables);
+    hop_tables: the inputs are the previous hop (>= 1) of this same graph's build (CsrGraph.struct)"""
     N = csr.num_nodes
     if mh_in is not None and mh_out is None:
         mh_out = torch.empty_like(mh_in)
@@ -25,7 +27,7 @@ def _propagate(csr, mh_in, hll_in, device, cards_out=None, cards_stride=0, param
     P = mh_in.size(1) if mh_in is not None else 0
     M = hll_in.size(1) if hll_in is not None else 0
     prm = byref(params.struct) if params is not None else None
-    graph = csr.struct(rows, mirrors)
+    graph = csr.struct(rows, mirrors, hop_tables=hop_tables)
     with _Span('propagate' if (mh_in is not None and hll_in is not None) else ('propagate_mh' if hll_in is None else 'propagate_hll'), device):
         _native.check(_native.lib().ss_propagate(byref(graph), _ptr(mh_in), _ptr(mh_out), P, _ptr(hll_in), _ptr(hll_out), M,
                                                  _ptr(cards_out), cards_stride, prm, _stream(device)), 'ss_propagate')
