@@ -11,10 +11,10 @@ import torch
 from . import _native, knobs
 from ._runtime import _compute_device, _ptr, _stream, _Span
 
-# (device, stream) -> (N, slots, zeroed uint8 slot arena of ss_exact_large).  One arena per STREAM: the arena must be all zero when a
-# call's large-tier launch starts and is all zero again when it ends, which holds for calls ordered on one stream; calls in flight on
-# two streams at once get two arenas.  An entry is replaced (the old arena freed into the stream it was used on) when N or the slot
-# count changes.
+# (device, stream) -> (N, slots, zeroed uint8 slot arena of ss_exact_large).  One arena per STREAM: every slot's distance words must
+# be zero when a call's large-tier launch starts and are zero again when it ends (the visit lists behind them are scratch, written
+# before they are read), which holds for calls ordered on one stream; calls in flight on two streams at once get two arenas.  An
+# entry is replaced (the old arena freed into the stream it was used on) when N or the slot count changes.
 _ARENA = {}
 
 

@@ -80,13 +80,14 @@ def walk(nb, u, v, h, cap=None, ratio=1.0, seed=0, fringes=None):
     return hop_of
 
 
-def restate_nodes(num_nodes, edge_index, links, h, cap=None, ratio=1.0, seed=0, max_nodes=None, return_info=False):
+def restate_nodes(num_nodes, edge_index, links, h, cap=None, ratio=1.0, seed=0, max_nodes=None, return_info=False, nb=None):
     """(rowptr int64 [L + 1], ids int64 [T], hop uint8 [T]) of `links` (int [L, 2], negative ids wrapped); with return_info also
-    {'truncated': indices of the rows emptied by max_nodes, 'sampled_links': links where some hop dropped a node}"""
+    {'truncated': indices of the rows emptied by max_nodes, 'sampled_links': links where some hop dropped a node}.  nb: the caller's own
+    node -> set of in-neighbours in place of in_neighbours(num_nodes, edge_index) (a sparse mapping where a list of N sets is too much)"""
     n = int(num_nodes)
     links = np.asarray(links, dtype=np.int64).reshape(-1, 2)
     links = np.where(links < 0, links + n, links)
-    nb = in_neighbours(n, edge_index)
+    nb = in_neighbours(n, edge_index) if nb is None else nb
     rowptr, ids, hops, gone, sampled = [0], [], [], [], 0
     for q, (u, v) in enumerate(links.tolist()):
         fr = []
