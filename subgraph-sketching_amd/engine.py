@@ -1109,8 +1109,10 @@ class ElphHashes(object):
                of an undirected change); only their targets (row 1) are used; at least one must be given.  Ids outside [0, num_nodes)
                are reported as build_hash_tables reports them (strict_bounds)
         @param copy: False updates the given objects in place; True clones the tables first and leaves the inputs untouched
-        @param return_info: also return {'seed_rows': int, 'dirty_rows': {k: rows recomputed at hop k}} (one host read, after the
-               last launch)
+        @param return_info: also return {'seed_rows': int, 'dirty_rows': {k: rows recomputed at hop k}, 'row_list': {k: ...},
+               'hub_list': {k: ...}} (one host read, after the last launch).  'masks' adds what the marking kernels left in the
+               workspace: 'dirty_mask' {k: bool [N] device tensor, the rows hop k recomputed}, and 'rows' / 'hubs' {k: int32 device
+               tensor}, the listed regular rows and the listed hub rows (in-degree above the CSR's hub threshold) in list order
         @return: (table, cards[, info]): every hop table bit-identical to build_hash_tables(num_nodes, edge_index)"""
         from . import update
         return update.update_hash_tables(self, hash_table, cards, num_nodes, edge_index, added=added, removed=removed, copy=copy,

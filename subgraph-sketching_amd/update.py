@@ -71,9 +71,44 @@ def _refresh_leaves(entry, mh, hll):
         entry._leaf_versions[key] = leaf._version
 
 
+HEADER_BYTES = 256  # kUpdHeaderBytes of ss_update.hip
+
+
+def carve_workspace(ws, num_nodes, h):
+    """the workspace of ss_update_mark / ss_update_hop carved exactly as carve_update_ws (ss_update.hip) carves it -> (counters,
+    maps, lists), all views of `ws` (uint8, ss_update_workspace_bytes(N, h) long):
+      counters  int32 [64]: word 0 = seed rows, words 4k .. 4k+2 = hop k's dirty rows, row-list length, hub-list length
+      maps      h byte maps uint8 [N] (1 = dirty at that hop), pad(N) = (N + 255) & ~255 bytes apart
+      lists     h int32 [pad(N)] lists: the regular rows fill one from the front, the hub rows from index N - 1 downwards"""
+    N = int(num_nodes)
+    pad = (N + 255) & ~255
+    counters = ws[:HEADER_BYTES].view(torch.int32)
+    maps = [ws[HEADER_BYTES + k * pad:HEADER_BYTES + k * pad + N] for k in range(h)]
+    first = HEADER_BYTES + h * pad
+    lists = [ws[first + 4 * k * pad:first + 4 * (k + 1) * pad].view(torch.int32) for k in range(h)]
+    return counters, maps, lists
+
+
+def workspace_info(ws, num_nodes, h, masks=False):
+    """the `info` of update_hash_tables read from a marked workspace (one host read of the counters)"""
+    counters, maps, lists = carve_workspace(ws, num_nodes, h)
+    words = counters[:4 * (h + 1)].cpu().tolist()
+    hops = range(1, h + 1)
+    info = {'seed_rows': words[0], 'dirty_rows': {k: words[4 * k] for k in hops}, 'row_list': {k: words[4 * k + 1] for k in hops},
+            'hub_list': {k: words[4 * k + 2] for k in hops}}
+    if masks:
+        N = int(num_nodes)
+        info['dirty_mask'] = {k: maps[k - 1] != 0 for k in hops}
+        info['rows'] = {k: lists[k - 1][:info['row_list'][k]].clone() for k in hops}
+        info['hubs'] = {k: lists[k - 1][N - info['hub_list'][k]:N].flip(0) for k in hops}  # in the order the hub kernels take them
+    return info
+
+
 def update_hash_tables(eh, hash_table, cards, num_nodes, edge_index, added=None, removed=None, copy=False, return_info=False):
     """see ElphHashes.update_hash_tables"""
     h = eh.max_hops
+    if return_info not in (False, True, 'masks'):
+        raise ValueError(f"return_info must be False, True or 'masks', got {return_info!r}")
     N, ei, add, rem, entries = check_arguments(eh, hash_table, cards, num_nodes, edge_index, added, removed)
     if not cards.is_cuda or any(e.mh_u32.device != cards.device or e.hll_u8.device != cards.device for e in entries):
         raise ValueError('update_hash_tables updates the packed tables where they live: hash_table and cards must be on the compute device')
@@ -97,7 +132,15 @@ def update_hash_tables(eh, hash_table, cards, num_nodes, edge_index, added=None,
     if out_cards.stride(1) != 1 or out_cards.stride(0) < h:
         raise ValueError('cards must be a row-major tensor')
     if N == 0:
-        return (table, out_cards, {'seed_rows': 0, 'dirty_rows': {k: 0 for k in range(1, h + 1)}}) if return_info else (table, out_cards)
+        if not return_info:
+            return table, out_cards
+        none = {k: 0 for k in range(1, h + 1)}
+        info = {'seed_rows': 0, 'dirty_rows': dict(none), 'row_list': dict(none), 'hub_list': dict(none)}
+        if return_info == 'masks':
+            info['dirty_mask'] = {k: torch.zeros(0, dtype=torch.bool, device=device) for k in none}
+            info['rows'] = {k: torch.zeros(0, dtype=torch.int32, device=device) for k in none}
+            info['hubs'] = {k: torch.zeros(0, dtype=torch.int32, device=device) for k in none}
+        return table, out_cards, info
 
     # the CSR of the graph AFTER the change, exactly as build_hash_tables builds it (implicit self loops below max(edge_index) + 1)
     check, err_flag = eh._bounds(device, f'update_hash_tables(num_nodes={N})')
@@ -144,7 +187,4 @@ def update_hash_tables(eh, hash_table, cards, num_nodes, edge_index, added=None,
         raise IndexError(f'added / removed refer to nodes outside [0, {N})')
     if not return_info:
         return table, out_cards
-    words = ws[:4 * (h + 1) * 4].view(torch.int32).cpu().tolist()
-    info = {'seed_rows': words[0], 'dirty_rows': {k: words[4 * k] for k in range(1, h + 1)},
-            'row_list': {k: words[4 * k + 1] for k in range(1, h + 1)}, 'hub_list': {k: words[4 * k + 2] for k in range(1, h + 1)}}
-    return table, out_cards, info
+    return table, out_cards, workspace_info(ws, N, h, masks=return_info == 'masks')

@@ -1,8 +1,11 @@
 """ElphHashes.update_hash_tables on the GPU (update.py, csrc/ss_update.hip).  Reference in every case: build_hash_tables of the SAME
 engine on the new edge list (itself pinned on goldens and oracle by the rest of the suite).  Per case: hop tables torch.equal to the
 rebuild; cards within DESIGN 4's bar (rtol 1e-5, atol 1e-5 * 4 * max|cards|); cards outside dirty_k bit-identical to their OLD values
-(never written); info['dirty_rows'][k] == |dirty_k| of the numpy restatement (tests/update_restatement.py) exactly -- which a rebuild
-in disguise cannot meet, because every case first asserts |dirty_h| < N on the restatement alone."""
+(never written); and, from return_info='masks', the marker's own record equal to the numpy restatement (tests/update_restatement.py) AS
+SETS: the byte map of hop k == dirty_k, the row list and the hub list together == dirty_k with each row once, the hub list == the dirty
+rows above the CSR's hub threshold, the counters == the lengths -- which a rebuild in disguise cannot meet, because every case first
+asserts |dirty_h| < N on the restatement alone.  (A MinHash or HLL row rarely changes when one in-neighbour does: "equal to the
+rebuild" alone passes for most rows a marker wrongly skips, and a count passes for a marker that swaps one row for another.)"""
 from argparse import Namespace
 
 import numpy as np
@@ -55,15 +58,40 @@ def _assert_cards_bar(got, want):
     np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-5, atol=1e-5 * 4 * float(np.abs(want).max() if want.size else 0.0))
 
 
-def check_update(ssa, dev, n, old_ei, new_ei, added, removed, h=2, num_perm=128, p=8, copy=False):
-    """-> (eh, updated table, updated cards, rebuilt table, rebuilt cards, dirty)"""
+def hub_threshold_of(ssa, new_ei):
+    """the threshold build_csr gives the CSR of the update: the knob, or the default for that many edges"""
+    forced = ssa.knobs.HUB_THRESHOLD
+    return forced if forced is not None else ssa.hashing.default_hub_threshold(np.asarray(new_ei).shape[1])
+
+
+def assert_marks(ssa, dev, n, new_ei, info, dirty, h):
+    """the marker's maps, lists and counters against the restatement, as sets"""
+    deg = np.bincount(np.asarray(new_ei, dtype=np.int64)[1], minlength=n)
+    above = deg > hub_threshold_of(ssa, new_ei)
+    assert info['seed_rows'] == int(dirty[1].sum())
+    for k in range(1, h + 1):
+        mask = info['dirty_mask'][k]
+        assert mask.dtype == torch.bool and mask.device.type == 'cuda' and tuple(mask.shape) == (n,)
+        assert torch.equal(mask, torch.from_numpy(dirty[k]).to(dev)), \
+            f'hop {k}: the map differs from dirty_{k} at rows {np.flatnonzero(mask.cpu().numpy() != dirty[k])[:8]}'
+        assert info['rows'][k].dtype == torch.int32 and info['hubs'][k].dtype == torch.int32
+        rows, hubs = info['rows'][k].cpu().numpy(), info['hubs'][k].cpu().numpy()
+        listed = np.concatenate([rows, hubs])
+        assert np.array_equal(np.sort(listed), np.flatnonzero(dirty[k])), f'hop {k}: the lists are not dirty_{k}, each row once'
+        assert np.array_equal(np.sort(hubs), np.flatnonzero(dirty[k] & above)), f'hop {k}: the hub list is not the dirty rows above the threshold'
+        assert (info['dirty_rows'][k], info['row_list'][k], info['hub_list'][k]) == (listed.size, rows.size, hubs.size), (k, info['dirty_rows'])
+
+
+def check_update(ssa, dev, n, old_ei, new_ei, added, removed, h=2, num_perm=128, p=8, copy=False, hubs_at=None):
+    """-> (eh, updated table, updated cards, rebuilt table, rebuilt cards, dirty)
+    hubs_at: {k: bool}, whether hop k must have listed hub rows (a case that is meant to reach the hub kernels says so)"""
     dirty = expected_dirty(n, old_ei, new_ei, added, removed, h)
     eh = _eh(ssa, h, num_perm, p)
     t_old, c_old = eh.build_hash_tables(n, _t(old_ei, dev))
     snap_t, snap_c = _snapshot(t_old, c_old, h)
     t_ref, c_ref = eh.build_hash_tables(n, _t(new_ei, dev))
     t_up, c_up, info = eh.update_hash_tables(t_old, c_old, n, _t(new_ei, dev), added=_t(added, dev), removed=_t(removed, dev), copy=copy,
-                                             return_info=True)
+                                             return_info='masks')
     if copy:
         assert t_up is not t_old and c_up is not c_old
         for k in range(1, h + 1):  # the inputs are bit-identical to what they were
@@ -74,10 +102,11 @@ def check_update(ssa, dev, n, old_ei, new_ei, added, removed, h=2, num_perm=128,
         assert t_up is t_old and c_up is c_old
     assert getattr(c_up, '_ss_tables', None) == eh.tables_id
     assert t_up[0] is t_old[0]  # hop 0 never changes
-    print(f'N={n} h={h} shape=({num_perm},{p}) info={info}')
-    assert info['seed_rows'] == int(dirty[1].sum())
+    print(f'N={n} h={h} shape=({num_perm},{p}) info={ {key: info[key] for key in ("seed_rows", "dirty_rows", "row_list", "hub_list")} }')
+    assert_marks(ssa, dev, n, new_ei, info, dirty, h)
+    for k, want in (hubs_at or {}).items():
+        assert (info['hub_list'][k] > 0) == want, f'hop {k} lists {info["hub_list"][k]} hub rows'
     for k in range(1, h + 1):
-        assert info['dirty_rows'][k] == int(dirty[k].sum()), (k, info, int(dirty[k].sum()))
         assert torch.equal(t_up[k].mh_u32, t_ref[k].mh_u32), f'MinHash hop {k}'
         assert torch.equal(t_up[k].hll_u8, t_ref[k].hll_u8), f'HLL hop {k}'
         clean = torch.from_numpy(~dirty[k]).to(dev)
@@ -274,3 +303,217 @@ def test_out_of_range_targets_are_reported(ssa, dev):
     eh.update_hash_tables(t, c, n, _t(ei, dev), added=_t(np.array([[1], [n + 5]], dtype=np.int64), dev))
     with pytest.raises(IndexError):
         eh.check_errors()
+
+
+# ---- hub rows at every sketch shape, and many of them ----------------------------------------------------------------------------------
+def _leaf_to_hub_case():
+    n = 20000
+    ei = ur.power_law_graph(n, 100000, 65)
+    deg = np.bincount(ei[1], minlength=n)
+    hub, leaf = int(np.argmax(deg)), int(np.flatnonzero(deg == 0)[0])
+    assert deg[hub] > 2048 and (deg > 40).sum() > 100  # a row only the whole workgroup (or, unlisted, one wavefront) walks
+    new, added = ur.add_edges(ei, np.array([[leaf], [hub]]))
+    return n, ei, new, added
+
+
+@pytest.mark.parametrize('threshold', [40, 10 ** 9])
+@pytest.mark.parametrize('num_perm,p,h', [(128, 8, 2), (64, 6, 2), (192, 8, 2), (256, 10, 2), (8, 4, 2), (128, 8, 3), (8, 4, 3)])
+def test_hub_kernels_at_every_shape(ssa, dev, monkeypatch, num_perm, p, h, threshold):
+    """update_hub_first_kernel<PPL> at PPL 1 .. 4 and update_hub_table_kernel at M = 16 / 64 / 256 / 1 024 and P = 8 (threshold 40: the
+    changed hub and the hubs among its neighbours are listed at every hop); with everything regular (threshold 10^9) one wavefront of
+    the row kernels walks the 3 700-edge row"""
+    monkeypatch.setattr(ssa.knobs, 'HUB_THRESHOLD', threshold)
+    n, ei, new, added = _leaf_to_hub_case()
+    check_update(ssa, dev, n, ei, new, added, None, h=h, num_perm=num_perm, p=p, hubs_at={k: threshold == 40 for k in range(1, h + 1)})
+
+
+@pytest.mark.parametrize('num_perm,p', [(128, 8), (8, 4)])
+def test_more_listed_hubs_than_hub_workgroups(ssa, dev, monkeypatch, num_perm, p):
+    """threshold 8 on a graph of mean degree 20: nearly every dirty row is a hub row, more than the 256 workgroups of a hub launch --
+    the `q += gridDim.x` stride of update_hub_first_kernel (128, 8) and of update_hub_table_kernel (hop 2; at (8, 4) hop 1 as well)"""
+    monkeypatch.setattr(ssa.knobs, 'HUB_THRESHOLD', 8)
+    n = 20000
+    ei = ur.uniform_graph(n, 200000, 61)
+    new, added = ur.add_edges(ei, np.random.RandomState(62).randint(0, n, size=(2, 150)))
+    _, _, _, _, _, dirty = check_update(ssa, dev, n, ei, new, added, None, h=2, num_perm=num_perm, p=p, hubs_at={1: True, 2: True})
+    deg = np.bincount(new[1], minlength=n)
+    assert (dirty[1] & (deg > 8)).sum() > 256 and (dirty[2] & (deg > 8)).sum() > 2048
+
+
+@pytest.mark.parametrize('num_perm,p', [(128, 8), (8, 4)])
+def test_fewer_nodes_than_hub_workgroups(ssa, dev, monkeypatch, num_perm, p):
+    """N = 100: hub_grid = N, one 256-row block, every launch smaller than its cap"""
+    monkeypatch.setattr(ssa.knobs, 'HUB_THRESHOLD', 8)
+    n = 100
+    ei = ur.uniform_graph(n, 1500, 63)
+    new, added = ur.add_directed(ei, np.array([[5], [17]]))
+    check_update(ssa, dev, n, ei, new, added, None, h=2, num_perm=num_perm, p=p, hubs_at={1: True, 2: True})
+
+
+# ---- directed and multigraph changes ---------------------------------------------------------------------------------------------------
+def _directed_graph():
+    n = 6000
+    return n, ur.directed_graph(n, 18000, 64)
+
+
+def directed_change(n, ei, kind):
+    """3 directed additions (at least one of their sources is no target of any change), 4 directed removals, or both"""
+    rng = np.random.RandomState(70)
+    new, added, removed = ei, None, None
+    if kind in ('remove', 'mixed'):
+        new, removed = ur.remove_directed(ei, rng.choice(ei.shape[1], size=4, replace=False))
+    if kind in ('add', 'mixed'):
+        new, added = ur.add_directed(new, rng.randint(0, n, size=(2, 3)))
+    return new, added, removed
+
+
+@pytest.mark.parametrize('h', [1, 2, 3])
+@pytest.mark.parametrize('kind', ['add', 'remove', 'mixed'])
+def test_directed_changes_on_a_directed_graph(ssa, dev, kind, h):
+    """only edge[1] of a changed edge is a seed, and dirt travels along the edges' direction (CSR by destination): on undirected lists
+    both endpoints are targets, and a marker that read the wrong row of `added`, or pushed along out-edges, would pass"""
+    n, ei = _directed_graph()
+    new, added, removed = directed_change(n, ei, kind)
+    changes = np.concatenate([c for c in (added, removed) if c is not None], axis=1)
+    sources_only = np.setdiff1d(changes[0], changes[1])
+    assert sources_only.size >= 1 and ur.n_self_of(ei) == ur.n_self_of(new)
+    _, _, _, _, _, dirty = check_update(ssa, dev, n, ei, new, added, removed, h=h)
+    # (check_update compared the engine's hop-1 map with this one exactly)
+    assert not dirty[1][sources_only].any() and dirty[1].sum() == np.unique(changes[1]).size
+
+
+def _old_tables(ssa, dev, n, ei, h):
+    t, _ = _eh(ssa, h).build_hash_tables(n, _t(ei, dev))
+    return t
+
+
+@pytest.mark.parametrize('form', ['copy-added', 'copy-removed', 'self-loop', 'empty-added', 'int32-added'])
+def test_multigraph_changes_and_input_forms(ssa, dev, form):
+    n, ei = _directed_graph()
+    h = 2
+    edge = ei[:, 100:101]
+    assert edge[0, 0] != edge[1, 0]
+    if form == 'copy-added':      # a second copy of an existing edge: no table changes, the target is dirty all the same
+        new, added = ur.add_directed(ei, edge)
+        _, t_up, _, _, _, dirty = check_update(ssa, dev, n, ei, new, added, None, h=h)
+        assert dirty[1].sum() == 1 and dirty[1][edge[1, 0]]
+        t_old = _old_tables(ssa, dev, n, ei, h)
+        for k in range(1, h + 1):
+            assert torch.equal(t_up[k].mh_u32, t_old[k].mh_u32) and torch.equal(t_up[k].hll_u8, t_old[k].hll_u8)
+    elif form == 'copy-removed':  # one of two copies goes
+        old, removed = ur.add_directed(ei, edge)
+        check_update(ssa, dev, n, old, ei, None, removed, h=h)
+    elif form == 'self-loop':     # an explicit (u, u) beside the implicit one
+        u = int(edge[0, 0])
+        new, added = ur.add_directed(ei, np.array([[u], [u]]))
+        _, _, _, _, _, dirty = check_update(ssa, dev, n, ei, new, added, None, h=h)
+        assert np.flatnonzero(dirty[1]).tolist() == [u]
+    elif form == 'empty-added':   # `added` of shape [2, 0] beside a non-empty `removed`
+        new, removed = ur.remove_directed(ei, np.array([7, 4000]))
+        check_update(ssa, dev, n, ei, new, np.zeros((2, 0), dtype=np.int64), removed, h=h)
+    else:                         # int32 ids
+        new, added = ur.add_directed(ei, np.array([[11, 5000], [4999, 12]]))
+        check_update(ssa, dev, n, ei, new, added.astype(np.int32), None, h=h)
+
+
+# ---- the update writes exactly its rows ------------------------------------------------------------------------------------------------
+SENTINEL_BYTE, SENTINEL_CARD = 0xA5, -7.0
+
+
+@pytest.fixture(scope='module')
+def uniform_20k():
+    n = 20000
+    ei = ur.uniform_graph(n, 200000, 61)
+    assert ur.n_self_of(ei) == n
+    return n, ei
+
+
+@pytest.mark.parametrize('num_perm,p', [(128, 8), (8, 4)])
+@pytest.mark.parametrize('h', [1, 2, 3])
+@pytest.mark.parametrize('k', [1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65])
+def test_update_writes_exactly_its_rows(ssa, dev, uniform_20k, k, h, num_perm, p):
+    """k directed additions with distinct non-hub targets: the hop-1 row list is k long -- around the 4 rows a workgroup of the
+    wave-per-row kernels takes and the 16 of the 16-lane ones, whose `q >= n` groups must store nothing.  Before the update every row
+    of the LAST hop's packed tables and cards column outside dirty_h is filled with a sentinel (bytes 0xA5, card -7.0): a clean row
+    that is recomputed gets its own bits back, so only a sentinel shows a stray store.  Only the last hop can be poisoned -- later
+    hops read the earlier ones -- and at h = 1 its cards column is also the marker's self-loop memory (cards_old > 0), so there the
+    sentinel card is +7.0: every row keeps saying "had its loop", and must still hold +7.0 bit for bit.
+    The packed tensors are edited directly: a HopSketch watches its materialised leaves for caller edits, not its packed twins, and
+    no leaf is materialised here."""
+    n, ei = uniform_20k
+    rng = np.random.RandomState(1000 * h + k)
+    targets = rng.choice(n, size=k, replace=False)
+    new, added = ur.add_directed(ei, np.stack([rng.randint(0, n, size=k), targets]))
+    deg = np.bincount(new[1], minlength=n)
+    assert (deg[targets] <= hub_threshold_of(ssa, new)).all()
+    dirty = expected_dirty(n, ei, new, added, None, h)
+    assert dirty[1].sum() == k
+    eh = _eh(ssa, h, num_perm, p)
+    t, c = eh.build_hash_tables(n, _t(ei, dev))
+    t_ref, c_ref = eh.build_hash_tables(n, _t(new, dev))
+    clean = torch.from_numpy(~dirty[h]).to(dev)
+    d = ~clean
+    card = torch.tensor([SENTINEL_CARD if h > 1 else -SENTINEL_CARD], dtype=torch.float32, device=dev)
+    t[h].mh_u32.view(torch.uint8)[clean] = SENTINEL_BYTE
+    t[h].hll_u8[clean] = SENTINEL_BYTE
+    c[clean, h - 1] = card[0]
+    t_up, c_up, info = eh.update_hash_tables(t, c, n, _t(new, dev), added=_t(added, dev), return_info='masks')
+    assert t_up is t and c_up is c
+    assert_marks(ssa, dev, n, new, info, dirty, h)
+    assert info['row_list'][1] == k and info['hub_list'][1] == 0
+    for j in range(1, h):  # the hops below the last one: equal to the rebuild everywhere
+        assert torch.equal(t[j].mh_u32, t_ref[j].mh_u32) and torch.equal(t[j].hll_u8, t_ref[j].hll_u8), f'hop {j}'
+    _assert_cards_bar(c[:, :h - 1], c_ref[:, :h - 1])
+    mh, hll = t[h].mh_u32.view(torch.uint8), t[h].hll_u8
+    stray_mh = (mh[clean] != SENTINEL_BYTE).any(dim=1)
+    stray_hll = (hll[clean] != SENTINEL_BYTE).any(dim=1)
+    stray_card = c[clean, h - 1].view(torch.int32) != card.view(torch.int32)
+    rows = torch.nonzero(clean).flatten()
+    assert not bool(stray_mh.any()), f'MinHash rows outside dirty_{h} were written: {rows[stray_mh][:8].tolist()}'
+    assert not bool(stray_hll.any()), f'HLL rows outside dirty_{h} were written: {rows[stray_hll][:8].tolist()}'
+    assert not bool(stray_card.any()), f'cards outside dirty_{h} were written: {rows[stray_card][:8].tolist()}'
+    assert torch.equal(t[h].mh_u32[d], t_ref[h].mh_u32[d]) and torch.equal(hll[d], t_ref[h].hll_u8[d]), f'rows of dirty_{h}'
+    _assert_cards_bar(c[d, h - 1], c_ref[d, h - 1])
+    eh.check_errors()
+
+
+# ---- a chain of in-place updates -------------------------------------------------------------------------------------------------------
+def test_chain_of_in_place_updates(ssa, dev):
+    """eight successive in-place updates of one table set, directed additions and removals in turn, one of which moves
+    max(edge_index) up and a later one down again: after each step the tables are the rebuild's, and the marker's maps are the
+    restatement's with "had its self loop" read from the PREVIOUS graph -- the cards column of the updated tables is the loop memory of
+    the next update"""
+    n, h = 6000, 2
+    ei = ur.directed_graph(5900, 18000, 71)
+    top = ur.n_self_of(ei)
+    assert top <= 5900
+    rng = np.random.RandomState(72)
+    up_edge = np.array([[5950], [7]])
+    eh = _eh(ssa, h)
+    t, c = eh.build_hash_tables(n, _t(ei, dev))
+    for step in range(8):
+        added = removed = None
+        if step == 2:    # rows top .. 5 950 gain their implicit self loop
+            new, added = ur.add_directed(ei, up_edge)
+        elif step == 5:  # ... and lose it again
+            pos = np.flatnonzero((ei[0] == 5950) & (ei[1] == 7))
+            assert pos.size == 1
+            new, removed = ur.remove_directed(ei, pos)
+        elif step % 2 == 0:
+            new, added = ur.add_directed(ei, rng.randint(0, 5900, size=(2, 3)))
+        else:
+            candidates = np.flatnonzero(ei[0] != 5950)
+            new, removed = ur.remove_directed(ei, rng.choice(candidates, size=3, replace=False))
+        dirty = expected_dirty(n, ei, new, added, removed, h)
+        if step in (2, 5):
+            assert ur.n_self_of(new) != ur.n_self_of(ei) and dirty[1][top:5951].all() and not dirty[1][5951:].any()
+        t2, c2, info = eh.update_hash_tables(t, c, n, _t(new, dev), added=_t(added, dev), removed=_t(removed, dev), return_info='masks')
+        assert t2 is t and c2 is c
+        assert_marks(ssa, dev, n, new, info, dirty, h)
+        t_ref, c_ref = eh.build_hash_tables(n, _t(new, dev))
+        for k in range(1, h + 1):
+            assert torch.equal(t[k].mh_u32, t_ref[k].mh_u32) and torch.equal(t[k].hll_u8, t_ref[k].hll_u8), f'step {step}, hop {k}'
+        _assert_cards_bar(c, c_ref)
+        assert torch.equal(c[:, 0] > 0, torch.from_numpy(np.arange(n) < ur.n_self_of(new)).to(dev)), f'step {step}: the loop memory'
+        ei = new
+    eh.check_errors()

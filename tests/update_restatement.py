@@ -73,6 +73,26 @@ def add_edges(edge_index, und_edges):
     return np.concatenate([np.asarray(edge_index, dtype=np.int64), add], axis=1), add
 
 
+def directed_graph(n, e, seed):
+    """e directed edges with uniform endpoints (copies and self loops as they fall)"""
+    return np.random.RandomState(seed).randint(0, n, size=(2, e)).astype(np.int64)
+
+
+def remove_directed(edge_index, positions):
+    """drop the directed edges at `positions` -> (new edge_index, removed [2, R])"""
+    ei = np.asarray(edge_index, dtype=np.int64)
+    pos = np.asarray(positions, dtype=np.int64)
+    keep = np.ones(ei.shape[1], dtype=bool)
+    keep[pos] = False
+    return ei[:, keep], ei[:, pos]
+
+
+def add_directed(edge_index, edges):
+    """append the directed edges [2, A] -> (new edge_index, added [2, A])"""
+    add = np.asarray(edges, dtype=np.int64).reshape(2, -1)
+    return np.concatenate([np.asarray(edge_index, dtype=np.int64), add], axis=1), add
+
+
 def changed_rows(old, new):
     """bool [N]: rows of two [N, W] tables that differ anywhere"""
     return (np.asarray(old) != np.asarray(new)).reshape(len(old), -1).any(axis=1)
