@@ -22,7 +22,8 @@
 //                      whole workgroup instead of one 16-lane group.
 // Both tiers then count a (h + 2) x (h + 2) histogram of (d_u, d_v) (h + 1 = not within h) over the visited nodes; I and the two
 // ball sizes are its prefix sums.  Integer counts: the result does not depend on the order of anything.
-// The tables and the BFS of both tiers live in ss_exact_bfs.hpp (ss_exact_nodes.hip lists the visited nodes with the same walk).
+// The tables, the BFS of both tiers, their leaf helpers and the host prelude of the entry points live in ss_exact_bfs.hpp, shared with
+// ss_exact_nodes.hip (lists the visited nodes with the same walk) and ss_sampled_nodes.hip; this file keeps its two kernels' loops.
 #include "ss_exact_bfs.hpp"
 #include "ss_feature_algebra.hpp"
 
@@ -118,10 +119,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
     __shared__ ExactLds s;
     const int t = threadIdx.x;
     const int64_t n_self = exact_n_self(g);
-    for (int i = t; i < kExactSlots; i += kExactThreads) {
-        s.key[i] = kEmpty;
-        if (i < kExactSlots / 2) s.val[i] = 0;
-    }
+    lds_clear(s);
     for (int64_t q = blockIdx.x; q < B; q += gridDim.x) {
         int64_t u, v;
         const bool ok = link_ids(links, q, N, u, v);  // (workgroup-uniform)
@@ -140,26 +138,15 @@ __global__ __launch_bounds__(kExactThreads) void exact_lds_kernel(ss_csr_graph g
         if (ovf) {
             if (t == 0) overflow[atomicAdd(&ws->count, 1)] = (int32_t)q;
             __syncthreads();
-            for (int i = t; i < kExactSlots; i += kExactThreads) {
-                s.key[i] = kEmpty;
-                if (i < kExactSlots / 2) s.val[i] = 0;
-            }
+            lds_clear(s);
             __syncthreads();
             continue;
         }
         const int cu = s.cnt[0], cv = s.cnt[1];
-        for (int i = t; i < cu + cv; i += kExactThreads) {
-            const int slot = i < cu ? s.list[0][i] : s.list[1][i - cu];
-            const uint32_t b = (s.val[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu;
-            if (i < cu || (b & 0xFFu) == 0) atomicAdd(&s.hist[exact_bucket<H>(b)], 1);  // (nodes on both sides: counted from u's list)
-        }
+        for_union(s, cu, cv, [&](int, uint32_t b) { atomicAdd(&s.hist[exact_bucket<H>(b)], 1); });  // (nodes on both sides: once)
         __syncthreads();
         if (t == 0) exact_finish<H>(s.hist, q, flags, o);
-        for (int i = t; i < cu + cv; i += kExactThreads) {
-            const int slot = i < cu ? s.list[0][i] : s.list[1][i - cu];
-            s.key[slot] = kEmpty;
-            atomicAnd(&s.val[slot >> 1], ~(0xFFFFu << (16 * (slot & 1))));  // (the other half may be cleared by another lane)
-        }
+        for (int i = t; i < cu + cv; i += kExactThreads) lds_release(s, i < cu ? s.list[0][i] : s.list[1][i - cu]);
         __syncthreads();
     }
 }
@@ -180,9 +167,8 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
     const ExactSlot sl = exact_slot(arena, N);
     const int total = ws->count;
     for (;;) {
+        large_claim(ws, overflow, total, &next_q);
         if (t == 0) {
-            const int i = atomicAdd(&ws->cursor, 1);
-            next_q = i < total ? (int64_t)overflow[i] : -1;
             cnt[0] = cnt[1] = 0;
             n_big = 0;
         }
@@ -197,36 +183,12 @@ __global__ __launch_bounds__(kExactThreads) void exact_large_kernel(ss_csr_graph
         }
         exact_slot_bfs<H>(sl, g, u, v, n_self, flags, cnt, big, &n_big);
         const int64_t cu = cnt[0], cv = cnt[1];
-        for (int64_t i = t; i < cu + cv; i += kExactThreads) {
-            const int32_t x = i < cu ? sl.list[0][i] : sl.list[1][i - cu];
-            const uint32_t b = slot_byte(sl, x);
-            if (i < cu || (b & 0xFFu) == 0) atomicAdd(&hist[exact_bucket<H>(b)], 1);
-        }
+        for_union(sl, cu, cv, [&](int32_t, uint32_t b) { atomicAdd(&hist[exact_bucket<H>(b)], 1); });
         __syncthreads();
         if (t == 0) exact_finish<H>(hist, q, flags, o);
-        for (int64_t i = t; i < cu + cv; i += kExactThreads) {  // back to all-zero for the next pair
-            const int32_t x = i < cu ? sl.list[0][i] : sl.list[1][i - cu];
-            atomicAnd(&sl.dist[x >> 2], ~(0xFFu << (8 * (x & 3))));
-        }
+        for (int64_t i = t; i < cu + cv; i += kExactThreads) slot_clear(sl, i < cu ? sl.list[0][i] : sl.list[1][i - cu]);  // all-zero again
         __syncthreads();
     }
-}
-
-template <int H>
-void launch_exact_lds(const ss_csr_graph &g, const int64_t *links, int64_t B, int64_t N, int limit, uint32_t flags, const ExactOut &o,
-                      ExactWs *ws, int32_t *overflow, hipStream_t s)
-{
-    const int64_t blocks = B < kExactGrid ? B : kExactGrid;
-    hipLaunchKernelGGL(exact_lds_kernel<H>, dim3((unsigned)blocks), dim3(kExactThreads), 0, s, g, links, B, N, limit, flags, o, ws,
-                       overflow);
-}
-
-template <int H>
-void launch_exact_large(const ss_csr_graph &g, const int64_t *links, int64_t N, uint32_t flags, const ExactOut &o, ExactWs *ws,
-                        const int32_t *overflow, uint32_t *arena, int slots, hipStream_t s)
-{
-    hipLaunchKernelGGL(exact_large_kernel<H>, dim3((unsigned)slots), dim3(kExactThreads), 0, s, g, links, N, flags, o, ws, overflow,
-                       arena);
 }
 
 }  // namespace ss
@@ -243,42 +205,22 @@ extern "C" size_t ss_exact_slot_bytes(int64_t N)
     return 4 * (size_t)ss::exact_slot_words(N);
 }
 
-// argument checks before any launch: SS_ERR_UNSUPPORTED for h outside [1, 3] (as ss_pair_features), SS_ERR_INVALID_ARG for negative
-// sizes or null pointers, 1 (nothing to do) for B == 0
-static int exact_check(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, float *feats, void *workspace,
-                       size_t workspace_bytes)
-{
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
-    if (B == 0) return 1;
-    if (!graph || !links || !feats || !workspace || N == 0 || N >= ((int64_t)1 << 31) || graph->num_nodes != N || !graph->rowptr ||
-        !graph->col)
-        return SS_ERR_INVALID_ARG;
-    const size_t need = ss_exact_workspace_bytes(B);
-    if (need == 0) return SS_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return SS_ERR_WORKSPACE;
-    return SS_OK;
-}
-
 extern "C" int ss_exact_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags,
                               int32_t lds_max_nodes, int32_t *I, int32_t *balls, float *feats, int32_t *err_flag, void *workspace,
                               size_t workspace_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = exact_check(graph, links, B, N, h, feats, workspace, workspace_bytes);
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, feats != nullptr);
+    if (rc == SS_OK) rc = tier_lds(lds_max_nodes, workspace, stream, t);
     if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (lds_max_nodes < 0) return SS_ERR_INVALID_ARG;
-    const int limit = lds_max_nodes < kExactMaxNodes ? lds_max_nodes : kExactMaxNodes;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    int32_t *overflow = reinterpret_cast<int32_t *>(ws + 1);
-    if (hipMemsetAsync(ws, 0, sizeof(ExactWs), s) != hipSuccess) return SS_ERR_LAUNCH;
+    if (hipMemsetAsync(t.ws, 0, sizeof(ExactWs), t.stream) != hipSuccess) return SS_ERR_LAUNCH;
     const ExactOut o = {I, balls, feats, err_flag};
-    switch (h) {
-        case 1: launch_exact_lds<1>(*graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-        case 2: launch_exact_lds<2>(*graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-        default: launch_exact_lds<3>(*graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-    }
+    const dim3 grid((unsigned)(B < kExactGrid ? B : kExactGrid)), block(kExactThreads);
+    dispatch_h(h, [&](auto H) {
+        hipLaunchKernelGGL(exact_lds_kernel<decltype(H)::value>, grid, block, 0, t.stream, *graph, links, B, N, t.limit, flags, o, t.ws,
+                           t.overflow);
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -288,20 +230,15 @@ extern "C" int ss_exact_large(const ss_csr_graph *graph, const int64_t *links, i
                               void *arena, size_t arena_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = exact_check(graph, links, B, N, h, feats, workspace, workspace_bytes);
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, feats != nullptr);
+    if (rc == SS_OK) rc = tier_large(N, slots, arena, arena_bytes, workspace, stream, t);
     if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (slots <= 0 || !arena) return SS_ERR_INVALID_ARG;
-    if (arena_bytes / ss_exact_slot_bytes(N) < (size_t)slots) return SS_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    const int32_t *overflow = reinterpret_cast<const int32_t *>(ws + 1);
-    const ExactOut o = {I, balls, feats, nullptr};
-    uint32_t *a = static_cast<uint32_t *>(arena);
-    switch (h) {
-        case 1: launch_exact_large<1>(*graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-        case 2: launch_exact_large<2>(*graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-        default: launch_exact_large<3>(*graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-    }
+    const ExactOut o = {I, balls, feats, nullptr};  // (ss_exact_pairs has zeroed the cursor)
+    dispatch_h(h, [&](auto H) {
+        hipLaunchKernelGGL(exact_large_kernel<decltype(H)::value>, dim3((unsigned)slots), dim3(kExactThreads), 0, t.stream, *graph, links,
+                           N, flags, o, t.ws, t.overflow, static_cast<uint32_t *>(arena));
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

@@ -1,9 +1,16 @@
-// ss_exact_bfs.hpp -- the two-sided BFS of one link, shared by the exact counts (ss_exact.hip) and the exact node lists
-// (ss_exact_nodes.hip): the on-chip tier's LDS hash table and the large tier's slot of device memory, each with the walk that fills it.
-// What a kernel does with the visited nodes afterwards (a histogram, a sorted list) is its own; see ss_exact.hip for the tiers.  The two
-// ways a row is put in id order -- the on-chip sort and the ordered scan of a slot's bytes -- are here too, shared by the node lists
-// and the sampled node lists (ss_sampled_nodes.hip), which walks in its own way and uses the tables, the slots and these two.
+// ss_exact_bfs.hpp -- everything the two tiers of the exact family share: the exact counts (ss_exact.hip), the exact node lists
+// (ss_exact_nodes.hip) and the sampled node lists (ss_sampled_nodes.hip) keep their own kernels (loop, barriers, what a link's end
+// writes) and take the rest from here:
+//   on-chip tier  the LDS hash table with its leaf helpers (clear, value, release, find, the union walk), the two-sided BFS into it,
+//                 the bitonic sort and the ordered emit of a table's chosen keys
+//   large tier    the slot of device memory with its leaf helpers (byte, clear, the union walk), the two-sided BFS into it, the
+//                 claim of the next overflow entry and the ordered scan of a slot's bytes
+//   both          a fill pass's row fetch
+//   host          the argument checks (tier_check), what an entry point hands its launch (Tier, tier_lds, tier_large), dispatch_h
+// The sampled walk is its own (one joint walk, its own level byte: ss_sampled_nodes.hip); it uses the tables, the slots and the leaves.
 #pragma once
+#include <type_traits>
+
 #include "ss_common.hpp"
 
 namespace ss {
@@ -44,10 +51,39 @@ struct ExactLds {
     int cnt[2];
 };
 
+// where the probe for node x starts
+__device__ __forceinline__ uint32_t lds_hash(uint32_t x) { return (x * 2654435761u) >> (32 - kExactSlotsLog); }
+
+// an empty table (whole workgroup; no barrier inside)
+__device__ __forceinline__ void lds_clear(ExactLds &s)
+{
+    for (int i = threadIdx.x; i < kExactSlots; i += kExactThreads) {
+        s.key[i] = kEmpty;
+        if (i < kExactSlots / 2) s.val[i] = 0;
+    }
+}
+
+__device__ __forceinline__ uint32_t lds_value(const ExactLds &s, int slot) { return (s.val[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu; }
+
+// one slot back to empty: the key and its half of the value word (the other half may be cleared by another lane)
+__device__ __forceinline__ void lds_release(ExactLds &s, int slot)
+{
+    s.key[slot] = kEmpty;
+    atomicAnd(&s.val[slot >> 1], ~(0xFFFFu << (16 * (slot & 1))));
+}
+
+// slot of a node x that is in the table (lds_slot's probe without the insert)
+__device__ __forceinline__ int lds_find(const ExactLds &s, uint32_t x)
+{
+    uint32_t i = lds_hash(x);
+    while (s.key[i] != x) i = (i + 1) & (kExactSlots - 1);
+    return (int)i;
+}
+
 // slot of node x (inserted if new; -1: the pair has passed its node limit)
 __device__ __forceinline__ int lds_slot(ExactLds &s, uint32_t x, int limit)
 {
-    uint32_t i = (x * 2654435761u) >> (32 - kExactSlotsLog);
+    uint32_t i = lds_hash(x);
     for (int probe = 0; probe < kExactSlots; ++probe) {
         const uint32_t k = s.key[i];
         if (k == x) return (int)i;
@@ -142,6 +178,43 @@ __device__ __forceinline__ void lds_bitonic_sort(uint32_t *sorted, int P)
         }
 }
 
+// the union of the two balls (whole workgroup): f(slot, value) for u's list, then for the nodes only v reached
+template <class F>
+__device__ __forceinline__ void for_union(const ExactLds &s, int cu, int cv, F f)
+{
+    for (int i = threadIdx.x; i < cu + cv; i += kExactThreads) {
+        const int slot = i < cu ? s.list[0][i] : s.list[1][i - cu];
+        const uint32_t b = lds_value(s, slot);
+        if (i < cu || (b & 0xFFu) == 0) f(slot, b);
+    }
+}
+
+// chosen keys of the table in ascending order (whole workgroup): sorted[0 .. n) holds them (n workgroup-uniform, written since the
+// last barrier at the earliest); they are padded to a power of two (no node id is 2^32 - 1: N < 2^31), sorted, and emit(i, x, slot)
+// is called for place i < min(n, len) with its key and the key's slot (n == len: a store never leaves the row)
+template <class Emit>
+__device__ __forceinline__ void lds_ordered_emit(const ExactLds &s, uint32_t *sorted, int n, int64_t len, Emit emit)
+{
+    const int t = threadIdx.x;
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int i = n + t; i < P; i += kExactThreads) sorted[i] = kEmpty;
+    __syncthreads();
+    lds_bitonic_sort(sorted, P);
+    const int m = n < len ? n : (int)len;
+    for (int i = t; i < m; i += kExactThreads) {
+        const uint32_t x = sorted[i];
+        emit(i, x, lds_find(s, x));
+    }
+}
+
+// a fill pass's row of link q
+__device__ __forceinline__ void fill_row(const int64_t *rowptr, int64_t q, int64_t &row, int64_t &len)
+{
+    row = rowptr[q];
+    len = rowptr[q + 1] - row;
+}
+
 // ---- large tier -----------------------------------------------------------------------------------------------------------------
 // slot arena: uint32 dist[ceil(N / 4)] (one byte per node: bits 0-3 side u, 4-7 side v), int32 list_u[N], int32 list_v[N]
 __host__ __device__ __forceinline__ int64_t exact_dist_words(int64_t N) { return (N + 3) / 4; }
@@ -172,6 +245,30 @@ __device__ __forceinline__ uint32_t slot_byte(const ExactSlot &sl, int32_t x)
     const uint32_t w = __hip_atomic_load(&sl.dist[x >> 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t b = (w >> (8 * (x & 3))) & 0xFFu;
     return (b & 0xFu) | ((b >> 4) << 8);  // -> the LDS tier's layout for exact_bucket
+}
+
+// the byte of node x back to zero
+__device__ __forceinline__ void slot_clear(const ExactSlot &sl, int32_t x) { atomicAnd(&sl.dist[x >> 2], ~(0xFFu << (8 * (x & 3)))); }
+
+// the union of the two balls (whole workgroup): f(node, slot_byte) for u's list, then for the nodes only v reached
+template <class F>
+__device__ __forceinline__ void for_union(const ExactSlot &sl, int64_t cu, int64_t cv, F f)
+{
+    for (int64_t i = threadIdx.x; i < cu + cv; i += kExactThreads) {
+        const int32_t x = i < cu ? sl.list[0][i] : sl.list[1][i - cu];
+        const uint32_t b = slot_byte(sl, x);
+        if (i < cu || (b & 0xFFu) == 0) f(x, b);
+    }
+}
+
+// thread 0 takes the next entry of the overflow list into the workgroup's *next_q (-1: none left; `total` = ws->count); the caller's
+// barrier hands it to the other threads
+__device__ __forceinline__ void large_claim(ExactWs *ws, const int32_t *overflow, int total, int64_t *next_q)
+{
+    if (threadIdx.x == 0) {
+        const int i = atomicAdd(&ws->cursor, 1);
+        *next_q = i < total ? (int64_t)overflow[i] : -1;
+    }
 }
 
 // both BFSs of the pair (u, v) into the slot (whole workgroup).  cnt[2], big[kBigList] and *n_big are the workgroup's LDS; the caller
@@ -284,6 +381,59 @@ __device__ __forceinline__ void slot_ordered_scan(const ExactSlot &sl, int64_t N
             }
         }
         done += all;
+    }
+}
+
+// ---- host side of an entry point ------------------------------------------------------------------------------------------------
+// argument checks before any launch: SS_ERR_UNSUPPORTED for h outside [1, 3] (as ss_pair_features), SS_ERR_INVALID_ARG for negative
+// sizes, null pointers or missing outputs, SS_ERR_WORKSPACE for a workspace below ss_exact_workspace_bytes(B), 1 (nothing to do) for B == 0
+inline int tier_check(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, const void *workspace,
+                      size_t workspace_bytes, bool outputs)
+{
+    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
+    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
+    if (B == 0) return 1;
+    if (!graph || !links || !outputs || !workspace || N == 0 || N >= ((int64_t)1 << 31) || graph->num_nodes != N || !graph->rowptr ||
+        !graph->col)
+        return SS_ERR_INVALID_ARG;
+    const size_t need = ss_exact_workspace_bytes(B);
+    if (need == 0) return SS_ERR_INVALID_ARG;
+    if (workspace_bytes < need) return SS_ERR_WORKSPACE;
+    return SS_OK;
+}
+
+struct Tier {
+    int limit;          // on-chip node limit (on-chip entry points)
+    ExactWs *ws;
+    int32_t *overflow;  // [B] behind ws
+    hipStream_t stream;
+};
+
+// what an on-chip entry point launches with, after a tier_check that returned SS_OK
+inline int tier_lds(int32_t lds_max_nodes, void *workspace, void *stream, Tier &t)
+{
+    if (lds_max_nodes < 0) return SS_ERR_INVALID_ARG;
+    ExactWs *ws = static_cast<ExactWs *>(workspace);
+    t = {lds_max_nodes < kExactMaxNodes ? lds_max_nodes : kExactMaxNodes, ws, reinterpret_cast<int32_t *>(ws + 1), (hipStream_t)stream};
+    return SS_OK;
+}
+
+// the same for a large-tier entry point, with the checks of its slots and arena
+inline int tier_large(int64_t N, int32_t slots, const void *arena, size_t arena_bytes, void *workspace, void *stream, Tier &t)
+{
+    if (slots <= 0 || !arena) return SS_ERR_INVALID_ARG;
+    if (arena_bytes / ss_exact_slot_bytes(N) < (size_t)slots) return SS_ERR_WORKSPACE;
+    return tier_lds(0, workspace, stream, t);
+}
+
+// f(std::integral_constant<int, h>) for the kernels templated on the hop count (h checked: 1 .. 3)
+template <class F>
+inline void dispatch_h(int32_t h, F f)
+{
+    switch (h) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
     }
 }
 

@@ -1,6 +1,7 @@
 // ss_exact_nodes.hip -- exact subgraph node lists: per link (u, v) every node of B_h(u) | B_h(v), ascending by id, with the pair of
-// distances (d_u, d_v) (ElphHashes.exact_subgraph_nodes).  The walk is the two-sided BFS of the exact counts (ss_exact_bfs.hpp, tiers
-// as in ss_exact.hip); what differs is the end of a pair: the counts fold the visited nodes into a histogram, this file writes them out.
+// distances (d_u, d_v) (ElphHashes.exact_subgraph_nodes).  The walk is the two-sided BFS of the exact counts (ss_exact_bfs.hpp, which
+// also holds the tiers' leaf helpers and the entry points' host prelude; tiers as in ss_exact.hip); what differs is the end of a pair:
+// the counts fold the visited nodes into a histogram, this file writes them out.
 //
 // A root is always in its own ball at distance 0 here (n_self = N is handed to the BFS: a node at or above max(edge_index) + 1 has no
 // in-edges, so nothing else changes), which is what a node list wants; the sketch balls of such a node are empty.
@@ -32,14 +33,6 @@ struct NodesOut {
 template <int H>
 __device__ __forceinline__ uint8_t nodes_distance(uint32_t bits) { return (uint8_t)(bits ? __builtin_ctz(bits) : H + 1); }
 
-__device__ __forceinline__ void lds_clear_table(ExactLds &s)
-{
-    for (int i = threadIdx.x; i < kExactSlots; i += kExactThreads) {
-        s.key[i] = kEmpty;
-        if (i < kExactSlots / 2) s.val[i] = 0;
-    }
-}
-
 // ---- on-chip tier ---------------------------------------------------------------------------------------------------------------
 template <int H, bool FILL>
 __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g, const int64_t *__restrict__ links, int64_t B, int64_t N,
@@ -50,14 +43,13 @@ __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g
     __shared__ uint32_t sorted[FILL ? kExactMaxNodes : 1];
     __shared__ int n_sorted;
     const int t = threadIdx.x;
-    lds_clear_table(s);
+    lds_clear(s);
     for (int64_t q = blockIdx.x; q < B; q += gridDim.x) {
         int64_t u, v;
         const bool ok = link_ids(links, q, N, u, v);  // (workgroup-uniform)
         int64_t row = 0, len = 0;
         if (FILL) {
-            row = o.rowptr[q];
-            len = o.rowptr[q + 1] - row;
+            fill_row(o.rowptr, q, row, len);
             if (!ok || len <= 0 || len > limit) continue;  // capped, or the large tier's (nothing touched: no barrier needed)
         }
         if (t == 0) {
@@ -78,7 +70,7 @@ __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g
         if (ovf) {  // (fill pass: never -- the row length is the number of keys, and it is within the limit)
             if (!FILL && t == 0) overflow[atomicAdd(&ws->count, 1)] = (int32_t)q;
             __syncthreads();
-            lds_clear_table(s);
+            lds_clear(s);
             __syncthreads();
             continue;
         }
@@ -86,35 +78,18 @@ __global__ __launch_bounds__(kExactThreads) void nodes_lds_kernel(ss_csr_graph g
         if (!FILL) {
             if (t == 0) o.counts[q] = s.n_nodes;
         } else {
-            for (int i = t; i < cu + cv; i += kExactThreads) {  // the union: u's list, then what only v reached
-                const int slot = i < cu ? s.list[0][i] : s.list[1][i - cu];
-                const uint32_t b = (s.val[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu;
-                if (i < cu || (b & 0xFFu) == 0) sorted[atomicAdd(&n_sorted, 1)] = s.key[slot];
-            }
+            for_union(s, cu, cv, [&](int slot, uint32_t) { sorted[atomicAdd(&n_sorted, 1)] = s.key[slot]; });
             __syncthreads();
-            const int n = n_sorted;  // (<= s.n_nodes <= limit <= kExactMaxNodes)
-            int P = 1;
-            while (P < n) P <<= 1;
-            for (int i = n + t; i < P; i += kExactThreads) sorted[i] = kEmpty;  // (no node id is 2^32 - 1: N < 2^31)
-            __syncthreads();
-            lds_bitonic_sort(sorted, P);
-            const int m = n < len ? n : (int)len;  // (n == len; a store never leaves the row)
-            for (int i = t; i < m; i += kExactThreads) {
-                const uint32_t x = sorted[i];
-                uint32_t at = (x * 2654435761u) >> (32 - kExactSlotsLog);  // (lds_slot's probe; x is in the table)
-                while (s.key[at] != x) at = (at + 1) & (kExactSlots - 1);
-                const uint32_t b = (s.val[at >> 1] >> (16 * (at & 1))) & 0xFFFFu;
+            // (n_sorted <= s.n_nodes <= limit <= kExactMaxNodes)
+            lds_ordered_emit(s, sorted, n_sorted, len, [&](int i, uint32_t x, int slot) {
+                const uint32_t b = lds_value(s, slot);
                 o.ids[row + i] = (int64_t)x;
                 o.dist[2 * (row + i)] = nodes_distance<H>(b & 0xFFu);
                 o.dist[2 * (row + i) + 1] = nodes_distance<H>(b >> 8);
-            }
+            });
             __syncthreads();
         }
-        for (int i = t; i < cu + cv; i += kExactThreads) {
-            const int slot = i < cu ? s.list[0][i] : s.list[1][i - cu];
-            s.key[slot] = kEmpty;
-            atomicAnd(&s.val[slot >> 1], ~(0xFFFFu << (16 * (slot & 1))));  // (the other half may be cleared by another lane)
-        }
+        for (int i = t; i < cu + cv; i += kExactThreads) lds_release(s, i < cu ? s.list[0][i] : s.list[1][i - cu]);
         __syncthreads();
     }
 }
@@ -137,9 +112,8 @@ __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph
     const ExactSlot sl = exact_slot(arena, N);
     const int total = ws->count;
     for (;;) {
+        large_claim(ws, overflow, total, &next_q);
         if (t == 0) {
-            const int i = atomicAdd(&ws->cursor, 1);
-            next_q = i < total ? (int64_t)overflow[i] : -1;
             cnt[0] = cnt[1] = 0;
             n_big = 0;
             only_v = 0;
@@ -151,8 +125,7 @@ __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph
         int64_t row = 0, len = 0;
         bool skip = !link_ids(links, q, N, u, v);  // (never listed: the on-chip tier has answered such a pair)
         if (FILL && !skip) {
-            row = o.rowptr[q];
-            len = o.rowptr[q + 1] - row;
+            fill_row(o.rowptr, q, row, len);
             skip = len <= 0;  // capped by max_nodes
         }
         if (skip) {
@@ -167,10 +140,7 @@ __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph
             if (mine) atomicAdd(&only_v, mine);
             __syncthreads();
             if (t == 0) o.counts[q] = (int32_t)cu + only_v;
-            for (int64_t i = t; i < cu + cv; i += kExactThreads) {  // back to all-zero for the next pair
-                const int32_t x = i < cu ? sl.list[0][i] : sl.list[1][i - cu];
-                atomicAnd(&sl.dist[x >> 2], ~(0xFFu << (8 * (x & 3))));
-            }
+            for (int64_t i = t; i < cu + cv; i += kExactThreads) slot_clear(sl, i < cu ? sl.list[0][i] : sl.list[1][i - cu]);  // all-zero again
             __syncthreads();
             continue;
         }
@@ -186,67 +156,27 @@ __global__ __launch_bounds__(kExactThreads) void nodes_large_kernel(ss_csr_graph
     }
 }
 
-template <int H>
-void launch_nodes_lds(bool fill, const ss_csr_graph &g, const int64_t *links, int64_t B, int64_t N, int limit, uint32_t flags,
-                      const NodesOut &o, ExactWs *ws, int32_t *overflow, hipStream_t s)
-{
-    const int64_t most = fill ? kNodesFillGrid : kExactGrid;
-    const dim3 grid((unsigned)(B < most ? B : most)), block(kExactThreads);
-    if (fill)
-        hipLaunchKernelGGL((nodes_lds_kernel<H, true>), grid, block, 0, s, g, links, B, N, limit, flags, o, ws, overflow);
-    else
-        hipLaunchKernelGGL((nodes_lds_kernel<H, false>), grid, block, 0, s, g, links, B, N, limit, flags, o, ws, overflow);
-}
-
-template <int H>
-void launch_nodes_large(bool fill, const ss_csr_graph &g, const int64_t *links, int64_t N, uint32_t flags, const NodesOut &o, ExactWs *ws,
-                        const int32_t *overflow, uint32_t *arena, int slots, hipStream_t s)
-{
-    const dim3 grid((unsigned)slots), block(kExactThreads);
-    if (fill)
-        hipLaunchKernelGGL((nodes_large_kernel<H, true>), grid, block, 0, s, g, links, N, flags, o, ws, overflow, arena);
-    else
-        hipLaunchKernelGGL((nodes_large_kernel<H, false>), grid, block, 0, s, g, links, N, flags, o, ws, overflow, arena);
-}
-
 }  // namespace ss
-
-// argument checks before any launch (those of ss_exact_pairs / ss_exact_large): 1 = nothing to do
-static int nodes_check(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, int32_t *counts,
-                       const int64_t *rowptr, int64_t *ids, uint8_t *dist, void *workspace, size_t workspace_bytes)
-{
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
-    if (B == 0) return 1;
-    if (!graph || !links || !workspace || N == 0 || N >= ((int64_t)1 << 31) || graph->num_nodes != N || !graph->rowptr || !graph->col)
-        return SS_ERR_INVALID_ARG;
-    if (rowptr ? (!ids || !dist) : !counts) return SS_ERR_INVALID_ARG;
-    const size_t need = ss_exact_workspace_bytes(B);
-    if (need == 0) return SS_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return SS_ERR_WORKSPACE;
-    return SS_OK;
-}
 
 extern "C" int ss_exact_nodes_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, uint32_t flags,
                                     int32_t lds_max_nodes, int32_t *counts, const int64_t *rowptr, int64_t *ids, uint8_t *dist,
                                     int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = nodes_check(graph, links, B, N, h, counts, rowptr, ids, dist, workspace, workspace_bytes);
-    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (lds_max_nodes < 0) return SS_ERR_INVALID_ARG;
-    const int limit = lds_max_nodes < kExactMaxNodes ? lds_max_nodes : kExactMaxNodes;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    int32_t *overflow = reinterpret_cast<int32_t *>(ws + 1);
     const bool fill = rowptr != nullptr;
-    if (!fill && hipMemsetAsync(ws, 0, sizeof(ExactWs), s) != hipSuccess) return SS_ERR_LAUNCH;
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, fill ? ids && dist : counts != nullptr);
+    if (rc == SS_OK) rc = tier_lds(lds_max_nodes, workspace, stream, t);
+    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
+    if (!fill && hipMemsetAsync(t.ws, 0, sizeof(ExactWs), t.stream) != hipSuccess) return SS_ERR_LAUNCH;
     const NodesOut o = {counts, rowptr, ids, dist, err_flag};
-    switch (h) {
-        case 1: launch_nodes_lds<1>(fill, *graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-        case 2: launch_nodes_lds<2>(fill, *graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-        default: launch_nodes_lds<3>(fill, *graph, links, B, N, limit, flags, o, ws, overflow, s); break;
-    }
+    const int64_t most = fill ? kNodesFillGrid : kExactGrid;
+    const dim3 grid((unsigned)(B < most ? B : most)), block(kExactThreads);
+    dispatch_h(h, [&](auto H) {
+        constexpr int kH = decltype(H)::value;
+        const auto kernel = fill ? nodes_lds_kernel<kH, true> : nodes_lds_kernel<kH, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, t.stream, *graph, links, B, N, t.limit, flags, o, t.ws, t.overflow);
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -256,22 +186,19 @@ extern "C" int ss_exact_nodes_large(const ss_csr_graph *graph, const int64_t *li
                                     size_t workspace_bytes, int32_t slots, void *arena, size_t arena_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = nodes_check(graph, links, B, N, h, counts, rowptr, ids, dist, workspace, workspace_bytes);
-    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (slots <= 0 || !arena) return SS_ERR_INVALID_ARG;
-    if (arena_bytes / ss_exact_slot_bytes(N) < (size_t)slots) return SS_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    const int32_t *overflow = reinterpret_cast<const int32_t *>(ws + 1);
     const bool fill = rowptr != nullptr;
-    if (hipMemsetAsync(&ws->cursor, 0, sizeof(int32_t), s) != hipSuccess) return SS_ERR_LAUNCH;  // (the list is walked once per pass)
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, fill ? ids && dist : counts != nullptr);
+    if (rc == SS_OK) rc = tier_large(N, slots, arena, arena_bytes, workspace, stream, t);
+    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
+    if (hipMemsetAsync(&t.ws->cursor, 0, sizeof(int32_t), t.stream) != hipSuccess) return SS_ERR_LAUNCH;  // (the list is walked once per pass)
     const NodesOut o = {counts, rowptr, ids, dist, nullptr};
-    uint32_t *a = static_cast<uint32_t *>(arena);
-    switch (h) {
-        case 1: launch_nodes_large<1>(fill, *graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-        case 2: launch_nodes_large<2>(fill, *graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-        default: launch_nodes_large<3>(fill, *graph, links, N, flags, o, ws, overflow, a, slots, s); break;
-    }
+    dispatch_h(h, [&](auto H) {
+        constexpr int kH = decltype(H)::value;
+        const auto kernel = fill ? nodes_large_kernel<kH, true> : nodes_large_kernel<kH, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)slots), dim3(kExactThreads), 0, t.stream, *graph, links, N, flags, o, t.ws, t.overflow,
+                           static_cast<uint32_t *>(arena));
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

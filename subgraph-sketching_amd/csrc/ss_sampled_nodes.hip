@@ -11,7 +11,8 @@
 // Two lists per link: list 0 the visited nodes in the order they were reached (a hop's fringe is a range of it), list 1 the kept ones
 // (a hop's frontier is a range of it).
 //
-// Tiers as in ss_exact_nodes.hip, and two passes over the links (count, one host read for the allocation, fill):
+// Tiers as in ss_exact_nodes.hip (tables, slots, their leaf helpers and the entry points' host prelude: ss_exact_bfs.hpp; the helpers
+// that know this walk's level byte are here), and two passes over the links (count, one host read for the allocation, fill):
 //   on-chip   visited stays within the LDS table of ss_exact_bfs.hpp (key / val / the two slot lists; the value half holds the level
 //             byte).  A link whose visited set passes the node limit goes to the batch's overflow list and gets state bit 1, which
 //             is how the fill pass knows the tier (a row's length says nothing about the size of what was visited).  Fill: the kept
@@ -47,16 +48,6 @@ struct SampledOut {
 };
 
 // ---- on-chip tier ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sampled_lds_clear(ExactLds &s)
-{
-    for (int i = threadIdx.x; i < kExactSlots; i += kExactThreads) {
-        s.key[i] = kEmpty;
-        if (i < kExactSlots / 2) s.val[i] = 0;
-    }
-}
-
-__device__ __forceinline__ uint32_t sampled_lds_byte(const ExactLds &s, int slot) { return (s.val[slot >> 1] >> (16 * (slot & 1))) & 0xFFu; }
-
 // first visit of x: into the table and onto list 0 (nothing when the link has passed its node limit: s.ovf is set)
 __device__ __forceinline__ void sampled_lds_visit(ExactLds &s, uint32_t x, int limit)
 {
@@ -87,14 +78,13 @@ __global__ __launch_bounds__(kExactThreads) void sampled_lds_kernel(ss_csr_graph
     __shared__ uint32_t sorted[FILL ? kExactMaxNodes : 1];
     const int t = threadIdx.x;
     const int grp = t / kRow, lane = t & (kRow - 1);
-    sampled_lds_clear(s);
+    lds_clear(s);
     for (int64_t q = blockIdx.x; q < B; q += gridDim.x) {
         int64_t u, v;
         const bool ok = link_ids(links, q, N, u, v);  // (workgroup-uniform)
         int64_t row = 0, len = 0;
         if (FILL) {
-            row = o.rowptr[q];
-            len = o.rowptr[q + 1] - row;
+            fill_row(o.rowptr, q, row, len);
             if (!ok || len <= 0 || (o.state[q] & kStateSlot)) continue;  // emptied, or the slot tier's (nothing touched: no barrier needed)
         }
         __syncthreads();  // the table is empty and the last link's reads of s are over
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(kExactThreads) void sampled_lds_kernel(ss_csr_graph
                 o.state[q] = kStateSlot;
             }
             __syncthreads();
-            sampled_lds_clear(s);
+            lds_clear(s);
             continue;
         }
         const int visited = s.cnt[0] < kExactMaxNodes ? s.cnt[0] : kExactMaxNodes, kept = s.cnt[1] < kExactMaxNodes ? s.cnt[1] : kExactMaxNodes;
@@ -175,26 +165,14 @@ __global__ __launch_bounds__(kExactThreads) void sampled_lds_kernel(ss_csr_graph
                 o.state[q] = dropped ? kStateSampled : 0;
             }
         } else {
-            int P = 1;
-            while (P < kept) P <<= 1;
-            for (int i = t; i < P; i += kExactThreads) sorted[i] = i < kept ? s.key[s.list[1][i]] : kEmpty;  // (no node id is 2^32 - 1)
-            __syncthreads();
-            lds_bitonic_sort(sorted, P);
-            const int n = kept < len ? kept : (int)len;  // (kept == len; a store never leaves the row)
-            for (int i = t; i < n; i += kExactThreads) {
-                const uint32_t x = sorted[i];
-                uint32_t at = (x * 2654435761u) >> (32 - kExactSlotsLog);  // (lds_slot's probe; x is in the table)
-                while (s.key[at] != x) at = (at + 1) & (kExactSlots - 1);
+            for (int i = t; i < kept; i += kExactThreads) sorted[i] = s.key[s.list[1][i]];
+            lds_ordered_emit(s, sorted, kept, len, [&](int i, uint32_t x, int slot) {
                 o.ids[row + i] = (int64_t)x;
-                o.hop[row + i] = (uint8_t)((sampled_lds_byte(s, (int)at) & 0x7Fu) - 1);
-            }
+                o.hop[row + i] = (uint8_t)((lds_value(s, slot) & 0x7Fu) - 1);
+            });
             __syncthreads();
         }
-        for (int i = t; i < visited; i += kExactThreads) {  // back to an empty table
-            const int slot = s.list[0][i];
-            s.key[slot] = kEmpty;
-            atomicAnd(&s.val[slot >> 1], ~(0xFFFFu << (16 * (slot & 1))));  // (the other half may be cleared by another lane)
-        }
+        for (int i = t; i < visited; i += kExactThreads) lds_release(s, s.list[0][i]);  // back to an empty table
     }
 }
 
@@ -213,7 +191,6 @@ __device__ __forceinline__ uint32_t sampled_slot_byte(const ExactSlot &sl, int32
 {
     return (__hip_atomic_load(&sl.dist[x >> 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (8 * (x & 3))) & 0xFFu;
 }
-__device__ __forceinline__ void sampled_slot_clear(const ExactSlot &sl, int32_t x) { atomicAnd(&sl.dist[x >> 2], ~(0xFFu << (8 * (x & 3)))); }
 
 template <bool FILL>
 __global__ __launch_bounds__(kExactThreads) void sampled_slot_kernel(ss_csr_graph g, const int64_t *__restrict__ links, int64_t N, SampledArgs a,
@@ -232,11 +209,8 @@ __global__ __launch_bounds__(kExactThreads) void sampled_slot_kernel(ss_csr_grap
     const int total = ws->count;
     for (;;) {
         __syncthreads();  // the last link's reads of the LDS words are over
-        if (t == 0) {
-            const int i = atomicAdd(&ws->cursor, 1);
-            next_q = i < total ? (int64_t)overflow[i] : -1;
-            n_big = 0;
-        }
+        large_claim(ws, overflow, total, &next_q);
+        if (t == 0) n_big = 0;
         __syncthreads();
         const int64_t q = next_q;
         if (q < 0) break;
@@ -244,8 +218,7 @@ __global__ __launch_bounds__(kExactThreads) void sampled_slot_kernel(ss_csr_grap
         int64_t row = 0, len = 0;
         bool skip = !link_ids(links, q, N, u, v);  // (never listed: the on-chip tier has answered such a link)
         if (FILL && !skip) {
-            row = o.rowptr[q];
-            len = o.rowptr[q + 1] - row;
+            fill_row(o.rowptr, q, row, len);
             skip = len <= 0;  // emptied by max_nodes
         }
         if (skip) continue;
@@ -333,13 +306,13 @@ __global__ __launch_bounds__(kExactThreads) void sampled_slot_kernel(ss_csr_grap
                 o.counts[q] = kept;
                 o.state[q] = kStateSlot | (dropped ? kStateSampled : 0);
             }
-            for (int i = t; i < visited; i += kExactThreads) sampled_slot_clear(sl, sl.list[0][i]);  // back to all-zero for the next link
+            for (int i = t; i < visited; i += kExactThreads) slot_clear(sl, sl.list[0][i]);  // back to all-zero for the next link
             continue;
         }
         // the rejected nodes are cleared through list 0; what stays non-zero is the row
         for (int i = t; i < visited; i += kExactThreads) {
             const int32_t x = sl.list[0][i];
-            if (sampled_slot_byte(sl, x) == 0x80u) sampled_slot_clear(sl, x);
+            if (sampled_slot_byte(sl, x) == 0x80u) slot_clear(sl, x);
         }
         __syncthreads();
         // the row holds exactly the non-zero bytes (a store never leaves it); the scan leaves them all zero for the next link
@@ -354,22 +327,12 @@ __global__ __launch_bounds__(kExactThreads) void sampled_slot_kernel(ss_csr_grap
 
 }  // namespace ss
 
-// argument checks before any launch: 1 = nothing to do
-static int sampled_check(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h, int32_t max_nodes_per_hop,
-                         double ratio_per_hop, uint64_t seed, int32_t *counts, int32_t *state, const int64_t *rowptr, int64_t *ids,
-                         uint8_t *hop, void *workspace, size_t workspace_bytes)
+// the sampling arguments' own checks, in front of tier_check and of its B == 0 early-out (h outside [1, 3] is tier_check's to answer:
+// SS_ERR_UNSUPPORTED comes first)
+static bool sampled_bad(int32_t h, int32_t max_nodes_per_hop, double ratio_per_hop, uint64_t seed)
 {
-    if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (B < 0 || N < 0 || max_nodes_per_hop < 0) return SS_ERR_INVALID_ARG;
-    if (!(ratio_per_hop > 0.0 && ratio_per_hop <= 1.0) || seed >= ((uint64_t)1 << 63)) return SS_ERR_INVALID_ARG;  // (a NaN ratio fails too)
-    if (B == 0) return 1;
-    if (!graph || !links || !workspace || N == 0 || N >= ((int64_t)1 << 31) || graph->num_nodes != N || !graph->rowptr || !graph->col)
-        return SS_ERR_INVALID_ARG;
-    if (!state || (rowptr ? (!ids || !hop) : !counts)) return SS_ERR_INVALID_ARG;
-    const size_t need = ss_exact_workspace_bytes(B);
-    if (need == 0) return SS_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return SS_ERR_WORKSPACE;
-    return SS_OK;
+    return h >= 1 && h <= SS_MAX_HOPS &&
+           (max_nodes_per_hop < 0 || !(ratio_per_hop > 0.0 && ratio_per_hop <= 1.0) || seed >= ((uint64_t)1 << 63));  // (a NaN ratio fails too)
 }
 
 extern "C" int ss_sampled_nodes_pairs(const ss_csr_graph *graph, const int64_t *links, int64_t B, int64_t N, int32_t h,
@@ -378,24 +341,19 @@ extern "C" int ss_sampled_nodes_pairs(const ss_csr_graph *graph, const int64_t *
                                       size_t workspace_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = sampled_check(graph, links, B, N, h, max_nodes_per_hop, ratio_per_hop, seed, counts, state, rowptr, ids, hop, workspace,
-                                 workspace_bytes);
-    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (lds_max_nodes < 0) return SS_ERR_INVALID_ARG;
-    const int limit = lds_max_nodes < kExactMaxNodes ? lds_max_nodes : kExactMaxNodes;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    int32_t *overflow = reinterpret_cast<int32_t *>(ws + 1);
+    if (sampled_bad(h, max_nodes_per_hop, ratio_per_hop, seed)) return SS_ERR_INVALID_ARG;
     const bool fill = rowptr != nullptr;
-    if (!fill && hipMemsetAsync(ws, 0, sizeof(ExactWs), s) != hipSuccess) return SS_ERR_LAUNCH;
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, state && (fill ? ids && hop : counts != nullptr));
+    if (rc == SS_OK) rc = tier_lds(lds_max_nodes, workspace, stream, t);
+    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
+    if (!fill && hipMemsetAsync(t.ws, 0, sizeof(ExactWs), t.stream) != hipSuccess) return SS_ERR_LAUNCH;
     const SampledArgs a = {h, max_nodes_per_hop ? max_nodes_per_hop : INT32_MAX, ratio_per_hop, seed};
     const SampledOut o = {counts, state, rowptr, ids, hop, err_flag};
     const int64_t most = fill ? kSampledFillGrid : kExactGrid;
     const dim3 grid((unsigned)(B < most ? B : most)), block(kExactThreads);
-    if (fill)
-        hipLaunchKernelGGL((sampled_lds_kernel<true>), grid, block, 0, s, *graph, links, B, N, limit, a, o, ws, overflow);
-    else
-        hipLaunchKernelGGL((sampled_lds_kernel<false>), grid, block, 0, s, *graph, links, B, N, limit, a, o, ws, overflow);
+    const auto kernel = fill ? sampled_lds_kernel<true> : sampled_lds_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, t.stream, *graph, links, B, N, t.limit, a, o, t.ws, t.overflow);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -406,24 +364,18 @@ extern "C" int ss_sampled_nodes_large(const ss_csr_graph *graph, const int64_t *
                                       int32_t slots, void *arena, size_t arena_bytes, void *stream)
 {
     using namespace ss;
-    const int rc = sampled_check(graph, links, B, N, h, max_nodes_per_hop, ratio_per_hop, seed, counts, state, rowptr, ids, hop, workspace,
-                                 workspace_bytes);
-    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
-    if (slots <= 0 || !arena) return SS_ERR_INVALID_ARG;
-    if (arena_bytes / ss_exact_slot_bytes(N) < (size_t)slots) return SS_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    ExactWs *ws = static_cast<ExactWs *>(workspace);
-    const int32_t *overflow = reinterpret_cast<const int32_t *>(ws + 1);
+    if (sampled_bad(h, max_nodes_per_hop, ratio_per_hop, seed)) return SS_ERR_INVALID_ARG;
     const bool fill = rowptr != nullptr;
-    if (hipMemsetAsync(&ws->cursor, 0, sizeof(int32_t), s) != hipSuccess) return SS_ERR_LAUNCH;  // (the list is walked once per pass)
+    Tier t;
+    int rc = tier_check(graph, links, B, N, h, workspace, workspace_bytes, state && (fill ? ids && hop : counts != nullptr));
+    if (rc == SS_OK) rc = tier_large(N, slots, arena, arena_bytes, workspace, stream, t);
+    if (rc != SS_OK) return rc > 0 ? SS_OK : rc;
+    if (hipMemsetAsync(&t.ws->cursor, 0, sizeof(int32_t), t.stream) != hipSuccess) return SS_ERR_LAUNCH;  // (the list is walked once per pass)
     const SampledArgs a = {h, max_nodes_per_hop ? max_nodes_per_hop : INT32_MAX, ratio_per_hop, seed};
     const SampledOut o = {counts, state, rowptr, ids, hop, nullptr};
-    uint32_t *ar = static_cast<uint32_t *>(arena);
-    const dim3 grid((unsigned)slots), block(kExactThreads);
-    if (fill)
-        hipLaunchKernelGGL((sampled_slot_kernel<true>), grid, block, 0, s, *graph, links, N, a, o, ws, overflow, ar);
-    else
-        hipLaunchKernelGGL((sampled_slot_kernel<false>), grid, block, 0, s, *graph, links, N, a, o, ws, overflow, ar);
+    const auto kernel = fill ? sampled_slot_kernel<true> : sampled_slot_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)slots), dim3(kExactThreads), 0, t.stream, *graph, links, N, a, o, t.ws, t.overflow,
+                       static_cast<uint32_t *>(arena));
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

@@ -3,7 +3,8 @@ u and v in the graph build_hash_tables propagates over, counted by BFS, and the 
 them -- what the sketch query would return if MinHash and HLL++ were exact (reference hashing.py:139-189, 258-323).
 
 Host side only: argument checks, the CSR (the engine's cache), launch planning per batch (the on-chip tier, then the large tier over
-the pairs it left), the large tier's slot arena and the output tensors."""
+the pairs it left), the large tier's slot arena and the output tensors.  The node-list calls (exact_nodes.py, sampled_nodes.py) and
+exact_subgraphs take their checks, the kernels' graph struct, the arena and the node rows of no links from here."""
 from ctypes import byref, c_void_p
 
 import torch
@@ -42,6 +43,27 @@ def _arena(device, N):
     arena = torch.zeros(slots * slot_bytes, dtype=torch.uint8, device=device)
     _ARENA[key] = (N, slots, arena, want)
     return slots, arena
+
+
+def check_mask_target(mask_target):
+    if not isinstance(mask_target, bool):
+        raise ValueError(f'mask_target of the exact query is a bool (the links are masked in the edge_index given), got {type(mask_target).__name__}')
+
+
+def csr_graph(eh, ei, N, device):
+    """-> (the kernels' graph of `ei`, the implicit loops of build_hash_tables included, and the engine's cached CSR it points into: a
+    repeated edge_index is not rebuilt; the struct holds addresses only, so the caller keeps the CSR for as long as it launches)"""
+    csr = eh._csr_cache.get(ei, N, device)
+    return _native.CsrGraphStruct(rowptr=csr.rowptr.data_ptr(), col=csr.col.data_ptr(), num_nodes=N, n_self_loops=0,
+                                  n_self_loops_dev=csr.n_self_dev.data_ptr()), csr
+
+
+def empty_rows(home, tail, return_info, **more):
+    """what a node-list call returns for no links.  tail: the shape of what a listed node carries besides its id"""
+    out = (torch.zeros((1,), dtype=torch.int64, device=home), torch.empty((0,), dtype=torch.int64, device=home),
+           torch.empty((0,) + tail, dtype=torch.uint8, device=home))
+    info = {'truncated': torch.empty((0,), dtype=torch.int64, device=home), 'lds_links': 0, 'large_links': 0, **more}
+    return out + (info,) if return_info else out
 
 
 def check_arguments(h, links, num_nodes, edge_index, batch_size):
@@ -83,8 +105,7 @@ def exact_subgraph_features(eh, links, num_nodes, edge_index, batch_size=1100000
     """see ElphHashes.exact_subgraph_features.  stats (measurement hook, tools/probe_exact.py): a dict that receives the overflow
     count and the milliseconds of each tier, summed over batches (the call then synchronises after every launch)"""
     h = eh.max_hops
-    if not isinstance(mask_target, bool):
-        raise ValueError(f'mask_target of the exact query is a bool (the links are masked in the edge_index given), got {type(mask_target).__name__}')
+    check_mask_target(mask_target)
     lk, ei, N, batch_size = check_arguments(h, links, num_nodes, edge_index, batch_size)
     home, L, nf = lk.device, lk.size(0), h * (h + 2)
     if L == 0:
@@ -93,9 +114,7 @@ def exact_subgraph_features(eh, links, num_nodes, edge_index, batch_size=1100000
             return feats
         return (feats, torch.empty((0, h, h), dtype=torch.int32, device=home), torch.empty((0, 2, h), dtype=torch.int32, device=home))
     device = _compute_device(lk, ei)
-    csr = eh._csr_cache.get(ei, N, device)  # (the engine's CSR cache: a repeated edge_index is not rebuilt)
-    graph = _native.CsrGraphStruct(rowptr=csr.rowptr.data_ptr(), col=csr.col.data_ptr(), num_nodes=N, n_self_loops=0,
-                                   n_self_loops_dev=csr.n_self_dev.data_ptr())  # the implicit loops of build_hash_tables
+    graph, csr = csr_graph(eh, ei, N, device)
     lk = lk.to(device=device, dtype=torch.int64).contiguous()
     feats = torch.empty((L, nf), dtype=torch.float32, device=device)
     I = torch.empty((L, h, h), dtype=torch.int32, device=device) if return_counts else None

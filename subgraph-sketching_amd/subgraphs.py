@@ -117,8 +117,7 @@ def exact_subgraphs(eh, links, num_nodes, edge_index, batch_size=11000000, mask_
     """see ElphHashes.exact_subgraphs.  stats (measurement hook, tools/probe_subgraphs.py): a dict that receives the milliseconds of
     the node list's passes and of the adjacency count, the offsets with the host read, the adjacency fill and the labels"""
     h = eh.max_hops
-    if not isinstance(mask_target, bool):
-        raise ValueError(f'mask_target of the exact query is a bool (the links are masked in the edge_index given), got {type(mask_target).__name__}')
+    exact.check_mask_target(mask_target)
     exact_nodes._cap(max_nodes)
     node_label, max_dist = _label_arguments(node_label, max_dist)
     cap_hop, ratio, seed = sampled_nodes.sampling_arguments(max_nodes_per_hop, ratio_per_hop, seed)

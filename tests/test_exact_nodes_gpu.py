@@ -1,6 +1,7 @@
 """ElphHashes.exact_subgraph_nodes (exact_nodes.py, csrc/ss_exact_nodes.hip) on the GPU: rowptr, ids and dist must EQUAL the scipy
 restatement (tests/exact_nodes_restatement.py) -- on the BA-40 golden graph (every hop count, masked or not), a 3 000-node uniform
-graph under batching and shuffling, two stars through either kernel tier (and the arena all zero afterwards), against the histograms
+graph under batching and shuffling, two stars through either kernel tier (and the arena all zero afterwards), batches, max_nodes and
+both tiers in one call, against the histograms
 the shipped exact_subgraph_features counts, under max_nodes, and on the edge cases (no links, no edges, duplicate and self-loop edges,
 CPU inputs, a directed edge_index)."""
 from argparse import Namespace
@@ -153,6 +154,38 @@ def test_small_on_chip_limits(ssa, dev, lds_limit, uniform3000, limit):
     _same(got, want[False])
     large = int((np.diff(want[False][0]) > limit).sum())
     assert 0 < large == got[3]['large_links'] and got[3]['lds_links'] == len(links) - large and _arena_is_zero(ssa)
+
+
+# ---- batches, the cap and both tiers in one call ----------------------------------------------------------------------------------------
+def _hub60():
+    """hub 0 with leaves 1 .. 40 and a path 0 - 41 - 42 - ... - 59; 7 links: unions at the hub hold 42 to 49 nodes, unions on the path 5 to
+    9, and with batches of 3 every batch but the last holds both kinds"""
+    leaves, path = np.arange(1, 41), np.arange(41, 60)
+    src = np.concatenate([np.zeros_like(leaves), [0], path[:-1]])
+    dst = np.concatenate([leaves, path[:1], path[1:]])
+    ei = np.stack([np.concatenate([src, dst]), np.concatenate([dst, src])]).astype(np.int64)
+    return 60, ei, np.array([[1, 2], [0, 45], [50, 52], [59, 57], [44, 44], [0, 0], [-1, 3]], dtype=np.int64)
+
+
+@pytest.mark.parametrize('h', [2, 3])
+def test_batches_cap_and_both_tiers_in_one_call(ssa, dev, lds_limit, h):
+    """every batch keeps its own workspace (counters and overflow list) from the count pass to the fill pass: batches of 3, an on-chip
+    limit of 16 that sends the unions at the hub to the large tier, and max_nodes at the median row length, which empties three of the
+    large tier's rows and keeps one"""
+    n, ei, links = _hub60()
+    rowptr, ids, dist = nr.restate(n, ei, links, h)
+    sizes = np.diff(rowptr)
+    cap = int(np.median(sizes))
+    keep = sizes <= cap
+    assert (sizes[keep] > 16).any() and (sizes[keep] <= 16).any() and not keep.all()
+    full = nr.rows(rowptr, ids, dist)
+    want = (np.concatenate([[0], np.cumsum(np.where(keep, sizes, 0))]), np.concatenate([full[q][0] for q in np.nonzero(keep)[0]]),
+            np.concatenate([full[q][1] for q in np.nonzero(keep)[0]]))
+    lds_limit(16)
+    got = _run(_eh(ssa, h), n, ei, links, dev, batch_size=3, max_nodes=cap, return_info=True)
+    _same(got, want)
+    np.testing.assert_array_equal(got[3]['truncated'].cpu().numpy(), np.nonzero(~keep)[0])
+    assert got[3]['large_links'] == (sizes > 16).sum() and got[3]['lds_links'] == (sizes <= 16).sum() and _arena_is_zero(ssa)
 
 
 # ---- against the shipped counts -------------------------------------------------------------------------------------------------------

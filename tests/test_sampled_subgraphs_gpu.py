@@ -2,7 +2,7 @@
 seed=) on the GPU: rowptr, ids and hop -- and through exact_subgraphs every field -- must EQUAL the Python-set restatement
 (tests/sampled_subgraph_restatement.py): on BA-40 over hops, caps, ratios, seeds, labels and masking; on a 3 000-node uniform graph under
 batching, shuffling and duplicated links; on two stars through either kernel tier (fringes of thousands for a cap of 100, the arena all
-zero afterwards); at the selection boundaries; on the star of the sampling law; on K_8 with tails; under max_nodes; and on the edge cases
+zero afterwards); batches, max_nodes and both tiers in one call; at the selection boundaries; on the star of the sampling law; on K_8 with tails; under max_nodes; and on the edge cases
 (no links, no edges, CPU inputs, a directed edge_index).  With the default keywords exact_subgraphs is what it was."""
 from argparse import Namespace
 
@@ -13,7 +13,7 @@ import torch
 import sampled_subgraph_restatement as ssr
 import subgraph_restatement as sr
 from conftest import load_golden
-from test_exact_nodes_gpu import _arena_is_zero
+from test_exact_nodes_gpu import _arena_is_zero, _hub60
 from test_exact_nodes_host import _ba40, _uniform300
 from test_sampled_subgraphs_host import STAR_SEED, k8_with_tails, star
 
@@ -243,6 +243,32 @@ def test_stars_every_field_in_the_slot_tier(ssa, dev, lds_limit):
     _same(_subgraphs(ssa, eh, n, ei, links, dev, max_nodes_per_hop=100, seed=6), sub, 'drnl')
     lds_limit(1)
     _same(_subgraphs(ssa, eh, n, ei, links, dev, max_nodes_per_hop=100, seed=6, node_label='de'), sub, 'de')
+    assert _arena_is_zero(ssa)
+
+
+@pytest.mark.parametrize('h', [2, 3])
+def test_batches_cap_and_both_tiers_in_one_call(ssa, dev, lds_limit, h):
+    """every batch keeps its own workspace (counters and overflow list) from the count pass to the fill pass: 7 links in batches of 3, an
+    on-chip limit of 16 (the four links that visit the hub's leaves pass it), 4 nodes per hop, and max_nodes at the median row length,
+    which empties rows of either tier"""
+    n, ei, links = _hub60()
+    sizes = np.diff(ssr.restate_nodes(n, ei, links, h, cap=4)[0])
+    cut = int(np.median(sizes))
+    want = ssr.restate_nodes(n, ei, links, h, cap=4, max_nodes=cut, return_info=True)
+    nb, visited = ssr.in_neighbours(n, ei), []
+    for u, v in np.where(links < 0, links + n, links).tolist():  # what each link visits: its roots and every hop's whole fringe
+        fringes = []
+        ssr.walk(nb, u, v, h, cap=4, fringes=fringes)
+        visited.append(2 - (u == v) + sum(F for F, _ in fringes))
+    slot = np.array(visited) > 16
+    gone = np.zeros(len(links), dtype=bool)
+    gone[want[3]['truncated']] = True
+    assert (gone & slot).any() and (gone & ~slot).any() and (~gone & slot).any() and (~gone & ~slot).any()
+    lds_limit(16)
+    got = _nodes(_eh(ssa, h), n, ei, links, dev, batch_size=3, max_nodes_per_hop=4, max_nodes=cut, return_info=True)
+    _same_nodes(got, want)
+    np.testing.assert_array_equal(got[3]['truncated'].cpu().numpy(), want[3]['truncated'])
+    assert got[3]['sampled_links'] == want[3]['sampled_links'] > 0 and (got[3]['lds_links'], got[3]['large_links']) == ((~slot).sum(), slot.sum())
     assert _arena_is_zero(ssa)
 
 
