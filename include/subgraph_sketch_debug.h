@@ -22,7 +22,7 @@ extern "C" {
  * that family, returns their mean duration (ms) and count through host pointers, and removes them from the list. */
 #define SS_PROF_MINHASH_HOP 0     /* ss::propagate_kernel<128,256>, MinHash table hop (the dominant kernel of a build)   */
 #define SS_PROF_HLL_HOP 1         /* ss::hll_propagate_row16_kernel, HLL table hop + cardinalities                       */
-#define SS_PROF_FIRST_HOP_MH 2    /* ss::first_hop_kernel<..., true, false>                                              */
+#define SS_PROF_FIRST_HOP_MH 2    /* ss::first_hop_rows_kernel<P / 64, 8, ...>                                           */
 #define SS_PROF_FIRST_HOP_HLL 3   /* ss::hll_first_hop_kernel                                                            */
 #define SS_PROF_PAIRS 4           /* ss::pair_features_kernel                                                            */
 #define SS_PROF_CSR 5             /* all launches of one ss_csr_build                                                    */

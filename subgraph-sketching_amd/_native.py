@@ -8,7 +8,7 @@ import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (SS_LIB: measurement hook -- tools/ablate_fused.sh loads deliberately incomplete builds of the library to time what is left)
+# (SS_LIB: measurement hook -- tools/ab_variant.sh loads a scratch build of the library beside the product's)
 LIB_PATH = os.environ.get('SS_LIB') or os.path.join(_HERE, 'libsubgraph_sketch.so')
 
 SS_MAX_HOPS = 3

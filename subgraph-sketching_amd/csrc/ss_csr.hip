@@ -75,12 +75,8 @@ struct DenseSync {     // per registered bucket, zeroed by the tile sort of the 
 };
 
 // average edges of a fine bucket the plans aim for: 3/4 of the image (a bucket above it goes to the dense steps, at some cost;
-// half as many finish workgroups as at 1/2, each with the same fixed latencies).  SS_CSR_BUCKET_EDGES: tuning hook
-inline int64_t bucket_edges_target()
-{
-    static const int64_t env = getenv("SS_CSR_BUCKET_EDGES") ? atoll(getenv("SS_CSR_BUCKET_EDGES")) : 0;
-    return env > 0 ? env : kFinishCap * 3 / 4;
-}
+// half as many finish workgroups as at 1/2, each with the same fixed latencies)
+constexpr int64_t kBucketEdgesTarget = kFinishCap * 3 / 4;
 
 struct LevelPlan {
     int levels;
@@ -113,7 +109,7 @@ inline bool make_plan(int64_t N, int64_t E, int64_t max_src, LevelPlan &p)
     // edges on average, between 64 and 1024 nodes
     int node_shift = 10;
     if (((n + 1023) >> 10) > kMaxKeys)
-        while (node_shift > 6 && (E / n) * ((int64_t)1 << node_shift) > bucket_edges_target()) --node_shift;
+        while (node_shift > 6 && (E / n) * ((int64_t)1 << node_shift) > kBucketEdgesTarget) --node_shift;
     if (const char *forced = getenv("SS_CSR_NODE_SHIFT")) {  // test hook: reach the three-level plans with small graphs
         const int f = atoi(forced);
         if (f >= 4 && f <= 10) node_shift = f;
@@ -199,33 +195,6 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_keys(uint32_t x /* 0 fo
     do {                             \
         if ((word) && *(word)) return; \
     } while (0)
-
-#ifdef SS_CSR_TIMING  // measurement build only (SS_EXTRA_FLAGS=-DSS_CSR_TIMING): where a finish workgroup's time goes
-__device__ unsigned long long csr_phase_ticks[16];
-#define SS_TICK(i)                                                                                   \
-    do {                                                                                             \
-        if (threadIdx.x == 0) {                                                                      \
-            const unsigned long long now_ = wall_clock64();                                          \
-            atomicAdd(&csr_phase_ticks[i], now_ - tick_);                                            \
-            tick_ = now_;                                                                            \
-        }                                                                                            \
-    } while (0)
-#define SS_TICK_START() unsigned long long tick_ = wall_clock64()
-// the finish launch's timeline: slot 8 = earliest start of a workgroup, slots 9.. = latest time any workgroup passed mark i
-#define SS_MARK_START()                                                          \
-    do {                                                                         \
-        if (threadIdx.x == 0) atomicMin(&csr_phase_ticks[8], wall_clock64());    \
-    } while (0)
-#define SS_MARK(i)                                                               \
-    do {                                                                         \
-        if (threadIdx.x == 0) atomicMax(&csr_phase_ticks[i], wall_clock64());    \
-    } while (0)
-#else
-#define SS_TICK(i)
-#define SS_TICK_START()
-#define SS_MARK_START()
-#define SS_MARK(i)
-#endif
 
 // ---- level 0: every 4096-edge tile of the caller's list is sorted by key in LDS and written back as ONE contiguous tile (no global
 // offsets are needed for that), together with the tile's exclusive key offsets off[key][tile] (key-major, so that a group's row is
@@ -1318,10 +1287,8 @@ __device__ __forceinline__ bool dense_help_bucket(DenseRunLds &lds, uint32_t *st
         }
     }
     if (mine < 0) return false;
-    SS_MARK(11);
     // every share of the bucket is claimed (the counter ran out above), each by a workgroup that is inside its count step: safe to wait
     if (!wait_until(&sy->counted, b.shares, &lds.flag, o.err, o.fault_word, o.wait_ticks)) return true;
-    SS_MARK(12);
     // ---- place: the share whose records are still here ...
     {
         const uint32_t *sum = w.node_cnt + (size_t)d * 1024;
@@ -1493,7 +1460,6 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     __shared__ unsigned long long red_base[kRunThreads / kWave], red_max[kRunThreads / kWave];
     __shared__ uint32_t red_n[kRunThreads / kWave];
     SS_CSR_SKIP(o.skip);
-    SS_MARK_START();
     const DenseRunWork work = {par, staged, node_shift, src_bits, N, dense.list, dense.share_lo, dense.node_cnt, dense.share_off, col};
     DenseRunLds &help_lds = *reinterpret_cast<DenseRunLds *>(lds.image);
     uint32_t *help_stash = reinterpret_cast<uint32_t *>(lds.image) + kHelperStashWord;
@@ -1501,7 +1467,6 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     int own = -1;                                                // the registered bucket of this workgroup, if its bucket is dense
     // ONE call site of dense_help at the end of the kernel (three inlined copies: 166 VGPRs, one workgroup per CU instead of two)
     if (!dedicated) {
-    SS_TICK_START();
     const ChildGroup c = child_group(par, blockIdx.x);
     const uint32_t *row0 = par.off + (int64_t)c.k * par.tmax, *row1 = row0 + par.tmax;
     const int node0 = (int)((int64_t)blockIdx.x << node_shift);
@@ -1595,7 +1560,6 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     dense.row1 = row1;
     dense.t_lo = c.t_lo;
     dense.t_hi = c.t_hi;
-    SS_TICK(0);
     const int nb = 1 << node_shift;  // <= 1024 nodes
     uint32_t *cnt = lds.cnt;
     // above the image but walkable (resident descriptors, <= walk_max edges): counted here first -- it stays with this workgroup unless
@@ -1621,10 +1585,8 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     }
     if (n > (uint32_t)kDenseMin && !by_images) {  // (workgroup-uniform) registered, then worked off share by share by everybody
         own = announced ? dense.register_from_prefix(lds, base, n, nb, sc.ex, sc.len) : dense.register_bucket(lds, base, n, nb);
-        SS_MARK(14);
     } else {
     if (!announced) dense.arrive();
-    SS_MARK(15);
     if (!by_images) {
     for (int i = threadIdx.x; i < nb; i += kRunThreads) cnt[i] = 0;
     __syncthreads();
@@ -1637,12 +1599,10 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     else if (stashed) edges.for_each_stash(stash, [&](int, int y) { atomicAdd(&cnt[y], 1u); });
     else edges.for_each([&](int, int y) { atomicAdd(&cnt[y], 1u); });
     __syncthreads();
-    SS_TICK(1);
     scan_bucket_nodes(cnt, lds.excl, lds.wave_tot, nb, (int64_t)node0, N, base, n, true, o);
     __syncthreads();
     for (int i = threadIdx.x; i < nb; i += kRunThreads) cnt[i] = lds.excl[i];  // cursors
     __syncthreads();
-    SS_TICK(2);
     // anything registered by now?  Loaded here, used behind the bucket's last stores (the load's latency hides under the placing
     // sweep); a bucket registered later than this look is worked off by its own workgroup and by whoever finishes later
     const int registered = __hip_atomic_load(&dense.count[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) -
@@ -1681,18 +1641,14 @@ __global__ __launch_bounds__(kRunThreads) __attribute__((amdgpu_waves_per_eu(4, 
     if (stashed) edges.replay(stash, n, place);
     else edges.for_each(place);
     __syncthreads();
-    SS_TICK(3);
     if (threadIdx.x == 0) red_n[0] = (uint32_t)registered;  // (one thread's look decides for the workgroup)
     for (uint32_t q = threadIdx.x; q < n; q += kRunThreads) col[base + q] = lds.image[q];
     }
-    SS_TICK(4);
-    SS_MARK(9);
     __syncthreads();  // the image is free (it becomes the helper's LDS), the look is visible
     if ((int)red_n[0] <= 0) return;  // every unskewed graph; a skewed one whose dense buckets have all been taken
     }
     }
     dense_help<PACKED>(help_lds, help_stash, dedicated, (int)fine_buckets, own, work, o, dense);
-    SS_MARK(13);
 }
 
 struct Workspace {
@@ -1902,21 +1858,6 @@ extern "C" int ss_debug_csr_protocol_faults(void)
 }
 
 
-#ifdef SS_CSR_TIMING
-extern "C" int ss_csr_timing_read(unsigned long long *out16, int reset)
-{
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(ss::csr_phase_ticks), 16 * 8) != hipSuccess) return SS_ERR_LAUNCH;
-    if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(ss::csr_phase_ticks), z, 16 * 8) != hipSuccess) return SS_ERR_LAUNCH;
-    }
-    return SS_OK;
-}
-extern "C" int ss_csr_timing_write(const unsigned long long *in16)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(ss::csr_phase_ticks), in16, 16 * 8) == hipSuccess ? SS_OK : SS_ERR_LAUNCH;
-}
-#endif
 
 extern "C" size_t ss_csr_workspace_bytes(int64_t N, int64_t E)
 {

@@ -9,102 +9,23 @@
 // (VALU-bound: v_mul_lo_u32 / v_mad_u64_u32 issue at quarter rate, 16 cycles per wave64 on gfx950; measured
 // 0.17 ms vs 0.36 ms for init + propagate on the bench graph.)
 //
-// Mapping: one wavefront per destination row.  Lane l owns permutations l, l+64, .. (P/64 of them) and
+// Mapping of a walk (first_hop_walk, ss_walks.hpp): lane l owns permutations l, l+64, .. (P/64 of them) and
 // HLL registers 4l..4l+3 (M = 256).  Neighbour ids are fetched 64 at a time (one coalesced load), every
 // lane hashes ITS neighbour (64 hashes in parallel) and scatter-maxes that neighbour's single HLL register
-// into the wave's LDS row; then the wave walks the batch with v_readlane: the neighbour's hash is
-// wave-uniform (SGPR pair), each lane evaluates its own permutations on it.
+// into an LDS row; then the wave walks the batch with v_readlane: the neighbour's hash is
+// wave-uniform (SGPR pair), each lane evaluates its own permutations on it.  The row kernels below give a wavefront
+// several MinHash rows, a 16-lane group an HLL row.
 // Hub rows are hub units (ss_hub.hpp): a whole workgroup per row or slice of a row, waves take alternate 64-neighbour
 // batches and combine through LDS atomics -- the HLL side hosted by the leading workgroups of hll_first_hop_kernel's launch,
 // the MinHash side by the fused kernel's (ss_fused_hop.hip) or by first_hop_hub_kernel, a launch of its own.
-#include <cstdlib>
-#include <type_traits>
-
 #include "ss_hub.hpp"
 
 namespace ss {
 
-#ifndef SS_FORCE_EXACT_FIRST_HOP
-#define SS_FORCE_EXACT_FIRST_HOP 0
-#endif
-constexpr bool kForceExactFirstHop = SS_FORCE_EXACT_FIRST_HOP;  // build-time switch: every row through the exact walk
-
-template <int PPL /* permutations per lane = P / 64 */, bool DO_MH, bool DO_HLL>
-__global__ __launch_bounds__(256) void first_hop_kernel(GraphArgs g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
-                                                        uint32_t *__restrict__ mh_out, int p, uint8_t *__restrict__ hll_out,
-                                                        float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm,
-                                                        bool skip_hubs)
-{
-    __shared__ EstimatorLds lds;
-    __shared__ __attribute__((aligned(16))) uint32_t hll_rows[256 / kWave][256];  // one u32 per register and wave
-    const bool want_cards = DO_HLL && cards_out != nullptr;
-    EstimatorTables est;
-    if (want_cards) est = stage_tables(lds, prm);
-
-    constexpr int P = PPL * kWave;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int64_t i = g.row0 + (int64_t)blockIdx.x * (blockDim.x / kWave) + wave;
-    if (i >= g.row1) return;
-    const int64_t rb = g.rowptr[i];
-    const int deg = (int)(g.rowptr[i + 1] - rb);
-    if (skip_hubs && deg > g.hub_threshold) return;  // left to first_hop_hub_kernel
-
-    uint64_t a[PPL], b[PPL];
-    uint32_t acc[PPL];
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) {
-        a[q] = DO_MH ? pa[lane + kWave * q] : 0ULL;
-        b[q] = DO_MH ? pb[lane + kWave * q] : 0ULL;
-        acc[q] = 0xFFFFFFFFu;
-    }
-    uint32_t *my_row = hll_rows[wave];
-    *reinterpret_cast<u32x4 *>(my_row + 4 * lane) = u32x4{0u, 0u, 0u, 0u};
-
-    const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
-    const int total = deg + (i < n_self ? 1 : 0);
-    if (DO_MH && !DO_HLL && !kForceExactFirstHop) {
-        // MinHash alone: two-phase walk (one multiply per neighbour and permutation); the rare ambiguous row is redone exactly
-        first_hop_minhash_row<PPL>(g.col + rb, deg, total, i, p, a, b, acc, lane, true);
-    } else {
-        first_hop_walk<PPL, DO_MH, DO_HLL>(g.col + rb, deg, total, i, 0, 1, p, a, b, acc, my_row, lane);
-        if (DO_MH && total == 0) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) acc[q] = 0u;  // no in-edge, no self loop: all-zero row (PyG default)
-        }
-    }
-
-    if (DO_MH) {
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-            mh_out[i * P + lane + kWave * q] = acc[q];
-            mirror_mh1(g.mir, i * P + lane + kWave * q, acc[q]);
-        }
-    }
-    if (!DO_HLL) return;
-    // the wave's LDS row is only touched by this wave: a wave-level fence orders the atomics before the read
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const uint32_t regs = pack_hll_quad(my_row, lane);  // HLL registers 4*lane .. 4*lane+3
-    *reinterpret_cast<uint32_t *>(hll_out + i * 256 + 4 * lane) = regs;
-    mirror_hll4(g.mir, i * 256 + 4 * lane, regs);
-
-    if (want_cards) {
-        int nonzero = 0;
-        float hsum = 0.0f;
-        hll_dword_stats(regs, nonzero, hsum);
-        wave_sum_stats(nonzero, hsum);
-        if (lane == 0) {
-            const float card = hll_estimate(est, 256 - nonzero, hsum);
-            cards_out[i * cards_stride] = card;
-            mirror_card(g.mir, i * cards_stride, card);
-        }
-    }
-}
-
 // ---- MinHash first hop, several consecutive rows per wavefront ---------------------------------------------------------
-// first_hop_kernel spends about as many VALU instructions per row on fixed work (permutation parameters, neighbour-id
+// One row per wavefront spends about as many VALU instructions per row on fixed work (permutation parameters, neighbour-id
 // load + splitmix64, winner fetch, exact evaluation: ~105) as on the walk itself at the bench graph's degree (9 per
-// neighbour x 11), and the kernel is bound by VALU issue (VALUBusy 88 %).  Rows that are consecutive in the CSR are also
+// neighbour x 11), and is bound by VALU issue (VALUBusy 88 %).  Rows that are consecutive in the CSR are also
 // consecutive in `col`, so a wavefront that owns kRowsPerWave consecutive rows
 //   * loads a / b and sets up its lane constants once,
 //   * fetches and hashes the neighbour ids of ALL its rows in batches of 64 - kRowsPerWave col entries with one coalesced
@@ -129,12 +50,9 @@ __global__ __launch_bounds__(256) void first_hop_rows_kernel(GraphArgs g, const 
 
 // HLL-only first hop, latency-optimised: one 16-lane DPP row per destination (4 destinations in flight per wave).
 // Used when the caller asks for the HLL sketch alone (the two-stream build runs the HLL chain beside the MinHash
-// chain); the one-row-per-wave kernel above is a single dependent chain per wave and takes 4x longer for this.
-#ifndef SS_HLL_ROWS
-#define SS_HLL_ROWS 4
-#endif
-constexpr int kHllRows = SS_HLL_ROWS;  // (2, 6 and 8 measured the same 25 us on the bench graph: the kernel is not bound by its prefetch depth;
-                                       // round 6, -DSS_HLL_ROWS=3 / 4 / 6 / 8: 25.5 / 25.7 / 25.4 / 37.9 us -- 8 spills 100 bytes at the 64-VGPR budget)
+// chain); one row per wavefront is a single dependent chain per wave and takes 4x longer for this.
+constexpr int kHllRows = 4;  // (2, 6 and 8 measured the same 25 us on the bench graph: the kernel is not bound by its prefetch depth;
+                             // round 6, 3 / 4 / 6 / 8 rows: 25.5 / 25.7 / 25.4 / 37.9 us -- 8 spills 100 bytes at the 64-VGPR budget)
 
 // PPL only matters to the leading workgroups (hub units, ss_hub.hpp): with hub_mh_out they also serve the hop-1 MinHash table
 // (P = 64 * PPL) -- ss_fused_hop_stage's row kernel has no register to spare for them.  The register allocator is held to the 64
@@ -142,7 +60,7 @@ constexpr int kHllRows = SS_HLL_ROWS;  // (2, 6 and 8 measured the same 25 us on
 template <int PPL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void hll_first_hop_kernel(
     GraphArgs g, int p, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm, bool skip_hubs,
-    int hub_blocks, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ hub_mh_out, bool interleave)
+    int hub_blocks, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ hub_mh_out)
 {
     // only the linear-counting table is staged (this kernel is only launched for p = 8: 257 entries): a hop-1 row leaves the
     // linear-counting range at 147 neighbours, and those few read raw / bias from global memory.  17 KB of LDS and 60 VGPRs
@@ -162,10 +80,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void h
         const int first = hub_mh_out ? hub_blocks / 4 : hub_blocks;
         if ((int)blockIdx.x < first)
             first_hop_hub_units<PPL, kHubLeadWaves, false, true>(g, (int)blockIdx.x, first, nullptr, nullptr, nullptr, p, hll_out, cards_out,
-                                                                 cards_stride, est, want_cards, hub, false);
+                                                                 cards_stride, est, want_cards, hub);
         else
             first_hop_hub_units<PPL, kHubLeadWaves, true, false>(g, (int)blockIdx.x - first, hub_blocks - first, pa, pb, hub_mh_out, p, nullptr,
-                                                                 nullptr, 0, est, false, hub, kForceExactFirstHop);
+                                                                 nullptr, 0, est, false, hub);
         return;
     }
     const int l = threadIdx.x & (kRow - 1);
@@ -174,12 +92,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void h
     // neighbour ids of ALL of them are requested up front, so the two dependent global round trips (rowptr -> col) of
     // the later rows hide under the work of the earlier ones
     // Row r of lane group `grp` is row r * 16 + grp of the workgroup's 64: at any moment the 16 lane groups work on 16 CONSECUTIVE rows
-    // -- consecutive stretches of `col` and of the output (round 6; SS_HLL_ROW_MAP=0: the four consecutive rows per lane group of
-    // rounds 2-5, whose shared boundary lines were fetched twice at ogbl-ppa size)
+    // -- consecutive stretches of `col` and of the output (round 6; four consecutive rows per lane group, the map of rounds 2-5,
+    // fetched the shared boundary lines twice at ogbl-ppa size)
     const int groups = (int)(blockDim.x / kRow);
     const int64_t wg_first = g.row0 + (int64_t)((int)blockIdx.x - hub_blocks) * groups * kHllRows;
-    const int64_t first = interleave ? wg_first + grp : wg_first + (int64_t)grp * kHllRows;
-    const int64_t row_step = interleave ? groups : 1;
+    const int64_t first = wg_first + grp;
+    const int64_t row_step = groups;
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
     uint32_t *row = rows[grp];
     int64_t rbs[kHllRows];
@@ -234,64 +152,42 @@ __global__ __launch_bounds__(kHubThreads) void first_hop_hub_kernel(GraphArgs g,
     EstimatorTables est = {};
     if (want_cards) est = stage_tables(lds, prm);
     first_hop_hub_units<PPL, kHubWaves, DO_MH, DO_HLL>(g, (int)blockIdx.x, (int)gridDim.x, pa, pb, mh_out, p, hll_out, cards_out, cards_stride, est,
-                                                       want_cards, hub, kForceExactFirstHop);
+                                                       want_cards, hub);
 }
 
 int launch_first_hop_hub_only(const GraphArgs &g, const uint64_t *a, const uint64_t *b, int P, uint32_t *mh_out, int p, uint8_t *hll_out,
                               float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream);
-template <int PPL>
-void launch_minhash_rows(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, const ss_hll_params &prm,
-                         bool hubs, hipStream_t s);
 
-template <int PPL, bool DO_MH, bool DO_HLL>
-int launch_first_hop_v(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, uint8_t *hll_out,
-                       float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t s)
+// MinHash rows of one launch: kRowsPerWave consecutive rows per wavefront
+template <int PPL>
+void launch_minhash_rows(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, bool hubs, hipStream_t s)
 {
-    const int64_t blocks = (g.rows() + 3) / 4;
+    constexpr int rows_per_block = 4 * kRowsPerWave;
+    const dim3 grid((unsigned)((g.rows() + rows_per_block - 1) / rows_per_block));
+    if (g.mir.n > 0)
+        hipLaunchKernelGGL((first_hop_rows_kernel<PPL, kRowsPerWave, true>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
+    else
+        hipLaunchKernelGGL((first_hop_rows_kernel<PPL, kRowsPerWave, false>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
+}
+
+// MinHash alone: the row launch, then the hub units as a launch of their own
+template <int PPL>
+int launch_first_hop_mh(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, const ss_hll_params &prm,
+                        hipStream_t s)
+{
     const bool hubs = g.hub_rows && g.hub_count;
     {
-        ProfileSpan span(s, DO_MH && !DO_HLL ? SS_PROF_FIRST_HOP_MH : SS_PROF_TAGS);
-        if constexpr (DO_MH && !DO_HLL)
-            launch_minhash_rows<PPL>(g, a, b, mh_out, p, prm, hubs, s);
-        else
-            hipLaunchKernelGGL((first_hop_kernel<PPL, DO_MH, DO_HLL>), dim3((unsigned)blocks), dim3(256), 0, s, g, a, b, mh_out, p, hll_out,
-                               cards_out, cards_stride, prm, hubs);
+        ProfileSpan span(s, SS_PROF_FIRST_HOP_MH);
+        launch_minhash_rows<PPL>(g, a, b, mh_out, p, hubs, s);
     }
     SS_LAUNCH_CHECK();
     if (hubs) {
         note_hub_call();
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, DO_MH, DO_HLL>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p,
-                           hll_out, cards_out, cards_stride, prm);
+        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, true, false>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p,
+                           (uint8_t *)nullptr, (float *)nullptr, (int64_t)0, prm);
         SS_LAUNCH_CHECK();
     }
     return SS_OK;
-}
-
-// MinHash rows of one launch: kRowsPerWave consecutive rows per wavefront; SS_FIRST_HOP_ROWS=0 selects the one-row-per-wave
-// kernel (A/B measurements, and the build-time switch that forces the exact walk)
-template <int PPL>
-void launch_minhash_rows(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, const ss_hll_params &prm,
-                         bool hubs, hipStream_t s)
-{
-    static const int rows_env = getenv("SS_FIRST_HOP_ROWS") ? atoi(getenv("SS_FIRST_HOP_ROWS")) : kRowsPerWave;
-    if (kForceExactFirstHop || rows_env == 0) {
-        hipLaunchKernelGGL((first_hop_kernel<PPL, true, false>), dim3((unsigned)((g.rows() + 3) / 4)), dim3(256), 0, s, g, a, b, mh_out, p,
-                           (uint8_t *)nullptr, (float *)nullptr, (int64_t)0, prm, hubs);
-        return;
-    }
-    auto go = [&](auto rows_tag) {
-        constexpr int R = decltype(rows_tag)::value;
-        constexpr int rows_per_block = 4 * R;
-        const dim3 grid((unsigned)((g.rows() + rows_per_block - 1) / rows_per_block));
-        if (g.mir.n > 0)
-            hipLaunchKernelGGL((first_hop_rows_kernel<PPL, R, true>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
-        else
-            hipLaunchKernelGGL((first_hop_rows_kernel<PPL, R, false>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
-    };
-    if (rows_env == 4) go(std::integral_constant<int, 4>{});
-    else if (rows_env == 16) go(std::integral_constant<int, 16>{});
-    else if (rows_env == 2) go(std::integral_constant<int, 2>{});
-    else go(std::integral_constant<int, kRowsPerWave>{});
 }
 
 // HLL first hop of the regular rows alone (ss_fused_hop_stage owns the hub pass that follows)
@@ -301,10 +197,9 @@ template <int PPL>
 static int launch_hll_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
                            bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, hipStream_t s)
 {
-    static const bool interleave = !(getenv("SS_HLL_ROW_MAP") && atoi(getenv("SS_HLL_ROW_MAP")) == 0);  // (measurement hook, see the kernel)
     ProfileSpan span(s, SS_PROF_FIRST_HOP_HLL);
     hipLaunchKernelGGL((hll_first_hop_kernel<PPL>), dim3((unsigned)((g.rows() + 16 * kHllRows - 1) / (16 * kHllRows) + lead)), dim3(256), 0, s, g,
-                       p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, interleave);
+                       p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -335,13 +230,13 @@ int launch_first_hop(const GraphArgs &g, const uint64_t *a, const uint64_t *b, u
         if (rc != SS_OK) return rc;
         {
             ProfileSpan span(s, SS_PROF_FIRST_HOP_MH);
-            launch_minhash_rows<PPL>(g, a, b, mh_out, p, prm, hubs, s);
+            launch_minhash_rows<PPL>(g, a, b, mh_out, p, hubs, s);
         }
         SS_LAUNCH_CHECK();
         if (lead > 0) return SS_OK;  // (the hub units of both tables were hosted by the HLL launch)
         return launch_first_hop_hub_only(g, a, b, PPL * kWave, mh_out, p, hll_out, cards_out, cards_stride, prm, s);
     }
-    if (mh_out) return launch_first_hop_v<PPL, true, false>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, prm, s);
+    if (mh_out) return launch_first_hop_mh<PPL>(g, a, b, mh_out, p, prm, s);
     // HLL alone: 16-lane-per-row kernel for the regular rows, the cooperative hub kernel for the rest
     const bool hubs = g.hub_rows && g.hub_count;
     const int lead = hub_lead_blocks(hubs);

@@ -26,18 +26,12 @@
 // they are hub units (ss_hub.hpp) hosted by the launches before and after this one -- not by this one: the kernel sits exactly at its
 // 96-VGPR budget, and a hub branch, whatever it contained, cost the row path 64 bytes of scratch and 30 us (round 4).
 // P = 64 * PPL, M = 256 (p = 8) only -- the shapes ss_first_hop has a kernel for.
-#include <cstdlib>
-
 #include "ss_hub.hpp"
 
 namespace ss {
 
 constexpr int kFusedRows = 4;
-#ifndef SS_HLL_INFLIGHT
-#define SS_HLL_INFLIGHT 7
-#define SS_HLL_LDS 7
-#endif
-constexpr int kHllInFlight = SS_HLL_INFLIGHT;
+constexpr int kHllInFlight = 7;  // neighbour chunks per lane requested into registers up front
 
 struct HllPosted {  // one lane group's view of its row while the row's first chunks are in flight
     int64_t i;
@@ -63,7 +57,7 @@ __device__ __forceinline__ void hll_post(HllPosted &h, const uint8_t *__restrict
 // neighbour rows kHllInFlight .. kHllInFlight + kHllLds - 1 of every lane group travel into LDS instead of registers
 // (global_load_lds_dwordx4: no VGPR destination; one instruction = one neighbour of each of the wavefront's four rows, landing as
 // 64 lanes x 16 B = 1 KiB at the wave-uniform LDS address): rows of up to 16 neighbours need no load after the MinHash walk
-constexpr int kHllLds = SS_HLL_LDS;
+constexpr int kHllLds = 7;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(1))) const uint32_t global_u32;
 
@@ -177,22 +171,12 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
         const bool hub = skip_hubs && h.deg > g.hub_threshold;
         h.write = ok && !hub;
         h.total = h.write ? table_hop_total(h.deg, h.i < m.n_self, skip_self) : 0;
-        if constexpr (!(SS_FUSED_ABLATE & 2)) {
         hll_post<0>(h, hll_in, ids_cur.my_nb, c);              // HLL rows of chunk k
         hll_post_lds<kHllInFlight>(h, hll_in, ids_cur.my_nb, c, lds_wave);
-        }
         const Ids ids_next = load_ids(chunk + stride, rp_next); // ids of chunk k + 1 (its bounds arrived during the last walk)
         const int64_t rp_after = load_bounds(chunk + 2 * stride);  // bounds of chunk k + 2
-        if constexpr (!(SS_FUSED_ABLATE & 1)) {
 #pragma unroll 1
         for (int r = 0; r < m.rows; ++r) m.row(r, mh_out);       // MinHash first hop of chunk k: VALU work under all of the above
-        }
-        if constexpr (SS_FUSED_ABLATE & 2) {
-            rp_cur = rp_next;
-            rp_next = rp_after;
-            ids_cur = ids_next;
-            continue;
-        }
         u32x4 ae = {0u, 0u, 0u, 0u}, ao = {0u, 0u, 0u, 0u};
         hll_fold(h, ae, ao);
         if constexpr (kHllLds > 0) {
@@ -278,9 +262,7 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
     // 40 per CU: 148.7 / 147.8 / 146.2-146.9 / 149.9 / 149.2 / 151.2 us.  ppa / citation2 size (140 / 715 blocks per CU): 15 / 20 / 30 /
     // 48 / 64 / 100 / 200 / all: 1 832 / 1 819 / 1 774 / 1 724 / 1 738 / 1 728 / 1 751 / 1 748 us and 3 540 / 3 499 / 3 448 / 3 418 / 3 408 /
     // 3 419 / 3 457 / 3 814 us
-    static const int wg_per_cu_env = getenv("SS_FUSED_WG_PER_CU") ? atoi(getenv("SS_FUSED_WG_PER_CU")) : 0;
-    const int wg_per_cu = (wg_per_cu_env > 0 && wg_per_cu_env <= 4096) ? wg_per_cu_env  // (a bad value falls back to the default)
-                          : (blocks > 256u * 128u ? 64 : 20);
+    const int wg_per_cu = blocks > 256u * 128u ? 64 : 20;
     const unsigned grid = blocks < (unsigned)(256 * wg_per_cu) ? blocks : (unsigned)(256 * wg_per_cu);
     g.skip_self = own_hop1 ? skip_word : nullptr;
     {

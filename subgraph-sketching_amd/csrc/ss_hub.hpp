@@ -35,10 +35,10 @@ inline int hub_lead_blocks(bool hubs)
 {
     if (hubs) note_hub_call();
     static const bool launches = getenv("SS_HUB_LAUNCHES") && atoi(getenv("SS_HUB_LAUNCHES")) != 0;
-    static const int n = getenv("SS_HUB_LEAD_BLOCKS") ? atoi(getenv("SS_HUB_LEAD_BLOCKS")) : kHubLeadBlocks;
-    // (at least 4: the launches split the leading workgroups by integer division -- a quarter of them for the hop-1 HLL units, half
-    // for the MinHash units -- and every share must hold a workgroup)
-    return hubs && !launches ? (n >= 4 && n <= 65536 ? n : kHubLeadBlocks) : 0;
+    // (the launches split the leading workgroups by integer division -- a quarter of them for the hop-1 HLL units, half for the MinHash
+    // units -- and every share must hold a workgroup)
+    static_assert(kHubLeadBlocks >= 4, "every share of the leading workgroups holds one");
+    return hubs && !launches ? kHubLeadBlocks : 0;
 }
 
 struct HubCounts {
@@ -244,8 +244,7 @@ struct FirstHopHubLds {
 // (first_hop_hub_units below: a hub row or a slice of a mega row; update_hub_first_kernel of ss_update.hip: a whole listed row)
 template <int PPL, int WAVES, bool DO_MH, bool DO_HLL>
 __device__ __forceinline__ void first_hop_hub_walk(FirstHopHubLds<PPL> &s, int64_t i, const int32_t *__restrict__ nb, int deg, int lo, int hi,
-                                                   int p, const uint64_t (&a)[PPL], const uint64_t (&b)[PPL], int lane, int wave,
-                                                   bool force_exact)
+                                                   int p, const uint64_t (&a)[PPL], const uint64_t (&b)[PPL], int lane, int wave)
 {
     constexpr int P = PPL * kWave, THREADS = WAVES * kWave;
     for (int t = threadIdx.x; t < 256; t += THREADS) s.hll_row[t] = 0u;
@@ -259,7 +258,7 @@ __device__ __forceinline__ void first_hop_hub_walk(FirstHopHubLds<PPL> &s, int64
     if (DO_MH) {
         // the two-phase walk (ss_walks.hpp: 4-5 instead of 10 VALU per neighbour and permutation) over this wavefront's batches; a
         // wavefront whose share is ambiguous (duplicated minimum, key collision) redoes its share exactly
-        first_hop_minhash_row<PPL>(nb + lo, deg - lo, hi - lo, i, p, a, b, acc, lane, false, wave, WAVES, force_exact);
+        first_hop_minhash_row<PPL>(nb + lo, deg - lo, hi - lo, i, p, a, b, acc, lane, false, wave, WAVES);
 #pragma unroll
         for (int q = 0; q < PPL; ++q) atomicMin(&s.mh_row[lane + kWave * q], acc[q]);
     }
@@ -307,7 +306,7 @@ template <int PPL, int WAVES, bool DO_MH, bool DO_HLL>
 __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int worker, int n_workers, const uint64_t *__restrict__ pa,
                                                     const uint64_t *__restrict__ pb, uint32_t *__restrict__ mh_out, int p,
                                                     uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride,
-                                                    const EstimatorTables &est, bool want_cards_in, FirstHopHubLds<PPL> &s, bool force_exact)
+                                                    const EstimatorTables &est, bool want_cards_in, FirstHopHubLds<PPL> &s)
 {
     constexpr int P = PPL * kWave, THREADS = WAVES * kWave;
     constexpr int kTicket = DO_MH ? 3 : 4;
@@ -325,7 +324,7 @@ __device__ __forceinline__ void first_hop_hub_units(const GraphArgs &g, int work
     const int64_t n_self = g.n_self_dev ? *g.n_self_dev : g.n_self;
 
     auto walk = [&](int64_t i, const int32_t *nb, int deg, int lo, int hi) {
-        first_hop_hub_walk<PPL, WAVES, DO_MH, DO_HLL>(s, i, nb, deg, lo, hi, p, a, b, lane, wave, force_exact);
+        first_hop_hub_walk<PPL, WAVES, DO_MH, DO_HLL>(s, i, nb, deg, lo, hi, p, a, b, lane, wave);
     };
     auto finish = [&](int64_t i) {  // (no hub row is empty)
         first_hop_hub_finish<PPL, DO_MH, DO_HLL, true>(s, i, false, mh_out, hll_out, cards_out, cards_stride, est, want_cards, lane, g.mir);

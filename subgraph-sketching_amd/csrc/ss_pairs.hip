@@ -235,9 +235,9 @@ void pair_features_kernel(const int64_t *__restrict__ links, int64_t B, int64_t 
 // load, and the group walks the chunk keeping u's MinHash rows, HLL digests and cardinalities in registers while u does not
 // change: such a pair costs H * R + 8 + 4H + 4H(H+2) bytes instead of 2H * R + ... (2 412 instead of 4 708 at H = 3).  A pair's
 // features depend on its own rows only, so rows are bit-identical to pair_features_kernel's whatever the order or the chunking.
-// CAP: ask the register allocator for 4 (H <= 2) / 3 (H = 3) wavefronts per SIMD (some spills) instead of 3 / 2
-template <int H, int TP, int TM, bool CAP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H == 3 ? 3 : 4) : 1))) void pair_features_runs_kernel(const int64_t *__restrict__ links, const int32_t *__restrict__ order,
+// The register allocator is asked for 4 (H <= 2) / 3 (H = 3) wavefronts per SIMD (some spills) instead of 3 / 2
+template <int H, int TP, int TM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(H == 3 ? 3 : 4))) void pair_features_runs_kernel(const int64_t *__restrict__ links, const int32_t *__restrict__ order,
                                                                  int64_t B, int64_t N, int K, HopTables tabs,
                                                                  const float *__restrict__ cards, int64_t cards_stride, ss_hll_params prm,
                                                                  uint32_t flags, float *__restrict__ out, int32_t *__restrict__ err,
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAP ? (H ==
                 }
             }
             // lane c < H^2 finishes combination c, as pair_features_kernel does
-            // (written out, not a shared function: that moved the scratch bytes of the CAP builds -- DESIGN_EXPERIMENTS "One source for the pair finish")
+            // (written out, not a shared function: that moved the scratch bytes of the capped builds -- DESIGN_EXPERIMENTS "One source for the pair finish")
             const int my_mz = lane_select(mz, l);
             const float my_hs = lane_select(hs, l);
             float my_I = 0.0f;
@@ -401,23 +401,17 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &ta
     // 8 192, 2.18 with 2 048, 2.06 with 1 280).  Measured and rejected: 64- / 128-thread workgroups, persistent
     // grids of 512 - 1 024 workgroups, and a software-pipelined variant that requests the next pair's rows in the middle of the
     // current pair's arithmetic (165 VGPRs: +1.5 % on batches of millions, -7 % at B = 65 536).
-    // SS_PAIR_GRID / SS_PAIR_PER_GROUP: tuning hooks of tools/probe_pairs.py
-    static const int grid_env = getenv("SS_PAIR_GRID") ? atoi(getenv("SS_PAIR_GRID")) : 0;
-    static const int per_group_env = getenv("SS_PAIR_PER_GROUP") ? atoi(getenv("SS_PAIR_PER_GROUP")) : 0;
-    const int per_group = per_group_env > 0 ? per_group_env : (B <= 1024 * pairs_per_block ? 1 : 2);
-    const int64_t max_blocks = grid_env > 0 ? grid_env : kPairGrid;
+    const int per_group = B <= 1024 * pairs_per_block ? 1 : 2;
     int64_t blocks = (B + per_group * pairs_per_block - 1) / (per_group * pairs_per_block);
-    if (blocks > max_blocks) blocks = max_blocks;
+    if (blocks > kPairGrid) blocks = kPairGrid;
     if (blocks < 1) blocks = 1;
     // Which register budget (TP = 128 only: one more instantiation per hop count).  Walks with locality: the capped build (OCC, see the
     // kernel).  As-listed random pairs, round 6 (tools/probe_pairs_variants.py, profiles/round6_pairs_variants.txt; tables of 0.2 - 6.4
     // GB, cold and after 2 000 launches): at H = 3 the fourth wavefront per SIMD wins at every table size while the launch is small --
     // B = 65 536: -4 .. -9 %, B = 261 424 (ogbl-citation2's batch): -1 .. -5 % -- and is level (+-0.6 %) at 4 M pairs; at H = 2 the fifth
     // wins 1 - 4 % at B = 65 536 (the bench step's query, ELPH batches) and LOSES 2 - 9 % at 261 424 on tables above ~1.5 GB.
-    // SS_PAIR_OCC = 0 / 1 forces a build (probes).
-    static const int occ_env = getenv("SS_PAIR_OCC") ? atoi(getenv("SS_PAIR_OCC")) : -1;
     const bool small_launch = H == 3 ? B <= ((int64_t)1 << 21) : B <= 65536;
-    const bool occ = occ_env >= 0 ? occ_env != 0 : (grouped || small_launch);
+    const bool occ = grouped || small_launch;
     {
         ProfileSpan span(stream, SS_PROF_PAIRS, true);
         constexpr bool HAS_OCC = TP == 128 && H >= 2;  // (elsewhere both names below are the one default-budget kernel)
@@ -458,22 +452,16 @@ int launch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int6
                      hipStream_t stream)
 {
     // pairs per chunk: 16 once that still leaves >= 32 768 chunks (eight rounds of 16-group workgroups over 256 CUs); fewer for
-    // smaller batches so that the chip stays full.  SS_PAIR_RUN_CHUNK: tuning hook
-    static const int k_env = getenv("SS_PAIR_RUN_CHUNK") ? atoi(getenv("SS_PAIR_RUN_CHUNK")) : 0;
-    int64_t K = k_env > 0 && k_env <= kRow ? k_env : B / 32768;
+    // smaller batches so that the chip stays full
+    int64_t K = B / 32768;
     K = K < 1 ? 1 : (K > kRow ? kRow : K);
     const int64_t chunks = (B + K - 1) / K;
     int64_t blocks = (chunks + 256 / kRow - 1) / (256 / kRow);
     if (blocks > kPairGrid) blocks = kPairGrid;
-    static const bool cap = !(getenv("SS_PAIR_RUN_CAP") && atoi(getenv("SS_PAIR_RUN_CAP")) == 0);
     {
         ProfileSpan span(stream, SS_PROF_PAIRS);
-        if (cap)
-            hipLaunchKernelGGL((pair_features_runs_kernel<H, TP, 256, true>), dim3((unsigned)blocks), dim3(256), 0, stream, links, order, B, N, (int)K,
-                               tabs, cards, cards_stride, prm, flags, out, err, degrees);
-        else
-            hipLaunchKernelGGL((pair_features_runs_kernel<H, TP, 256, false>), dim3((unsigned)blocks), dim3(256), 0, stream, links, order, B, N, (int)K,
-                               tabs, cards, cards_stride, prm, flags, out, err, degrees);
+        hipLaunchKernelGGL((pair_features_runs_kernel<H, TP, 256>), dim3((unsigned)blocks), dim3(256), 0, stream, links, order, B, N, (int)K,
+                           tabs, cards, cards_stride, prm, flags, out, err, degrees);
     }
     SS_LAUNCH_CHECK();
     return SS_OK;

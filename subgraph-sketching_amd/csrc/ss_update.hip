@@ -385,7 +385,7 @@ __global__ __launch_bounds__(kUpdHubThreads) void update_hub_first_kernel(GraphA
         const int64_t rb = g.rowptr[i];
         const int deg = (int)(g.rowptr[i + 1] - rb);
         const int total = deg + (i < n_self ? 1 : 0);
-        first_hop_hub_walk<PPL, kUpdHubWaves, DO_MH, DO_HLL>(s, i, g.col + rb, deg, 0, total, p, a, b, lane, wave, false);
+        first_hop_hub_walk<PPL, kUpdHubWaves, DO_MH, DO_HLL>(s, i, g.col + rb, deg, 0, total, p, a, b, lane, wave);
         // (the update keeps the all-zero rule for a listed row without any neighbour; the build's hub units have no such rule)
         if (wave == 0) first_hop_hub_finish<PPL, DO_MH, DO_HLL, false>(s, i, total == 0, mh_out, hll_out, cards_out, cards_stride, est, DO_HLL, lane, g.mir);
         __syncthreads();

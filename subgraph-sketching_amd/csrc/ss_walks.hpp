@@ -4,14 +4,6 @@
 #pragma once
 #include "ss_common.hpp"
 
-// Measurement build only (SS_EXTRA_FLAGS=-DSS_FUSED_ABLATE=<mask>, tools/ablate_fused.sh): parts of the fused stage's wavefront are left out so
-// that what each costs can be read off the launch's duration -- the results of such a build are WRONG by construction.
-//   1: no MinHash rows at all   2: no HLL side (post / fold / finish)   4: no exact evaluation of the winners (phase 2 + ambiguity)
-//   8: no two-phase walk (the update loop)   16: neighbour ids are not hashed   32: no winner fetch (the two ds_bpermute per permutation and segment)
-#ifndef SS_FUSED_ABLATE
-#define SS_FUSED_ABLATE 0
-#endif
-
 namespace ss {
 
 __device__ __forceinline__ u32x4 shfl_xor4(u32x4 v, int mask)
@@ -74,35 +66,15 @@ __device__ __forceinline__ u32x4 minhash_walk128(const uint32_t *__restrict__ mh
     u32x4 acc = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     // one pair of neighbours per iteration, NOT batched: batches of 2 / 4 pairs (masked or clamped) measured 194-198 us
     // against 187 us for this loop -- eight waves per SIMD already cover the latency, extra instructions only cost issue slots.
-    // Round 3, all three shapes (SS_MH_BATCH = 1 / 2 / 3 / 4 pairs per iteration): collab size 191.4 / 193.1 / 196.2 / 199.4 us, ppa size
+    // Round 3, all three shapes (1 / 2 / 3 / 4 pairs per iteration): collab size 191.4 / 193.1 / 196.2 / 199.4 us, ppa size
     // 2 936 / 2 977 / 2 972 / 2 975 us, citation2 size (1.5 GB table, HBM-resident) 5 661 / 5 566-5 591 / 5 572-5 604 / 5 581-5 593 us:
     // -1.5 % where the table lives in HBM, +1 % where it does not.  Not worth a second instantiation.
-#ifndef SS_MH_BATCH
-#define SS_MH_BATCH 1
-#endif
-#if SS_MH_BATCH == 1
     for (int t0 = 0; t0 < head; t0 += 2) {  // wave-uniform trip count
         const int s0 = __builtin_amdgcn_readlane(my_nb, t0), s1 = __builtin_amdgcn_readlane(my_nb, (t0 + 1) & (kWave - 1));
         const int t = t0 + sg;
         const int64_t j = t < deg ? (int64_t)(sg ? s1 : s0) : self_row;
         if (t < head) acc = min4(acc, *reinterpret_cast<const u32x4 *>(mh_in + j * 128 + 4 * c));
     }
-#else
-    for (int t0 = 0; t0 < head; t0 += 2 * SS_MH_BATCH) {  // wave-uniform trip count
-        u32x4 x[SS_MH_BATCH];
-#pragma unroll
-        for (int k = 0; k < SS_MH_BATCH; ++k) {
-            const int s0 = __builtin_amdgcn_readlane(my_nb, (t0 + 2 * k) & (kWave - 1));
-            const int s1 = __builtin_amdgcn_readlane(my_nb, (t0 + 2 * k + 1) & (kWave - 1));
-            const int t = t0 + 2 * k + sg;
-            const int64_t j = t < deg ? (int64_t)(sg ? s1 : s0) : self_row;
-            x[k] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            if (t < head) x[k] = *reinterpret_cast<const u32x4 *>(mh_in + j * 128 + 4 * c);
-        }
-#pragma unroll
-        for (int k = 0; k < SS_MH_BATCH; ++k) acc = min4(acc, x[k]);
-    }
-#endif
     if (total > kWave) acc = min4(acc, minhash_walk(mh_in, nb, deg, total, self_row, kWave + sg, 2, 128, c));
     return acc;
 }
@@ -433,17 +405,17 @@ __device__ __forceinline__ bool first_hop_minhash_fast(const int32_t *__restrict
 
 // ---- one first-hop row (hop 1 from node ids), shared by the build kernels and the update kernels -----------------------------------
 // MinHash by one wavefront, over its batches first_batch, first_batch + batch_stride, ...: the two-phase walk, the wavefront's share
-// redone by the exact walk when any lane flags it ambiguous (or force_exact), `acc` left at 0xFFFFFFFF when the wavefront has no batch.
+// redone by the exact walk when any lane flags it ambiguous, `acc` left at 0xFFFFFFFF when the wavefront has no batch.
 // zero_empty: a row without in-edge and self loop becomes the all-zero row (PyG default) -- for a wavefront that owns the whole row.
 template <int PPL>
 __device__ __forceinline__ void first_hop_minhash_row(const int32_t *__restrict__ nb, int deg, int total, int64_t self_row, int p,
                                                       const uint64_t (&a)[PPL], const uint64_t (&b)[PPL], uint32_t (&acc)[PPL], int lane,
-                                                      bool zero_empty, int first_batch = 0, int batch_stride = 1, bool force_exact = false)
+                                                      bool zero_empty, int first_batch = 0, int batch_stride = 1)
 {
 #pragma unroll
     for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
     if (first_batch * kWave < total) {  // (wave-uniform) the wavefront has at least one batch
-        const bool amb = force_exact || first_hop_minhash_fast<PPL>(nb, deg, total, self_row, a, b, acc, lane, first_batch, batch_stride);
+        const bool amb = first_hop_minhash_fast<PPL>(nb, deg, total, self_row, a, b, acc, lane, first_batch, batch_stride);
         if (__any(amb)) {
 #pragma unroll
             for (int q = 0; q < PPL; ++q) acc[q] = 0xFFFFFFFFu;
@@ -577,7 +549,7 @@ struct MinhashRows {
     __device__ __forceinline__ void set_batch(int64_t id)
     {
         nid = id;
-        const uint64_t hv = (SS_FUSED_ABLATE & 16) ? (uint64_t)(nid + 1) : hash_u64((uint64_t)(nid + 1));
+        const uint64_t hv = hash_u64((uint64_t)(nid + 1));
         hv_lo = (uint32_t)hv;
         hv_hi = (uint32_t)(hv >> 32);
     }
@@ -640,7 +612,6 @@ struct MinhashRows {
                 // a row that lists itself would meet its implicit self loop as a duplicate (ambiguous for every permutation)
                 seen_self |= __any(lane >= s_lo && lane < s_hi && nid == i);
                 int k = s_lo;
-                if constexpr (!(SS_FUSED_ABLATE & 8)) {
                 for (; k + 3 < s_hi; k += 4) {
                     uint32_t hl[4];
 #pragma unroll
@@ -649,7 +620,6 @@ struct MinhashRows {
                     for (int u = 0; u < 4; ++u) update(hl[u], (uint32_t)(k + u));
                 }
                 for (; k < s_hi; ++k) update((uint32_t)__builtin_amdgcn_readlane((int)hv_lo, k), (uint32_t)k);
-                } else if (s_hi > s_lo) update((uint32_t)__builtin_amdgcn_readlane((int)hv_lo, s_lo), (uint32_t)s_lo);
                 pos = base + (s_hi > s_lo ? s_hi : s_lo);
                 const bool last = pos >= p1;
                 if (last && self && !seen_self) update((uint32_t)__builtin_amdgcn_readlane((int)hv_lo, kNb + r), (uint32_t)(kNb + r));
@@ -657,8 +627,7 @@ struct MinhashRows {
 #pragma unroll
                 for (int q = 0; q < PPL; ++q) {
                     const int slot = (int)(m1[q] & 63u);
-                    const uint32_t cand_lo = (SS_FUSED_ABLATE & 32) ? hv_lo : (uint32_t)__shfl((int)hv_lo, slot);
-                    const uint32_t cand_hi = (SS_FUSED_ABLATE & 32) ? hv_hi : (uint32_t)__shfl((int)hv_hi, slot);
+                    const uint32_t cand_lo = (uint32_t)__shfl((int)hv_lo, slot), cand_hi = (uint32_t)__shfl((int)hv_hi, slot);
                     const bool changed = m1[q] != before[q];
                     h1_lo[q] = changed ? cand_lo : h1_lo[q];
                     h1_hi[q] = changed ? cand_hi : h1_hi[q];
@@ -666,10 +635,6 @@ struct MinhashRows {
                 if (last) break;
             }
             bool ambiguous = false;
-            if constexpr (SS_FUSED_ABLATE & 4) {
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) acc[q] = m1[q] ^ h1_lo[q] ^ h1_hi[q] ^ m2[q];
-            } else
 #pragma unroll
             for (int q = 0; q < PPL; ++q) {
                 // x = a * h + b (mod 2^64); the permuted hash is x mod (2^61 - 1) = (x & M) + (x >> 61) [- M], whose low word

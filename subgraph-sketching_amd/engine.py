@@ -349,8 +349,7 @@ class ElphHashes(object):
             hll_prev = self._init_hll_u8(num_nodes, device)
             table[0] = HopSketch(mh_prev, hll_prev, home)
         # (collab-like -4 %, ppa-like -5 %, citation2-like -1.2 % per step against the unfused schedule)
-        if (shard is None and fused and h >= 2 and self.num_perm == 128 and self.fuse_hop_stage
-                and num_nodes * self.m <= knobs.FUSED_STAGE_MAX_TABLE_BYTES):
+        if shard is None and fused and h >= 2 and self.num_perm == 128 and self.fuse_hop_stage:
             # ONE call for hops 1 and 2: hop-1 HLL first (hop-2 HLL rows need that table complete), then hop-1 MinHash + hop-2 HLL
             # in one launch (the VALU-bound first hop and the memory-bound table hop interleaved inside every wavefront,
             # csrc/ss_fused_hop.hip), then hop-2 MinHash; further hops unfused

@@ -28,7 +28,7 @@ from .engine import LABEL_LOOKUP, ElphHashes  # noqa: F401
 from .head import StructureHead  # noqa: F401
 
 _KNOBS = ('KERNEL_TIMER', 'GROUP_LINKS_MIN', 'GROUP_GATHER_MIN', 'LAZY_MINHASH', 'DEFER_FIRST_HOP', 'DEFER_TABLE_HOP', 'HUB_THRESHOLD',
-          'REUSE_CSR_BY_CONTENT', 'FUSED_STAGE_MAX_TABLE_BYTES')
+          'REUSE_CSR_BY_CONTENT')
 
 
 def __getattr__(name):  # hashing.DEFER_TABLE_HOP etc. read the live value in knobs

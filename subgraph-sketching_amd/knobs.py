@@ -50,13 +50,6 @@ HUB_THRESHOLD = int(os.environ['SS_HUB_THRESHOLD']) if 'SS_HUB_THRESHOLD' in os.
 REUSE_CSR_BY_CONTENT = os.environ.get('SS_REUSE_CSR', '1') != '0'
 
 
-
-# largest hop-1 HLL table (bytes) ss_fused_hop_stage is used for.  The first version of the stage lost on tables that do not fit
-# the 256 MiB Infinity Cache (citation2-like: 4.40 against 4.09 ms for the two launches) and was capped there; with LDS landings
-# and batched tail walks it wins there too (3.70 against 3.92 ms), so there is no cap any more.  SS_FUSED_STAGE_MAX_MB:
-# measurement hook
-FUSED_STAGE_MAX_TABLE_BYTES = int(os.environ.get('SS_FUSED_STAGE_MAX_MB', str(1 << 30))) << 20
-
 # source columns per personalised-PageRank batch (heuristics.PPR / personalized_pagerank): the iterate is fp64 [N, S] and every
 # step gathers one S * 8-byte row per in-edge, so S = 64 makes each wavefront load of it a 512-byte row (the MinHash table hop's
 # access pattern); at ogbl-collab size the two iterates (2 x 120 MB) stay in the 256 MiB Infinity Cache.  Lowered automatically

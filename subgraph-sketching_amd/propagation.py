@@ -88,8 +88,7 @@ class MinhashPropagation(object):
             out_u32 = torch.empty((x.size(0), x.size(1)), dtype=torch.int32, device=device)
             P, p = x.size(1), hop0[1]
             defer_first = knobs.DEFER_FIRST_HOP if self.defer_first_hop is None else self.defer_first_hop
-            if (defer_first and knobs.LAZY_MINHASH and x.device == device and p == 8 and P % 64 == 0 and P <= 256
-                    and x.size(0) * 256 <= knobs.FUSED_STAGE_MAX_TABLE_BYTES):
+            if defer_first and knobs.LAZY_MINHASH and x.device == device and p == 8 and P % 64 == 0 and P <= 256:
                 perms = hop0[0]
 
                 def fill(csr=csr, perms=perms, P=P, p=p, out=out_u32, device=device):

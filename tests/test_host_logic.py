@@ -546,3 +546,29 @@ def test_linear_counting_table_has_an_independent_restatement(ssa):
         ulp = np.spacing(np.maximum(np.abs(want), np.float32(1e-30)))
         assert np.all(np.abs(got[1:] - want) <= 2 * ulp), p
         assert got[m] == 0.0 and np.all(np.diff(got[1:]) < 0)  # V = m: empty sketch -> 0; strictly decreasing in V
+
+
+def test_every_environment_hook_is_listed_in_the_integration_guide():
+    """INTEGRATION.md section 7 promises "every SS_* variable and module switch": every name the library reads with getenv("SS_...")
+    (csrc/*.hip, *.hpp) and every SS_... name the package reads from the environment (subgraph-sketching_amd/*.py) has a row there."""
+    import glob
+    import re
+    from conftest import REPO
+    pkg = os.path.join(REPO, 'subgraph-sketching_amd')
+    read = {}
+    for path in sorted(glob.glob(os.path.join(pkg, 'csrc', '*.hip')) + glob.glob(os.path.join(pkg, 'csrc', '*.hpp'))):
+        for name in re.findall(r'getenv\(\s*"(SS_[A-Z0-9_]+)"', open(path).read()):
+            read.setdefault(name, os.path.basename(path))
+    env_read = (r'environ\.get\(\s*[\'"](SS_[A-Z0-9_]+)[\'"]', r'environ\[\s*[\'"](SS_[A-Z0-9_]+)[\'"]\s*\]',
+                r'getenv\(\s*[\'"](SS_[A-Z0-9_]+)[\'"]', r'[\'"](SS_[A-Z0-9_]+)[\'"]\s+(?:not\s+)?in\s+os\.environ')
+    for path in sorted(glob.glob(os.path.join(pkg, '*.py'))):
+        text = open(path).read()
+        for pattern in env_read:
+            for name in re.findall(pattern, text):
+                read.setdefault(name, os.path.basename(path))
+    assert {'SS_SELF_SKIP', 'SS_HUB_LAUNCHES', 'SS_HUB_THRESHOLD', 'SS_EXCHANGE', 'SS_LIB'} <= set(read), sorted(read)  # both scans find something
+    guide = open(os.path.join(REPO, 'INTEGRATION.md')).read()
+    section = guide[guide.index('\n## 7. Knobs'):guide.index('\n### Behavioural differences from the reference')]
+    listed = set(re.findall(r'SS_[A-Z0-9_]+', section))
+    missing = {name: where for name, where in read.items() if name not in listed}
+    assert not missing, f'read by the code, absent from INTEGRATION.md section 7: {missing}'

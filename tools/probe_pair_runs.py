@@ -1,8 +1,7 @@
 """probe: the query over link sets with and without locality -- random pairs, pairs ordered by source, an evaluation-style set
 (`--negs` negatives per source listed together) -- through ss_pair_features (every pair reads its 2h rows), ss_pair_features_grouped
 without an order (runs as listed) and with the order of ss_group_links_by_source (grouping time included).  Rows are compared bit for bit.
-usage (GPU box): python tools/probe_pair_runs.py [--nodes N] [--hops 3] [--links L] [--json out.json]
-hooks: SS_PAIR_RUN_CAP=0 (uncapped registers), SS_PAIR_RUN_CHUNK=k (pairs per lane-group chunk)"""
+usage (GPU box): python tools/probe_pair_runs.py [--nodes N] [--hops 3] [--links L] [--json out.json]"""
 import argparse
 import json
 import os

@@ -1,8 +1,6 @@
 """probe: ss_pair_features kernel time against the batch size (ELPH batches of 1-2 k pairs up to BUDDY chunks of millions)
 and the hop count.  HIP events on the launch stream around 20 back-to-back launches (ss_time_pair_features).
-usage (GPU box): python tools/probe_pairs.py [--json out.json] [--nodes N]
-Tuning hooks read once per process by the library: SS_PAIR_GRID (max workgroups), SS_PAIR_PER_GROUP (pairs per 16-lane group
-the grid is sized for)."""
+usage (GPU box): python tools/probe_pairs.py [--json out.json] [--nodes N]"""
 import argparse
 import json
 import os
