@@ -729,9 +729,8 @@ class ElphHashes(object):
     def _topk_arguments(self, sources, hash_table, k, exclude, what='sources'):
         """what topk_candidates, topk_links and rank_links (its links, flattened: what='links') check before a device is touched:
         (sources, exclude or None, N, P)"""
-        src = torch.as_tensor(sources)
-        if src.dim() != 1 or src.dtype.is_floating_point or src.dtype == torch.bool:
-            raise ValueError(f'{what} must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
+        from .candidates import _check_host_ids, _id_list
+        src = _id_list(sources, what)
         N, P = _table_shape(hash_table, 1)
         _check_sizes(P, self.p)
         k = int(k)
@@ -742,9 +741,7 @@ class ElphHashes(object):
             ex = torch.as_tensor(exclude)
             if ex.dim() != 2 or ex.size(0) != 2 or ex.dtype.is_floating_point or ex.dtype == torch.bool:
                 raise ValueError(f'exclude must be an integer [2, E] edge_index, got {ex.dtype} {tuple(ex.shape)}')
-        # CPU ids are checked here, as the reference's CPU indexing would; device ids are reported late (strict_bounds)
-        if not src.is_cuda and src.numel() and (int(src.min()) < -N or int(src.max()) >= N):
-            raise IndexError(f'{what} refer to nodes outside [-{N}, {N})')
+        _check_host_ids(src, N, what)  # CPU ids are checked here, as the reference's CPU indexing would; device ids are reported late (strict_bounds)
         if ex is not None and not ex.is_cuda and ex.numel() and (int(ex.min()) < -N or int(ex.max()) >= N):
             raise IndexError(f'exclude refers to nodes outside [-{N}, {N})')
         return src, ex, N, P

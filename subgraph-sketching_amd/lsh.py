@@ -11,15 +11,13 @@ at least min_bands bands.  The 64-bit key the bands are sorted by only finds the
 slices meet in one range with probability about 2^-64 per pair, and the one way such a meeting could show is a range of more than
 max_bucket entries made of several smaller buckets, which is dropped like a large bucket.
 """
-from ctypes import c_void_p
-
-import numpy as np
 import torch
 
 from . import _native
-from ._runtime import _Span, _check_sizes, _compute_device, _ptr, _stream, _take_error
+from ._runtime import _Span, _check_sizes, _compute_device, _ptr, _stream
+from .candidates import _block_walk, _check_scoring, _int, _rows, _topk_rows
 from .containers import HopSketch, _packed_minhash_of
-from .engine import TOPK_SENTINEL, _csr_row_keys, _decode_topk_keys, _encode_topk_keys, _exclude_csr, _table_ptrs, _table_shape
+from .engine import _table_shape
 
 # rows depend on neither constant (not user knobs)
 _LSH_BLOCK_BYTES = 1 << 30  # bound on the arrays of one block of sources: counts + offsets per (source, band), then the block's entries
@@ -54,16 +52,6 @@ class LshIndex(object):
     def __repr__(self):
         return (f'LshIndex(hop={self.hop}, rows={self.rows}, bands={self.bands}, num_nodes={self.num_nodes}, num_perm={self.num_perm}, '
                 f'max_bucket={self.max_bucket}, nbytes={self.nbytes})')
-
-
-def _int(value, name, lo, hi=None):
-    try:
-        v = int(value)
-    except (TypeError, ValueError):
-        raise ValueError(f'{name} must be an integer, got {value!r}')
-    if v != value or v < lo or (hi is not None and v > hi):
-        raise ValueError(f'{name} must lie in [{lo}, {hi if hi is not None else "..."}], got {value!r}')
-    return v
 
 
 def build_lsh_index(eh, hash_table, hop, rows, bands, max_bucket, key_bits):
@@ -116,124 +104,57 @@ def _arguments(eh, sources, index, exclude, min_bands):
     return src, ex, min_bands
 
 
-def _walk(eh, what, src, ex, index, min_bands, consume):
-    """the walk both queries share: blocks of sources bounded by _LSH_BLOCK_BYTES -- the entries of a block cannot be known before
-    its counts are -- , per block the count and fill launches, sort + unique (the pairs, in how many bands each), min_bands, the
-    exclude list, then consume(b0, u, keys, bands, err): sources [b0, b0 + len(u)) with wrapped ids u; the block's pairs as sorted
-    unique keys s * N + v (s: the source's place in the block) and their band counts; err: the word the launches report into.
-    Host reads: one per block of counts (the sizes), one per block with an exclude list (the size of its rows)."""
-    device = index.mh_u32.device
-    N, P, b = index.num_nodes, index.num_perm, index.bands
-    S = src.numel()
-    lk = src.to(device=device, dtype=torch.int64).contiguous()
-    strict, err = eh._bounds(device, f'{what}({S} sources, num_nodes={N})')
-    csr, err = _exclude_csr(ex, N, device, strict, err)
-    lib = _native.lib()
-    shape = (_ptr(index.mh_u32), P, index.rows, b, index.key_bits, _ptr(index.keys), _ptr(index.perm), index.max_bucket)
-    cap = max(1, _LSH_BLOCK_BYTES // _LSH_ENTRY_BYTES)
-    cblk = max(1, min(S, _LSH_BLOCK_BYTES // (12 * b), ((1 << 31) - 1) // b))
-    for c0 in range(0, S, cblk):
-        nc = min(cblk, S - c0)
-        counts = torch.empty((nc * b,), dtype=torch.int32, device=device)
-        with _Span('lsh_count', device):
-            _native.check(lib.ss_lsh_count(c_void_p(lk.data_ptr() + 8 * c0), nc, N, *shape, _ptr(counts), _ptr(err), _stream(device)),
-                          'ss_lsh_count')
-        offsets = torch.zeros((nc * b + 1,), dtype=torch.int64, device=device)
+def _leading(index, sources):  # (the two launches are module-level, so that the host walk can be rehearsed without a device)
+    return (_ptr(sources), sources.numel(), index.num_nodes, _ptr(index.mh_u32), index.num_perm, index.rows, index.bands, index.key_bits,
+            _ptr(index.keys), _ptr(index.perm), index.max_bucket)
+
+
+def _launch_count(index, sources, counts, err):
+    with _Span('lsh_count', index.mh_u32.device):
+        _native.check(_native.lib().ss_lsh_count(*_leading(index, sources), _ptr(counts), _ptr(err), _stream(index.mh_u32.device)), 'ss_lsh_count')
+
+
+def _launch_fill(index, sources, offsets, entries):
+    with _Span('lsh_fill', index.mh_u32.device):
+        _native.check(_native.lib().ss_lsh_fill(*_leading(index, sources), _ptr(offsets), _ptr(entries), _stream(index.mh_u32.device)), 'ss_lsh_fill')
+
+
+def _walk(eh, what, src, ex, index, min_bands):
+    """candidates._block_walk over the buckets of the index, to be called with a consume: blocks of sources bounded by _LSH_BLOCK_BYTES,
+    per block the count launch (a size per source and band), per group the fill launch, then sort + unique: the pairs, and in how many
+    bands each; min_bands is the filter"""
+    device, b = index.mh_u32.device, index.bands
+
+    def count(_c0, sources, err):
+        counts = torch.empty((sources.numel() * b,), dtype=torch.int32, device=device)
+        _launch_count(index, sources, counts, err)
+        offsets = torch.zeros((counts.numel() + 1,), dtype=torch.int64, device=device)
         torch.cumsum(counts, 0, out=offsets[1:])
-        ends = offsets[b::b].cpu().numpy()  # entries up to and including each source
-        a = 0
-        while a < nc:  # as many whole sources as fit the budget, one at least
-            base = int(ends[a - 1]) if a else 0
-            e = min(nc, max(a + 1, int(np.searchsorted(ends, base + cap, side='right'))))
-            total = int(ends[e - 1]) - base
-            sb = lk[c0 + a:c0 + e]
-            u = torch.where(sb < 0, sb + N, sb)
-            u = u.masked_fill((u < 0) | (u >= N), 0)  # (an id out of range has no entries)
-            raw = torch.empty((total,), dtype=torch.int64, device=device)
-            if total:
-                at = offsets[a * b:e * b] - base
-                with _Span('lsh_fill', device):
-                    _native.check(lib.ss_lsh_fill(_ptr(sb), e - a, N, *shape, _ptr(at), _ptr(raw), _stream(device)), 'ss_lsh_fill')
-            with _Span('lsh_unique', device):
-                keys, bands = torch.unique(raw, return_counts=True)
-                keep = bands >= min_bands
-                if csr is not None and keys.numel():
-                    gone = _csr_row_keys(csr, u, N)
-                    if gone is not None:
-                        keep &= gone[torch.searchsorted(gone, keys).clamp_(max=gone.numel() - 1)] != keys
-                if min_bands > 1 or csr is not None:
-                    keys, bands = keys[keep], bands[keep]
-            consume(c0 + a, u, keys, bands, err)
-            a = e
-    if strict and S and _take_error(device):
-        raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
+        return offsets[b::b].cpu().numpy(), offsets
 
+    def expand(offsets, a, e, base, total, sb, _u):
+        raw = torch.empty((total,), dtype=torch.int64, device=device)
+        if total:
+            _launch_fill(index, sb, offsets[a * b:e * b] - base, raw)
+        with _Span('lsh_unique', device):
+            keys, bands = torch.unique(raw, return_counts=True)
+            return keys, bands, (bands >= min_bands if min_bands > 1 else None)
 
-def _row_starts(keys, n, N):
-    """where each of a block's n sources starts in its sorted keys s * N + v: int64 [n + 1]"""
-    return torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int64, device=keys.device) * N)
-
-
-def _select_rows(keys, sc, n, N, k):
-    """the k best pairs of each of a block's n sources: keys = the block's sorted unique s * N + v, sc their float32 scores ->
-    (ids int64 [n, k], scores float32 [n, k]) by (score desc, id asc), tails -1 / -inf (topk_links_lsh and topk_links_wedge)"""
-    device = keys.device
-    s = keys // N
-    rank = _encode_topk_keys(sc, keys - s * N)
-    by_key = torch.argsort(rank, descending=True)                  # unique inside a source: (score desc, id asc)
-    order = by_key[torch.sort(s[by_key], stable=True).indices]     # ... grouped by source again
-    s_o = s[order]
-    place = torch.arange(keys.numel(), dtype=torch.int64, device=device) - _row_starts(keys, n, N)[s_o]
-    take = place < k
-    top = torch.full((n, k), TOPK_SENTINEL, dtype=torch.int64, device=device)
-    top[s_o[take], place[take]] = rank[order][take]
-    return _decode_topk_keys(top)
+    block = max(1, min(_LSH_BLOCK_BYTES // (12 * b), ((1 << 31) - 1) // b))
+    room = max(1, _LSH_BLOCK_BYTES // _LSH_ENTRY_BYTES)
+    return lambda consume: _block_walk(device, index.num_nodes, src, ex, eh._bounds, what, 'lsh_unique', block, room, count, expand, consume)
 
 
 def lsh_candidates(eh, sources, index, exclude, min_bands):
     src, ex, min_bands = _arguments(eh, sources, index, exclude, min_bands)
-    home, S, N = src.device, src.numel(), index.num_nodes
-    device = index.mh_u32.device
-    sizes = torch.zeros((S,), dtype=torch.int64, device=device)
-    ids, bands = [torch.empty((0,), dtype=torch.int64, device=device)], [torch.empty((0,), dtype=torch.int32, device=device)]
-
-    def consume(b0, u, keys, n_bands, _err):
-        sizes[b0:b0 + u.numel()] = torch.diff(_row_starts(keys, u.numel(), N))
-        ids.append(keys % N)
-        bands.append(n_bands.to(torch.int32))
-
-    _walk(eh, 'lsh_candidates', src, ex, index, min_bands, consume)
-    rowptr = torch.zeros((S + 1,), dtype=torch.int64, device=device)
-    torch.cumsum(sizes, 0, out=rowptr[1:])
-    return eh._send_home(home, rowptr, torch.cat(ids), torch.cat(bands))
+    return eh._send_home(src.device, *_rows(index.mh_u32.device, src.numel(), index.num_nodes, _walk(eh, 'lsh_candidates', src, ex, index, min_bands)))
 
 
 def topk_links_lsh(eh, sources, hash_table, cards, k, head, index, degrees, exclude, min_bands):
-    eh._check_head(head, degrees)
-    if cards is None:
-        raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
+    _check_scoring(eh, cards, head, degrees)
     src, ex, min_bands = _arguments(eh, sources, index, exclude, min_bands)
     _, _, N, P = eh._topk_arguments(src, hash_table, k, None)
     if (index.num_nodes, index.num_perm) != (N, P):
         raise ValueError(f'the index was built over a [{index.num_nodes}, {index.num_perm}] MinHash table, hash_table holds [{N}, {P}] ones')
-    k = int(k)
-    home, S = src.device, src.numel()
-    device = index.mh_u32.device
-    mh, hll, N, P = eh._resolve_tables(hash_table, device)
-    params = eh._params(device)
-    cd, dg, hd = eh._device_cards(cards, N, device), eh._device_degrees(degrees, N, device), head._device(device)
-    mh_ptrs, hll_ptrs = _table_ptrs(mh, hll)
-    ids = torch.empty((S, k), dtype=torch.int64, device=device)
-    scores = torch.empty((S, k), dtype=torch.float32, device=device)
-
-    def consume(b0, u, keys, _bands, err):
-        score = eh._pair_scores(device, N, P, mh_ptrs, hll_ptrs, cd, params, dg, hd, err)
-        n = u.numel()
-        s = keys // N
-        v = keys - s * N
-        sc = score(torch.stack([u[s], v], dim=1).contiguous(), torch.empty((keys.numel(),), dtype=torch.float32, device=device))
-        with _Span('lsh_select', device):
-            ids[b0:b0 + n], scores[b0:b0 + n] = _select_rows(keys, sc, n, N, k)
-
-    _walk(eh, 'topk_links_lsh', src, ex, index, min_bands, consume)
-    return eh._send_home(home, ids, scores)
+    walk = _walk(eh, 'topk_links_lsh', src, ex, index, min_bands)
+    return _topk_rows(eh, src, hash_table, cards, int(k), head, degrees, index.mh_u32.device, 'lsh_select', walk)

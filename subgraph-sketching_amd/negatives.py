@@ -33,6 +33,7 @@ import torch
 
 from . import _native
 from ._runtime import _DeferredErrors, _Span, _compute_device, _error_flag, _ptr, _stream, _take_error
+from .candidates import _int
 from .engine import _exclude_csr
 
 _LAUNCH_SLOTS = 1 << 30  # slots per launch when batch_size is not given (rows do not depend on it; not a user knob)
@@ -56,16 +57,6 @@ def _graph_arguments(num_nodes, edge_index, exclude):
     if N >= (1 << 31):
         raise ValueError(f'negative sampling needs num_nodes < 2^31 (node ids are int32 in the CSR), got {N}')
     return N, _edge_index(edge_index, 'edge_index', N), None if exclude is None else _edge_index(exclude, 'exclude', N)
-
-
-def _int(value, name, lo, hi=None):
-    try:
-        v = int(value)
-    except (TypeError, ValueError):
-        raise ValueError(f'{name} must be an integer, got {value!r}')
-    if v != value or v < lo or (hi is not None and v > hi):
-        raise ValueError(f'{name} must lie in [{lo}, {hi if hi is not None else "..."}], got {value!r}')
-    return v
 
 
 def _sorted_rows(ei, N, device):

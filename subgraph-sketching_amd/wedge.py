@@ -17,10 +17,10 @@ import numpy as np
 import torch
 
 from . import _native
-from ._runtime import _DeferredErrors, _Span, _compute_device, _ptr, _stream, _take_error
-from .engine import _csr_row_keys, _exclude_csr, _table_shape, _table_ptrs
-from .lsh import _row_starts, _select_rows
-from .negatives import _edge_index, _int, _sorted_rows
+from ._runtime import _DeferredErrors, _Span, _compute_device, _ptr, _stream
+from .candidates import _block_walk, _check_host_ids, _check_scoring, _id_list, _int, _rows, _topk_rows
+from .engine import _table_shape
+from .negatives import _edge_index, _sorted_rows
 
 # rows depend on none of these (not user knobs)
 _WEDGE_BLOCK_BYTES = 1 << 30  # bound on the arrays of one block of sources: 24 bytes per source of the walks launch, then the block's walks
@@ -33,14 +33,11 @@ _PAD = (1 << 63) - 1          # kWedgePad of csrc/ss_wedge.hpp
 def _arguments(N, sources, exclude, min_common, max_walks, lds_slots):
     """what .candidates and topk_links_wedge check of their own arguments before a device is touched:
     (sources, exclude or None, min_common, the largest W(u) that is listed, lds_slots)"""
-    src = torch.as_tensor(sources)
-    if src.dim() != 1 or src.dtype.is_floating_point or src.dtype == torch.bool:
-        raise ValueError(f'sources must be a 1-D integer tensor, got {src.dtype} {tuple(src.shape)}')
+    src = _id_list(sources)
     if src.numel() >= (1 << 31):
         raise ValueError(f'sources holds {src.numel()} ids: a call takes fewer than 2^31')
     ex = None if exclude is None else _edge_index(exclude, 'exclude', N)
-    if not src.is_cuda and src.numel() and (int(src.min()) < -N or int(src.max()) >= N):
-        raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
+    _check_host_ids(src, N)
     min_common = _int(min_common, 'min_common', 1)
     cap = _MAX_WALKS if max_walks is None else min(_int(max_walks, 'max_walks', 0), _MAX_WALKS)
     slots = _native.WEDGE_MAX_SLOTS if lds_slots is None else _int(lds_slots, '_lds_slots', 1, _native.WEDGE_MAX_SLOTS)
@@ -70,74 +67,55 @@ def _launch_emit(graph, sources, take, offsets, slots, slices, keys):
                       'ss_wedge_emit')
 
 
-def _walk(graph, src, ex, min_common, cap, slots, bounds, consume):
-    """the walk both queries share: blocks of sources bounded by _WEDGE_BLOCK_BYTES -- the walks launch over a block, ONE host read
-    (its W(u): the sizes, and which tier has work), then as many whole sources as fit the budget (one at least): both tiers write into
-    one (key, count) array of sum W(u) places, the padding of the LDS tier is dropped, a sort and a run-length sum fold what the large
-    tier left unfolded, then min_common and the exclude list, then consume(b0, u, keys, common, err): sources [b0, b0 + len(u)) with
-    wrapped ids u, the block's pairs as sorted unique keys s * N + v (s: the source's place in the block) and their walk counts.
-    The tier never shows: every source goes through the same sort.  -> (W(u) int64 [S] on the device, tier counts [lds, large])"""
+def _walk(graph, src, ex, min_common, cap, slots, bounds):
+    """candidates._block_walk over the walks of the graph, to be called with a consume: blocks of sources bounded by _WEDGE_BLOCK_BYTES, per
+    block the walks launch (its W(u): the sizes, and which tier has work); per group both tiers write into one (key, count) array of sum
+    W(u) places, the LDS tier's padding is dropped, a sort and a run-length sum fold what the large tier left unfolded; min_common and
+    v != u are the filter.  -> (the walk; W(u) int64 [S] on the device, which it fills; the tier counts [lds, large], which it adds to)"""
     device, N = graph.device, graph.num_nodes
-    S = src.numel()
-    lk = src.to(device=device, dtype=torch.int64).contiguous()
-    strict, err = bounds(device, f'wedge candidates({S} sources, num_nodes={N})')
-    csr, err = _exclude_csr(ex, N, device, strict, err)
-    walks = torch.zeros((S,), dtype=torch.int64, device=device)
+    walks = torch.zeros((src.numel(),), dtype=torch.int64, device=device)
     served = [0, 0]
-    room = max(1, _WEDGE_BLOCK_BYTES // _WEDGE_WALK_BYTES)
-    cblk = max(1, min(S, _WEDGE_BLOCK_BYTES // 24))
-    for c0 in range(0, S, cblk):
-        nc = min(cblk, S - c0)
-        _launch_walks(graph, lk[c0:c0 + nc], walks[c0:c0 + nc], err)
-        w = walks[c0:c0 + nc].cpu().numpy()
+
+    def count(c0, sources, err):
+        mine = walks[c0:c0 + sources.numel()]
+        _launch_walks(graph, sources, mine, err)
+        w = mine.cpu().numpy()
         w = np.where(w > cap, 0, w)  # (a skipped source lists nothing)
-        ends = np.cumsum(w)
-        a = 0
-        while a < nc:  # as many whole sources as fit the budget, one at least
-            base = int(ends[a - 1]) if a else 0
-            e = min(nc, max(a + 1, int(np.searchsorted(ends, base + room, side='right'))))
-            total = int(ends[e - 1]) - base
-            sb = lk[c0 + a:c0 + e]
-            u = torch.where(sb < 0, sb + N, sb)
-            u = u.masked_fill((u < 0) | (u >= N), 0)  # (an id out of range has no walks)
-            keys = torch.empty((total,), dtype=torch.int64, device=device)
-            common = torch.ones((total,), dtype=torch.int32, device=device)
-            if total:
-                wb = w[a:e]
-                folds, emits = (wb > 0) & (2 * wb <= slots), 2 * wb > slots
-                served[0] += int(folds.sum())
-                served[1] += int(emits.sum())
-                take = walks[c0 + a:c0 + e]
-                take = take.masked_fill(take > cap, 0)
-                offsets = torch.cumsum(take, 0) - take
+        return np.cumsum(w), (w, mine)
+
+    def expand(block, a, e, _base, total, sb, u):
+        keys = torch.empty((total,), dtype=torch.int64, device=device)
+        common = torch.ones((total,), dtype=torch.int32, device=device)
+        if total:
+            wb = block[0][a:e]
+            folds, emits = (wb > 0) & (2 * wb <= slots), 2 * wb > slots
+            served[0] += int(folds.sum())
+            served[1] += int(emits.sum())
+            take = block[1][a:e]
+            take = take.masked_fill(take > cap, 0)
+            offsets = torch.cumsum(take, 0) - take
+            if folds.any():
+                _launch_fold(graph, sb, take, offsets, slots, keys, common)
+            if emits.any():
+                slices = min(_native.WEDGE_MAX_SLICES, -(-int(wb[emits].max()) // _WEDGE_SLICE_WALKS))
+                _launch_emit(graph, sb, take, offsets, slots, slices, keys)
+            with _Span('wedge_unique', device):
                 if folds.any():
-                    _launch_fold(graph, sb, take, offsets, slots, keys, common)
+                    used = keys != _PAD
+                    keys, common = keys[used], common[used]
+                keys, order = torch.sort(keys)
+                common = common[order]
                 if emits.any():
-                    slices = min(_native.WEDGE_MAX_SLICES, -(-int(wb[emits].max()) // _WEDGE_SLICE_WALKS))
-                    _launch_emit(graph, sb, take, offsets, slots, slices, keys)
-                with _Span('wedge_unique', device):
-                    if folds.any():
-                        used = keys != _PAD
-                        keys, common = keys[used], common[used]
-                    keys, order = torch.sort(keys)
-                    common = common[order]
-                    if emits.any():
-                        keys, run = torch.unique_consecutive(keys, return_inverse=True)
-                        common = torch.zeros((keys.numel(),), dtype=torch.int32, device=device).index_add_(0, run, common)
-            with _Span('wedge_filter', device):
-                keep = common >= min_common
-                s = keys // N
-                keep &= keys - s * N != u[s]
-                if csr is not None and keys.numel():
-                    gone = _csr_row_keys(csr, u, N)
-                    if gone is not None:
-                        keep &= gone[torch.searchsorted(gone, keys).clamp_(max=gone.numel() - 1)] != keys
-                keys, common = keys[keep], common[keep]
-            consume(c0 + a, u, keys, common, err)
-            a = e
-    if strict and S and _take_error(device):
-        raise IndexError(f'sources refer to nodes outside [-{N}, {N})')
-    return walks, served
+                    keys, run = torch.unique_consecutive(keys, return_inverse=True)
+                    common = torch.zeros((keys.numel(),), dtype=torch.int32, device=device).index_add_(0, run, common)
+        with _Span('wedge_filter', device):
+            s = keys // N
+            return keys, common, (common >= min_common) & (keys - s * N != u[s])
+
+    block = max(1, _WEDGE_BLOCK_BYTES // 24)
+    room = max(1, _WEDGE_BLOCK_BYTES // _WEDGE_WALK_BYTES)
+    walk = lambda consume: _block_walk(device, N, src, ex, bounds, 'wedge candidates', 'wedge_filter', block, room, count, expand, consume)
+    return walk, walks, served
 
 
 class WedgeGraph(object):
@@ -198,19 +176,8 @@ class WedgeGraph(object):
                  each kernel tier served}.  No CPU fallback."""
         N, device = self.num_nodes, self.device
         src, ex, min_common, cap, slots = _arguments(N, sources, exclude, min_common, max_walks, _lds_slots)
-        home, S = src.device, src.numel()
-        sizes = torch.zeros((S,), dtype=torch.int64, device=device)
-        ids, common = [torch.empty((0,), dtype=torch.int64, device=device)], [torch.empty((0,), dtype=torch.int32, device=device)]
-
-        def consume(b0, u, keys, counts, _err):
-            sizes[b0:b0 + u.numel()] = torch.diff(_row_starts(keys, u.numel(), N))
-            ids.append(keys % N)
-            common.append(counts)
-
-        walks, served = _walk(self, src, ex, min_common, cap, slots, self._bounds, consume)
-        rowptr = torch.zeros((S + 1,), dtype=torch.int64, device=device)
-        torch.cumsum(sizes, 0, out=rowptr[1:])
-        out = [rowptr, torch.cat(ids), torch.cat(common), walks]
+        walk, walks, served = _walk(self, src, ex, min_common, cap, slots, self._bounds)
+        home, out = src.device, [*_rows(device, src.numel(), N, walk), walks]
         if home != device:
             out = [t.to(home) for t in out]
             if self.strict_bounds == 'deferred':  # a copy has waited for the launches: a deferred report is final behind it
@@ -223,9 +190,7 @@ class WedgeGraph(object):
 
 
 def topk_links_wedge(eh, sources, hash_table, cards, k, head, graph, degrees, exclude, min_common, max_walks, lds_slots=None):
-    eh._check_head(head, degrees)
-    if cards is None:
-        raise ValueError('cards must be given: the feature row needs the neighbourhood sizes build_hash_tables returns')
+    _check_scoring(eh, cards, head, degrees)
     if not isinstance(graph, WedgeGraph):
         raise ValueError(f'graph must be a WedgeGraph (WedgeGraph(num_nodes, edge_index)), got {type(graph).__name__}')
     N, P = _table_shape(hash_table, 1)
@@ -233,23 +198,5 @@ def topk_links_wedge(eh, sources, hash_table, cards, k, head, graph, degrees, ex
         raise ValueError(f'the graph has {graph.num_nodes} nodes, hash_table holds [{N}, {P}] MinHash tables')
     eh._topk_arguments(sources, hash_table, k, None)
     src, ex, min_common, cap, slots = _arguments(N, sources, exclude, min_common, max_walks, lds_slots)
-    k = int(k)
-    home, S = src.device, src.numel()
-    device = graph.device
-    mh, hll, N, P = eh._resolve_tables(hash_table, device)
-    params = eh._params(device)
-    cd, dg, hd = eh._device_cards(cards, N, device), eh._device_degrees(degrees, N, device), head._device(device)
-    mh_ptrs, hll_ptrs = _table_ptrs(mh, hll)
-    ids = torch.empty((S, k), dtype=torch.int64, device=device)
-    scores = torch.empty((S, k), dtype=torch.float32, device=device)
-
-    def consume(b0, u, keys, _common, err):
-        score = eh._pair_scores(device, N, P, mh_ptrs, hll_ptrs, cd, params, dg, hd, err)
-        n = u.numel()
-        s = keys // N
-        sc = score(torch.stack([u[s], keys - s * N], dim=1).contiguous(), torch.empty((keys.numel(),), dtype=torch.float32, device=device))
-        with _Span('wedge_select', device):
-            ids[b0:b0 + n], scores[b0:b0 + n] = _select_rows(keys, sc, n, N, k)
-
-    _walk(graph, src, ex, min_common, cap, slots, eh._bounds, consume)
-    return eh._send_home(home, ids, scores)
+    walk = _walk(graph, src, ex, min_common, cap, slots, eh._bounds)[0]
+    return _topk_rows(eh, src, hash_table, cards, int(k), head, degrees, graph.device, 'wedge_select', walk)

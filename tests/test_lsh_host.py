@@ -1,10 +1,13 @@
 """The LSH index (ElphHashes.build_lsh_index / lsh_candidates / topk_links_lsh) without a GPU: the numpy restatement of
 its semantics (lsh_restatement.py) against a naive double loop written here, on oracle tables; the argument checks that run before a
-device is touched; the ranking key's torch form; the new entry points in the header, the bindings and the library."""
+device is touched; the ranking key's torch form and the selection by it; the host block walk rehearsed with numpy stand-ins for the two
+launches; the new entry points in the header, the bindings and the library."""
 from argparse import Namespace
+import collections
 import ctypes
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -175,6 +178,142 @@ def test_the_ranking_key_in_torch_is_the_inverse_of_its_decoder():
     assert keys[0] == keys[1] and bool((keys > TOPK_SENTINEL).all())
     order = np.lexsort((ids.numpy(), -scores.numpy()))  # (score desc, id asc); the two zeros are one key
     assert torch.equal(torch.argsort(keys, descending=True, stable=True), torch.from_numpy(order))
+
+
+def test_the_selection_against_a_lexsort():
+    from subgraph_sketching_amd.candidates import _select_rows
+    N, n, k = 50, 5, 3
+    rows = [([7], [0.5]),                                                  # one candidate
+            ([3, 20, 49], [1.0, 2.0, -1.0]),                               # exactly k
+            ([1, 4, 9, 16, 25, 36], [2.0, 3.0, 2.0, 3.0, 2.0, 1.0]),       # more than k, tied scores: ids break ties ascending
+            ([0, 2, 5, 8, 11], [-0.0, -2.5, 0.0, -1e-30, -0.0]),           # -0.0 and +0.0 are one key (the id decides), negative scores
+            ([], [])]                                                      # none, and the last: trailing rows
+    keys = torch.tensor([s * N + v for s, (ids, _) in enumerate(rows) for v in ids], dtype=torch.int64)
+    sc = torch.tensor([x for _, scores in rows for x in scores], dtype=torch.float32)
+    assert bool((keys[1:] > keys[:-1]).all())
+    got_ids, got = _select_rows(keys, sc, n, N, k)
+    assert got_ids.dtype == torch.int64 and got.dtype == torch.float32 and got_ids.shape == got.shape == (n, k)
+    want_ids, want = np.full((n, k), -1, dtype=np.int64), np.full((n, k), -np.inf, dtype=np.float32)
+    for s, (ids, scores) in enumerate(rows):
+        ids, scores = np.array(ids, dtype=np.int64), np.array(scores, dtype=np.float32)
+        order = np.lexsort((ids, -scores))[:k]  # (score desc, id asc); numpy compares the two zeros equal
+        want_ids[s, :len(order)], want[s, :len(order)] = ids[order], scores[order]
+    np.testing.assert_array_equal(got_ids.numpy(), want_ids)
+    np.testing.assert_array_equal(got.numpy(), want)
+    assert want_ids[2].tolist() == [4, 16, 1] and want_ids[3].tolist() == [0, 5, 11] and want_ids[4].tolist() == [-1] * k
+
+
+# ---- the host walk, rehearsed: the two launches replaced by numpy stand-ins that read the restatement's band groups ------------------
+def _rehearse(monkeypatch, mh, rows, bands, max_bucket):
+    import subgraph_sketching_amd as ssa
+    lsh = ssa.lsh
+    N, P = mh.shape
+    groups = restated.band_groups(mh, rows, bands)
+    rng = np.random.RandomState(0)
+    launches = collections.Counter()
+
+    def partners(u, j):
+        """the other members of u's band-j bucket: none for a skipped bucket and for an id out of range"""
+        u = u + N if u < 0 else u
+        if not 0 <= u < N:
+            return np.zeros(0, dtype=np.int64)
+        group, sizes = groups[j]
+        if sizes[group[u]] > max_bucket:
+            return np.zeros(0, dtype=np.int64)
+        members = np.nonzero(group == group[u])[0]
+        return members[members != u]
+
+    def count(index, sources, counts, err):
+        launches['count'] += 1
+        assert counts.shape == (sources.numel() * bands,) and counts.dtype == torch.int32
+        counts.copy_(torch.tensor([len(partners(u, j)) for u in sources.tolist() for j in range(bands)], dtype=torch.int32))
+
+    def fill(index, sources, offsets, entries):
+        launches['fill'] += 1
+        assert offsets.shape == (sources.numel() * bands,)
+        for s, u in enumerate(sources.tolist()):
+            for j in range(bands):
+                v, o = rng.permutation(partners(u, j)), int(offsets[s * bands + j])  # (in no particular order)
+                entries[o:o + len(v)] = torch.from_numpy(s * N + v)
+
+    def exclude_csr(ex, n, device, strict, err):
+        if ex is None:
+            return None, err
+        ex = ex.numpy()
+        ex = np.where(ex < 0, ex + n, ex)
+        gone = [ex[1][ex[0] == u] for u in range(n)]
+        return SimpleNamespace(rowptr=torch.from_numpy(np.concatenate([[0], np.cumsum([len(r) for r in gone])]).astype(np.int64)),
+                               col=torch.from_numpy(np.concatenate(gone).astype(np.int32))), err
+
+    monkeypatch.setattr(lsh, '_launch_count', count)
+    monkeypatch.setattr(lsh, '_launch_fill', fill)
+    monkeypatch.setattr(ssa.candidates, '_exclude_csr', exclude_csr)  # (where the shared walk looks it up)
+    index = lsh.LshIndex(1, rows, bands, max_bucket, torch.from_numpy(mh.astype(np.uint32).view(np.int32)), torch.zeros((bands, N), dtype=torch.int64),
+                         torch.zeros((bands, N), dtype=torch.int32), torch.zeros((bands,), dtype=torch.int64))
+    eh = _eh(P=P)
+    eh.strict_bounds = False
+    return lsh, eh, index, launches
+
+
+def _walk_sources(N):
+    return np.array(list(range(0, N, N // 15)) + [N - 1, -1, -N, 0, 0, 5 - N], dtype=np.int64)  # about twenty: negative ids, duplicates
+
+
+def _planted_table():
+    """[60, 16] with values in {0, 1, 2}: with rows = 2 nine slices per band, so buckets of several nodes and pairs that meet in several bands"""
+    return np.random.RandomState(3).randint(0, 3, size=(60, 16)).astype(np.int64)
+
+
+# (trailing: rows = 1, so that with the trailing nodes' buckets skipped (max_bucket = 9) a ring node alone still lists more than the
+# small budget holds: up to 253 entries against 224; rows = 4 leaves them 4 at the most)
+@pytest.mark.parametrize('name,rows,bands,max_bucket', [('trailing', 1, 128, 9), ('trailing', 1, 128, 10), ('planted', 2, 8, 1024)])
+def test_the_host_walk_rehearsed_with_stand_ins(monkeypatch, regenerated_tables, name, rows, bands, max_bucket):
+    if name == 'trailing':
+        N, ei, m = restated.trailing_graph()
+        mh = _oracle_tables(regenerated_tables, N, ei, 128)[1]
+    else:
+        mh = _planted_table()
+        N = mh.shape[0]
+    lsh, eh, index, launches = _rehearse(monkeypatch, mh, rows, bands, max_bucket)
+    src = _walk_sources(N)
+    S = len(src)
+    shared = restated.shared_bands(mh, src, rows, bands, max_bucket).astype(np.int64)
+    shared[np.arange(S), np.where(src < 0, src + N, src)] = 0
+    entries = shared.sum(axis=1)  # what each source lists before the pairs are made unique
+    if name == 'planted':
+        assert (np.bincount(shared.reshape(-1)) > 0).sum() >= 4 and entries.min() > 0, 'pairs that meet in 1, 2, 3 ... bands'
+    else:
+        trailing = entries[np.where(src < 0, src + N, src) >= N - m]
+        assert (trailing == ((m - 1) * bands if max_bucket >= m else 0)).all() and len(trailing) >= 3  # ONE bucket per band: kept or skipped
+    pair = restated.lsh_candidates(mh, src, rows, bands, max_bucket)
+    exclude = np.stack([np.repeat(src, np.diff(pair[0]))[::2], pair[1][::2]])  # every other listed pair ...
+    exclude = np.concatenate([exclude, exclude[:, :3], np.array([[0, -1, 5], [0, 3, 5 - N]])], axis=1)  # ... a repeated pair, a self loop, a negative id
+    for kw in (dict(), dict(min_bands=2), dict(exclude=exclude)):
+        want = restated.lsh_candidates(mh, src, rows, bands, max_bucket, **kw)
+        assert want[1].size, 'a trivial case checks nothing'
+        tkw = {k: torch.from_numpy(v) if isinstance(v, np.ndarray) else v for k, v in kw.items()}
+        whole = eh.lsh_candidates(torch.from_numpy(src), index, **tkw)
+        _assert_same([t.numpy() for t in whole], want)
+        # a few hundred bytes: a block boundary falls inside the source list, and one source alone exceeds the entry budget
+        small = 12 * bands * 7
+        monkeypatch.setattr(lsh, '_LSH_BLOCK_BYTES', small)
+        assert S > 7 and entries.max() > small // lsh._LSH_ENTRY_BYTES
+        before = launches['count']
+        split = eh.lsh_candidates(torch.from_numpy(src), index, **tkw)
+        assert all(torch.equal(a, b) for a, b in zip(split, whole))
+        assert launches['count'] - before == -(-S // 7)
+        monkeypatch.setattr(lsh, '_LSH_BLOCK_BYTES', 1 << 30)
+    none = eh.lsh_candidates(torch.from_numpy(src[:0]), index)
+    assert none[0].tolist() == [0] and none[1].shape == (0,) and none[1].dtype == torch.int64 and none[2].dtype == torch.int32
+    # one source outside [-N, N) (a device caller's: CPU ids are refused by the argument check): its row is empty, the others are as before
+    from subgraph_sketching_amd.candidates import _rows
+    bad = np.concatenate([src[:4], [N + 3], src[4:]])
+    with pytest.raises(IndexError):
+        eh.lsh_candidates(torch.from_numpy(bad), index)
+    rowptr, ids, n_bands = _rows(torch.device('cpu'), S + 1, N, lsh._walk(eh, 'lsh_candidates', torch.from_numpy(bad), None, index, 1))
+    want = restated.lsh_candidates(mh, src, rows, bands, max_bucket)
+    np.testing.assert_array_equal(rowptr.numpy(), np.concatenate([want[0][:5], want[0][4:]]))
+    _assert_same((ids.numpy(), n_bands.numpy()), want[1:])
 
 
 def test_the_entry_points_are_declared_bound_and_exported():

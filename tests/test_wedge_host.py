@@ -287,8 +287,9 @@ def _rehearse(monkeypatch, N, ei):
         return SimpleNamespace(rowptr=torch.from_numpy(np.concatenate([[0], np.cumsum([len(r) for r in gone])]).astype(np.int64)),
                                col=torch.from_numpy(np.concatenate(gone).astype(np.int32))), err
 
-    for name, fn in (('_launch_walks', walks), ('_launch_fold', fold), ('_launch_emit', emit), ('_exclude_csr', exclude_csr)):
+    for name, fn in (('_launch_walks', walks), ('_launch_fold', fold), ('_launch_emit', emit)):
         monkeypatch.setattr(wedge, name, fn)
+    monkeypatch.setattr(ssa.candidates, '_exclude_csr', exclude_csr)  # (where the shared walk looks it up)
     return wedge, _host_graph(N, ei), launches
 
 
