@@ -52,6 +52,30 @@ def negatives_graph():
     return _graph()
 
 
+# the sources of directed_graph(), by what the wedge walk meets at each
+DIRECTED_SOURCES = {'mixed': 0, 'all_sinks': 5, 'rejected': 20, 'repeated': 30, 'no_out_arc': 40}
+
+
+@functools.lru_cache(maxsize=None)
+def _directed():
+    e = [(0, 1), (0, 2), (0, 3), (0, 4), (1, 10), (1, 11), (2, 11), (2, 12), (2, 0),   # 0: 1 and 2 lead on, 3 and 4 are sinks
+         (5, 6), (5, 7), (5, 8),                                                         # 5: every neighbour is a sink
+         (20, 21), (20, 22), (21, 20), (21, 22), (22, 20), (22, 21),                     # 20: two steps end in 20, 21 or 22 only
+         (30, 31), (30, 31), (30, 31), (30, 32), (31, 33), (31, 34), (32, 35),           # 30: the arc 30 -> 31 three times
+         (41, 40), (41, 42), (42, 40)]                                                   # 40: arcs in, none out
+    ei = np.array(e, dtype=np.int64).T
+    ei.setflags(write=False)
+    return 48, ei
+
+
+def directed_graph():
+    """(N, edge_index int64 [2, E], DIRECTED: no arc has its reverse unless listed): the sources DIRECTED_SOURCES -- one whose
+    neighbours are partly sinks (nodes without an out-arc), one whose neighbours are all sinks (every wedge attempt stops at its w:
+    every slot unsampled), one whose two-step endpoints are itself and its own out-neighbours only (every proposal rejected), one
+    with a repeated out-arc, one without an out-arc"""
+    return _directed()
+
+
 def rows_of(N, ei):
     """row u = the sorted list of every v with u -> v in ei, duplicates kept, negative ids wrapped"""
     rows = [[] for _ in range(N)]

@@ -1,9 +1,10 @@
 """Negative sampling on the GPU (csrc/ss_negatives.hip, negatives.py): NegativeSampler.sample / sample_negatives against
 the Python restatement of their semantics (negatives_restatement.py).  "Equal" means the whole int64 [n_slots, 2] tensor and the
 unsampled count, exactly.  The graph (400 nodes: a random part, a hub, a K5, a star, isolated nodes, a doubled edge) is the one
-test_negatives_host.py checks the restatement on.
+test_negatives_host.py checks the restatement on.  The wedge mode runs on a small DIRECTED graph as well (directed_graph: neighbours
+without an out-arc, which a symmetric graph does not have).
 
-Written, not yet run on an MI355X (the restatement's side of every case was rehearsed on the CPU)."""
+Run on an MI355X: profiles/wedge_planted_tests.txt."""
 from argparse import Namespace
 import functools
 
@@ -142,6 +143,39 @@ def test_max_tries_reaches_the_kernel(sampler, dev):
     expected = want('nodes', 3, 'wedge', 0, max_tries=1)
     assert expected[1] > want('nodes', 3, 'wedge', 0)[1]
     _equal(sampler.sample(pos, num_neg=3, mode='wedge', seed=0, max_tries=1, return_info=True), expected, dev)
+
+
+# ---- a directed graph: neighbours without an out-arc ---------------------------------------------------------------------------------
+DN, DEI = restated.directed_graph()
+DPOS = np.stack([np.arange(DN), np.arange(DN)[::-1]], axis=1).astype(np.int64)  # every node as a source: the planted ones among them
+
+
+@pytest.fixture(scope='module')
+def directed(ssa, dev):
+    return ssa.NegativeSampler(DN, torch.from_numpy(DEI.copy()).to(dev))
+
+
+@pytest.mark.parametrize('max_tries', [1, 4, 16])
+@pytest.mark.parametrize('num_neg', [1, 3, 7])
+def test_wedge_on_a_directed_graph(directed, dev, num_neg, max_tries):
+    """a neighbour w without an out-arc ends the attempt, not the slot: the source of sinks alone is unsampled in every slot"""
+    expected = restated.sample(DN, DEI, DPOS, num_neg=num_neg, mode='wedge', seed=2, max_tries=max_tries)
+    src = restated.DIRECTED_SOURCES
+    by_source = expected[0][:, 1].reshape(DN, num_neg)
+    assert (by_source[[src['all_sinks'], src['rejected'], src['no_out_arc']]] == -1).all() and (by_source[src['repeated']] >= 0).any()
+    assert max_tries == 1 or (by_source[src['mixed']] >= 0).any()
+    _equal(directed.sample(torch.from_numpy(DPOS).to(dev), num_neg=num_neg, mode='wedge', seed=2, max_tries=max_tries, return_info=True),
+           expected, dev)
+    if (num_neg, max_tries) == (7, 4):  # launches that start inside a positive
+        _equal(directed.sample(torch.from_numpy(DPOS).to(dev), num_neg=7, mode='wedge', seed=2, max_tries=4, batch_size=5, return_info=True),
+               expected, dev)
+
+
+@pytest.mark.parametrize('mode', ['uniform', 'same_source'])
+def test_the_other_modes_on_a_directed_graph(directed, dev, mode):
+    expected = restated.sample(DN, DEI, DPOS, num_neg=3, mode=mode, seed=2)
+    assert (expected[0][:, 1] >= 0).all()
+    _equal(directed.sample(torch.from_numpy(DPOS).to(dev), num_neg=3, mode=mode, seed=2, return_info=True), expected, dev)
 
 
 def test_ids_out_of_range(ssa, dev):

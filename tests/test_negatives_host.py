@@ -36,23 +36,34 @@ def test_known_answers_of_the_draw():
     assert restated.pick((1 << 64) - 1, 400) == 399 and restated.pick(0, 400) == 0 and restated.pick(1 << 63, 401) == 200
 
 
-def _candidates(u, mode, gone=frozenset()):
-    """every v a slot of source u may return, from sets alone"""
-    reach = {v for w in OUT[u] for v in OUT[w]} if mode == 'wedge' else set(range(N))
-    return {v for v in reach if v != u and (u, v) not in EDGES and (u, v) not in gone}
+def _sets(n, ei):
+    """(N, the set of arcs, {u: {v : u -> v}}) of a graph"""
+    edges = set(zip(*np.asarray(ei).tolist()))
+    out = collections.defaultdict(set)
+    for u, v in edges:
+        out[u].add(v)
+    return n, edges, out
 
 
-def _check(out, unsampled, mode, positives, num_neg, gone=frozenset()):
+def _candidates(u, mode, gone=frozenset(), graph=None):
+    """every v a slot of source u may return, from sets alone (graph: _sets of another graph than the module's)"""
+    n, edges, out = graph or (N, EDGES, OUT)
+    reach = {v for w in out[u] for v in out[w]} if mode == 'wedge' else set(range(n))
+    return {v for v in reach if v != u and (u, v) not in edges and (u, v) not in gone}
+
+
+def _check(out, unsampled, mode, positives, num_neg, gone=frozenset(), graph=None):
+    n, edges, arcs = graph or (N, EDGES, OUT)
     assert out.dtype == np.int64 and out.shape == (len(positives) * num_neg, 2)
     assert unsampled == int((out[:, 1] < 0).sum())
     for q, (u, v) in enumerate(out.tolist()):
-        assert u == int(positives[q // num_neg][0]) % N
-        if not _candidates(u, mode, gone):
+        assert u == int(positives[q // num_neg][0]) % n
+        if not _candidates(u, mode, gone, graph):
             assert v == -1, f'source {u} has no candidate in mode {mode}'
         if v >= 0:
-            assert v != u and (u, v) not in EDGES and (u, v) not in gone
+            assert v != u and (u, v) not in edges and (u, v) not in gone
             if mode == 'wedge':
-                assert OUT[u] & {w for w in range(N) if v in OUT[w]}, f'no w with {u} -> w -> {v}'
+                assert arcs[u] & {w for w in range(n) if v in arcs[w]}, f'no w with {u} -> w -> {v}'
 
 
 @pytest.mark.parametrize('mode', restated.MODES)
@@ -79,6 +90,49 @@ def test_restatement_with_an_exclude_list(mode):
     free, _ = restated.sample(N, EI, positives, num_neg=5, mode=mode, seed=3)
     if mode == 'wedge':  # 388 -> 398 -> 389 is a wedge: without the list it comes back, with it never
         assert (388, 389) in set(map(tuple, free.tolist())) and (388, 389) not in set(map(tuple, out.tolist()))
+
+
+@pytest.mark.parametrize('mode', restated.MODES)
+@pytest.mark.parametrize('num_neg,max_tries', [(1, 1), (3, 4), (7, 16)])
+def test_restatement_on_the_directed_graph(mode, num_neg, max_tries):
+    n, ei = restated.directed_graph()
+    graph = _sets(n, ei)
+    assert not {(1, 0), (10, 1), (6, 5), (31, 30), (40, 41)} & graph[1], 'a directed graph'
+    positives = np.stack([np.arange(n), np.arange(n)[::-1]], axis=1).astype(np.int64)
+    out, unsampled = restated.sample(n, ei, positives, num_neg=num_neg, mode=mode, seed=2, max_tries=max_tries)
+    _check(out, unsampled, mode, positives, num_neg, graph=graph)
+    src = restated.DIRECTED_SOURCES
+    if mode == 'wedge':
+        for name in ('all_sinks', 'rejected', 'no_out_arc'):
+            assert not _candidates(src[name], 'wedge', graph=graph)
+        assert _candidates(src['mixed'], 'wedge', graph=graph) == {10, 11, 12}  # (not 0 itself, reached through 2)
+        assert _candidates(src['repeated'], 'wedge', graph=graph) == {33, 34, 35}
+
+
+def test_the_directed_plan_is_not_trivial():
+    """the all-sinks source is unsampled in every slot (each attempt stops at a w without an out-arc), the mixed source is sampled in
+    some slot and stopped at a sink in some attempt, and the repeated arc 30 -> 31 is picked three times out of four"""
+    n, ei = restated.directed_graph()
+    rows = restated.rows_of(n, ei)
+    src = restated.DIRECTED_SOURCES
+    assert all(not rows[w] for w in rows[src['all_sinks']]) and len(rows[src['all_sinks']]) == 3
+    assert [bool(rows[w]) for w in rows[src['mixed']]] == [True, True, False, False]
+    assert rows[src['repeated']] == [31, 31, 31, 32] and not rows[src['no_out_arc']]
+    for num_neg, max_tries in ((1, 1), (3, 4), (7, 16)):
+        positives = np.array([[src['all_sinks'], 0], [src['mixed'], 0], [src['repeated'], 0]], dtype=np.int64)
+        out, unsampled = restated.sample(n, ei, positives, num_neg=num_neg, mode='wedge', seed=0, max_tries=max_tries)
+        by = out[:, 1].reshape(3, num_neg)
+        assert (by[0] == -1).all() and (out[:num_neg, 0] == src['all_sinks']).all()
+        assert unsampled >= num_neg
+        if max_tries > 1:
+            assert (by[1] >= 0).any() and (by[2] >= 0).all()
+    # at one try per slot, a slot of the mixed source whose w is a sink stays unsampled: the `continue` is taken, not only passed by
+    first_w = [rows[0][restated.pick(restated.draw(0, q, 0, 0), 4)] for q in range(64)]
+    out, _ = restated.sample(n, ei, np.array([[0, 0]]), num_neg=64, mode='wedge', seed=0, max_tries=1)
+    assert {3, 4} & set(first_w) and {1, 2} & set(first_w)
+    assert all(v == -1 for w, v in zip(first_w, out[:, 1].tolist()) if w in (3, 4))
+    many, _ = restated.sample(n, ei, np.array([[30, 0]]), num_neg=400, mode='wedge', seed=1, max_tries=1)
+    assert 250 < int(np.isin(many[:, 1], [33, 34]).sum()) < 350  # 3 / 4 of 400, within 5 sigma (43)
 
 
 def test_any_source_uniform():

@@ -6,7 +6,7 @@ brute-force composition (score_links over the restated candidate pairs, sorted),
 Left out: the agreement with topk_links under a head that scores 0 outside the common-neighbour set.  The head reads sketch ESTIMATES
 of the intersections, which are not zero exactly where the exact count is, so no such head is easy to construct.
 
-Written, not yet run on an MI355X (the host walk was rehearsed on the CPU with numpy stand-ins for the three launches)."""
+Run on an MI355X: profiles/wedge_planted_tests.txt."""
 from argparse import Namespace
 
 import numpy as np

@@ -44,6 +44,16 @@ int main()
         for (const int n : hits) used += n > 0;
         CHECK(used > (1 << k) / 2);  // (32 768 probes: the multiply spreads them)
     }
+    // known answers of the slot hash: the literal table KNOWN_SLOTS of tests/wedge_planted.py, whose Python twin finds the ids that the
+    // planted collision graphs are made of -- change the hash and both fail
+    // (tests/test_wedge_planted_host.py reads this table out of this file: keep `known[] = {`, the {v, k, slot} triples and the loop below)
+    static const struct { int32_t v; int k, slot; } known[] = {
+        {0, 1, 0}, {1, 1, 1}, {2, 1, 0}, {3, 1, 1}, {69999, 1, 1}, {2147483646, 1, 0}, {2147483647, 1, 1},
+        {1, 6, 39}, {2, 6, 15}, {3, 6, 54}, {255, 6, 38}, {65536, 6, 30}, {123456789, 6, 31}, {2147483647, 6, 56},
+        {1, 8, 158}, {5, 8, 23}, {256, 8, 55}, {4095, 8, 217}, {69999, 8, 194}, {1073741823, 8, 161}, {2147483647, 8, 225},
+        {1, 12, 2531}, {2, 12, 966}, {3, 12, 3498}, {4096, 12, 1913}, {65535, 12, 3511}, {1000003, 12, 3444},
+        {1073741824, 12, 1024}, {2147483646, 12, 1081}, {2147483647, 12, 3612}};
+    for (const auto &a : known) CHECK(wedge_slot(a.v, a.k) == a.slot);
     // the entry points: all rejected (-1), or nothing to do (0), before any launch
     std::vector<int64_t> some(8, 0);
     std::vector<int32_t> col(8, 0);
