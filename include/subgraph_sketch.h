@@ -326,6 +326,32 @@ int ss_common_neighbour_scores(const int64_t *rowptr, const int32_t *col, const 
 int ss_common_neighbour_scores_f32(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
                                    int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream);
 
+/* The common neighbours themselves, and node features pooled over them (csrc/ss_cn_pool.hip).  The common neighbours of
+ * (u, v) = links[q] are the columns STORED in both row u and row v of the CSR above (a stored zero counts), ascending;
+ * member w carries the coefficient
+ *     c(q, w) = (float)( A[u, w] * (A[v, w] * mult[w]) )      fp64 with this association (the term of
+ *   ss_common_neighbour_scores), rounded once -- for every matrix dtype; there is no float32 mode here.
+ *   rowptr / col / val / mult / links / err_flag: as ss_common_neighbour_scores (val NULL = all 1, mult NULL = 1).  A link
+ *   with an id outside [0, N) has no common neighbours (count 0, nothing filled, a pooled row of +0.0) and sets *err_flag.
+ *     ss_common_neighbour_count  counts[q] = the number of common neighbours of link q (device int64[B])
+ *     ss_common_neighbour_fill   ids[offsets[q] + k] = the k-th common neighbour of link q, coef[offsets[q] + k] = its
+ *                                coefficient (coef NULL: ids only).  offsets: device int64[B], the exclusive prefix sum of the
+ *                                counts of THESE links; ids device int64[T], coef device fp32[T], T = the sum of the counts.
+ *                                Exactly [offsets[q], offsets[q] + counts[q]) is written for every q.
+ *     ss_common_neighbour_pool   out[q, :] = sum over the common neighbours w of link q, ascending, of c(q, w) * x[w, :]:
+ *                                fp32 from +0.0, product and sum rounded separately, each element accumulated by one lane in
+ *                                that order -- a row's bits do not depend on B, the launch, or which of the two rows is longer.
+ *                                x: device fp32 [N, F] row-major, out: device fp32 [B, F] (every row written; 64-bit offsets),
+ *                                F >= 0; float4 accesses when F % 4 == 0 and x and out are 16-byte aligned, scalar ones
+ *                                otherwise.  No float atomics, no workspace. */
+int ss_common_neighbour_count(const int64_t *rowptr, const int32_t *col, int64_t N, const int64_t *links, int64_t B, int64_t *counts,
+                              int32_t *err_flag, void *stream);
+int ss_common_neighbour_fill(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult, int64_t N,
+                             const int64_t *links, int64_t B, const int64_t *offsets, int64_t *ids, float *coef, int32_t *err_flag,
+                             void *stream);
+int ss_common_neighbour_pool(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult, int64_t N,
+                             const int64_t *links, int64_t B, const float *x, int32_t F, float *out, int32_t *err_flag, void *stream);
+
 /* Personalised PageRank of many sources at once -- the fourth link heuristic (reference heuristics.py:74-113: PPR, one
  * fast_pagerank.pagerank_power(A, p, personalize=e_src, tol) power iteration per distinct source).  With r = row sums of A,
  * n = N, s_j = n e_src_j and z_u = ((1-p)[r_u != 0] + [r_u == 0]) / n, every source column j iterates

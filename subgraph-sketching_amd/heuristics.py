@@ -9,6 +9,10 @@ and float64 matrices (ss_common_neighbour_scores: CN of integer weights is exact
 products and numpy's float32 pairwise summation order for float32 matrices (ss_common_neighbour_scores_f32: bit-identical).
 No CPU fallback: the kernels need a HIP device.
 
+`common_neighbours(A, edge_index, weighting)` lists the nodes those sums run over, with their coefficients, and
+`common_neighbour_features(A, edge_index, x, weighting)` pools the node features x over them, one [F] row per link
+(ss_common_neighbour_count / _fill / _pool: csrc/ss_cn_pool.hip).
+
 `PPR(A, edge_index)` keeps the reference's own return convention, which differs from the other three: the scores come in the
 order of `torch.sort(edge_index[:, 0])` and the second value is that sorted link list as a [2, L] tensor.  The personalised
 PageRank vectors of all distinct sources are computed in batches of S columns (ss_ppr_*: csrc/ss_ppr.hip);
@@ -219,6 +223,129 @@ def RA(A, edge_index, batch_size=100000):
     scores, edge_index = _scores('RA', A, edge_index, batch_size)
     logger.info(f'evaluated Resource Allocation for {len(scores)} edges')
     return scores, edge_index
+
+
+CommonNeighbours = collections.namedtuple('CommonNeighbours', 'rowptr ids coef')
+
+
+def _num_nodes(A):
+    return A.num_nodes if isinstance(A, DeviceAdjacency) else A.shape[0]
+
+
+def _check_links(edge_index):
+    links = torch.as_tensor(edge_index)
+    if links.dim() != 2 or links.size(1) != 2 or links.dtype.is_floating_point or links.dtype.is_complex or links.dtype == torch.bool:
+        raise ValueError('edge_index must be an int tensor of links with shape [num_links, 2]')
+    return links
+
+
+def _check_weighting(A, weighting, allow_none):
+    """host-side checks of `weighting`: 'CN' | 'AA' | 'RA', a 1-D float tensor / array of length N, or (lists only) None"""
+    if weighting is None:
+        if not allow_none:
+            raise ValueError("weighting=None is for common_neighbours only: pass 'CN' for unweighted pooling")
+        return None
+    if isinstance(weighting, str):
+        if weighting not in ('CN', 'AA', 'RA'):
+            raise ValueError(f"weighting must be 'CN', 'AA', 'RA' or a multiplier of length N, got {weighting!r}")
+        return weighting
+    w = torch.as_tensor(weighting)
+    if w.dim() != 1 or not w.dtype.is_floating_point or w.numel() != _num_nodes(A):
+        raise ValueError(f'a custom multiplier must be a 1-D float tensor or array of length N = {_num_nodes(A)}, '
+                         f'got {w.dtype} {tuple(w.shape)}')
+    return w
+
+
+def _multiplier(adj, weighting):
+    """(mult, with_coef): the device fp64 multiplier (None = 1) of a checked `weighting`"""
+    if weighting is None:
+        return None, False
+    if isinstance(weighting, str):
+        return adj.multiplier(weighting), True
+    return weighting.detach().to(device=adj.device, dtype=torch.float64).contiguous(), True
+
+
+def common_neighbours(A, edge_index, weighting=None):
+    """The common neighbours of every link as a list: CommonNeighbours(rowptr int64 [L + 1], ids int64 [T], coef float32 [T] or None);
+    link q's are ids[rowptr[q]:rowptr[q + 1]], ascending.  They are the columns STORED in both row u and row v of the canonical CSR of
+    A (sorted, duplicate-free rows -- what CN / AA / RA sum over; an explicitly stored zero counts, and u or v itself is one when A
+    says so).  coef[k] = float32(A[u, w] * (A[v, w] * mult[w])), evaluated in fp64 with this association and rounded once, for every
+    matrix dtype (the scipy-float32 emulation of the scores is not repeated here).  `weighting`: None (no coef), 'CN' (mult = 1),
+    'AA' / 'RA' (the multiplier of the scores), or a 1-D float tensor / array of length N (the caller's own, used as fp64).
+    A, edge_index as CN takes them; CPU links in, CPU tensors out.  A count pass, a cumsum, one host read of T, a fill pass
+    (ss_common_neighbour_count / _fill: csrc/ss_cn_pool.hip).  A link id outside [0, N) raises IndexError after the launches."""
+    links = _check_links(edge_index)
+    weighting = _check_weighting(A, weighting, allow_none=True)
+    home = links.device
+    device = _compute_device(links)
+    adj = _adjacency(A, device)
+    mult, with_coef = _multiplier(adj, weighting)
+    lk = links.to(device=device, dtype=torch.int64).contiguous()
+    L = lk.size(0)
+    rowptr = torch.zeros(L + 1, dtype=torch.int64, device=device)
+    lib, err, stream = _native.lib(), _error_flag(device), _stream(device)
+    T = 0
+    if L:
+        counts = torch.empty(L, dtype=torch.int64, device=device)
+        _native.check(lib.ss_common_neighbour_count(_ptr(adj.rowptr), _ptr(adj.col), adj.num_nodes, _ptr(lk), L, _ptr(counts), _ptr(err),
+                                                    stream), 'ss_common_neighbour_count')
+        torch.cumsum(counts, 0, out=rowptr[1:])
+        T = int(rowptr[-1].item())
+    ids = torch.empty(max(T, 1), dtype=torch.int64, device=device)  # (never an empty device buffer behind the C ABI)
+    coef = torch.empty(max(T, 1), dtype=torch.float32, device=device) if with_coef else None
+    if T:
+        _native.check(lib.ss_common_neighbour_fill(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes, _ptr(lk), L,
+                                                   _ptr(rowptr), _ptr(ids), _ptr(coef), _ptr(err), stream), 'ss_common_neighbour_fill')
+    if _take_error(device):
+        raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
+    return CommonNeighbours(rowptr.to(home), ids[:T].to(home), coef[:T].to(home) if with_coef else None)
+
+
+def common_neighbour_features(A, edge_index, x, weighting='CN', batch_size=100000, out=None):
+    """Node features pooled over every link's common neighbours: float32 [L, F] with
+        out[q, :] = sum over the common neighbours w of link q, ASCENDING w, of c(q, w) * x[w, :]
+    where the common neighbours and c(q, w) = float32(A[u, w] * (A[v, w] * mult[w])) are those of `common_neighbours` -- the device
+    form of (A[src].multiply(A_[dst])) @ x without the [L, N] matrix, a BUDDY-style precompute for a fixed x (raw or SIGN features)
+    stored beside subgraph_features and RA.  The sum is float32 from +0.0, product and sum rounded separately, each element
+    accumulated by one lane in that order: a row has ONE value whatever batch_size, the order or repetition of the links, or which of
+    the two rows is longer; a link without common neighbours gets +0.0.
+    x: float32 [N, F] on the CPU or the device (anything else is a ValueError -- no silent cast; a non-contiguous x is made
+    contiguous); any F >= 0.  weighting: 'CN', 'AA', 'RA' or a 1-D float multiplier of length N.  out: optional contiguous float32
+    [L, F] on the compute device, filled and returned.  batch_size: links per launch.  Otherwise the result is on the links' device.
+    Inference and precompute only: there is NO gradient with respect to x (it would be a float scatter-add), and NaN or Inf in x is
+    outside the contract (0 * Inf of a stored zero is NaN).  A link id outside [0, N) gives a row of zeros and an IndexError after
+    the launches (ss_common_neighbour_pool: csrc/ss_cn_pool.hip)."""
+    links = _check_links(edge_index)
+    weighting = _check_weighting(A, weighting, allow_none=False)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError('x must be a float32 tensor of shape [N, F]')
+    N, F, L = _num_nodes(A), x.size(1), links.size(0)
+    if x.size(0) != N:
+        raise ValueError(f'x has {x.size(0)} rows, the adjacency matrix has N = {N}')
+    if F >= 1 << 31:
+        raise ValueError('F must be below 2^31')
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (L, F)
+                            or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous float32 tensor of shape [{L}, {F}]')
+    home = links.device
+    device = _compute_device(links, x)
+    if out is not None and out.device != device:
+        raise ValueError(f'out must be on the compute device {device}, it is on {out.device}')
+    adj = _adjacency(A, device)
+    mult, _ = _multiplier(adj, weighting)
+    lk = links.to(device=device, dtype=torch.int64).contiguous()
+    xd = x.detach().to(device).contiguous()
+    res = out if out is not None else torch.empty((L, F), dtype=torch.float32, device=device)
+    lib, err, stream = _native.lib(), _error_flag(device), _stream(device)
+    step = max(int(batch_size), 1)
+    for lo in range(0, L, step):
+        hi = min(lo + step, L)
+        _native.check(lib.ss_common_neighbour_pool(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes,
+                                                   _ptr(lk[lo:hi]), hi - lo, _ptr(xd), F, _ptr(res[lo:hi]), _ptr(err), stream),
+                      'ss_common_neighbour_pool')
+    if _take_error(device):
+        raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
+    return res if out is not None else res.to(home)
 
 
 PprPlan = collections.namedtuple('PprPlan', 'edge_reindex sources link_col batches')

@@ -191,6 +191,22 @@ def wedge_bytes(sources, neighbours, walks, candidates):
     return sources * (8 + 16 + 8) + 2 * neighbours * (4 + 16) + 4 * walks + 12 * candidates
 
 
+def cn_features_bytes(links, row_entries, hits, F, weighted=False):
+    """algorithmic bytes per launch of the three kernels of heuristics.common_neighbours / common_neighbour_features
+    (csrc/ss_cn_pool.hip) over `links` links whose two CSR rows hold `row_entries` entries in all and which share
+    `hits` = T common neighbours.  Every launch reads the links (16 each) and the two rows per link: four row pointer words (32) and 4
+    bytes per stored column (the binary search probes the longer row instead of streaming it: an upper bound there).  `weighted`
+    (a matrix with values, a multiplier): the fp64 values of both rows (8 per entry) and one fp64 multiplier per hit.
+      'count'  + one int64 count per link
+      'fill'   + one int64 offset per link, 8 + 4 bytes written per hit (id + coefficient)
+      'pool'   + hits * 4F gathered from x and links * 4F written -- the term that decides the launch at F = 128"""
+    rows = 16 * links + 32 * links + 4 * row_entries
+    values = (8 * row_entries + 8 * hits) if weighted else 0
+    return {'count': rows + 8 * links,
+            'fill': rows + values + 8 * links + 12 * hits,
+            'pool': rows + values + hits * 4 * F + links * 4 * F}
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
