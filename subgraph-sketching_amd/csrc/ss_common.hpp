@@ -419,6 +419,21 @@ inline const int32_t *self_skip_word(const ss_csr_graph &g, bool promised)
 // (wave-uniform: *GraphArgs.skip_self) says the graph is symmetric and the row has an in-edge whose row covers it already
 __device__ __forceinline__ int table_hop_total(int deg, bool self, bool skip) { return deg + ((self && !(skip && deg > 0)) ? 1 : 0); }
 
+// A table addressed through a raw buffer descriptor (base, stride 0, `bytes` records of one byte): a load takes a 32-bit byte offset per
+// lane instead of a 64-bit address, and a lane whose offset lies beyond the records gets zeros from the range check instead of a branch
+// around the load.  Build it from wave-uniform values only (kernel arguments), or every load is wrapped in a readfirstlane loop.
+// The descriptor counts its bytes in 32 bits: larger tables keep flat addresses (buffer_describable, asked on the host).  `past`: how
+// far beyond the table the kernel's out-of-range offsets reach; offset + access size must not wrap around 2^32 either.
+inline bool buffer_describable(int64_t bytes, int64_t past) { return bytes >= 0 && bytes + past < ((int64_t)1 << 32); }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const void *base, uint32_t bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ u32x4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_offset)
+{
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_offset, 0, 0));
+}
+
 inline GraphArgs to_args(const ss_csr_graph &g)
 {
     const bool all = g.row_end == 0 && g.row_begin == 0;

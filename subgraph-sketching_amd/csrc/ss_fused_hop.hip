@@ -21,11 +21,15 @@
 // 60 col entries of a batch almost always cover the whole chunk: a batch reload in the middle of the walk would have to wait for
 // its ids with vmcnt(0) -- vmcnt retires in order -- and so for every HLL row posted before it).  HLL side: one 16-lane DPP row
 // per destination (lane c = 16-byte chunk c of the 256-byte row); the first kHllInFlight = 7 neighbour chunks per lane are
-// requested into registers up front and the next kHllLds = 7 into LDS (global_load_lds_dwordx4; ids by one coalesced load per
+// requested into registers up front and the next kHllLds = 7 into LDS (LDS-DMA loads; both through a buffer descriptor of the table where
+// it fits one, HllSource below; ids by one coalesced load per
 // lane group, handed out by DPP row_newbcast), the rest of rows longer than 14 after the MinHash walk (hll_row16_finish).  Hub rows are skipped by both sides:
 // they are hub units (ss_hub.hpp) hosted by the launches before and after this one -- not by this one: the kernel sits exactly at its
 // 96-VGPR budget, and a hub branch, whatever it contained, cost the row path 64 bytes of scratch and 30 us (round 4).
 // P = 64 * PPL, M = 256 (p = 8) only -- the shapes ss_first_hop has a kernel for.
+#include <cstring>
+#include <type_traits>
+
 #include "ss_hub.hpp"
 
 namespace ss {
@@ -41,36 +45,75 @@ struct HllPosted {  // one lane group's view of its row while the row's first ch
     u32x4 x[kHllInFlight];
 };
 
-// requests chunk c of the first min(total, kHllInFlight) neighbour rows (the implicit self loop is neighbour `deg`)
-template <int T0>
-__device__ __forceinline__ void hll_post(HllPosted &h, const uint8_t *__restrict__ hll_in, int my_nb, int c)
+// How the posts address the hop-1 HLL table.  The ids a lane group hands out by DPP (Ids::my_nb, load_ids below) already say what to
+// fetch: lane t < total of the group holds the id of the row's neighbour t -- its own row for the implicit self loop -- and every
+// other lane the id N, the row after the table's last.
+// BUF: through a raw buffer descriptor over the table's N * 256 bytes (table_rsrc, ss_common.hpp).  A post is the DPP broadcast, one
+// shift-or for the 32-bit offset and a buffer_load_dwordx4; the row N lies beyond the records and the range check answers it with
+// zeros: no compare, no select, no zeroed landing, no exec-mask frame around the load, no 64-bit id or address.
+// !BUF: flat 64-bit addresses under a branch on t < total, for tables the descriptor cannot hold (buffer_describable, asked by ss_fused_hop_stage).
+struct HllSource {
+    const uint8_t *base;
+    __amdgpu_buffer_rsrc_t rsrc;
+};
+
+template <bool BUF>
+__device__ __forceinline__ HllSource hll_source(const uint8_t *__restrict__ hll_in, int64_t N)
+{
+    HllSource s;
+    s.base = hll_in;
+    if constexpr (BUF) s.rsrc = table_rsrc(hll_in, (uint32_t)(N * 256));  // (the host has checked that it fits)
+    return s;
+}
+
+// lane T of the caller's 16-lane row, by DPP row_newbcast.  (No old value: every lane is written, and a zero handed in as one costs a
+// v_mov per broadcast)
+template <int T>
+__device__ __forceinline__ int row_bcast(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, 0x150 + T, 0xF, 0xF, true);
+}
+
+// requests chunk c (c16 = 16 * c) of the first min(total, kHllInFlight) neighbour rows
+template <bool BUF, int T0>
+__device__ __forceinline__ void hll_post(HllPosted &h, const HllSource &src, int my_nb, uint32_t c16)
 {
     if constexpr (T0 < kHllInFlight) {
-        const int nbt = __builtin_amdgcn_update_dpp(0, my_nb, 0x150 + T0, 0xF, 0xF, false);  // row_newbcast: lane T0 of the 16-lane row
-        const int64_t j = T0 < h.deg ? (int64_t)nbt : h.i;
-        h.x[T0] = u32x4{0u, 0u, 0u, 0u};
-        if (T0 < h.total) h.x[T0] = *reinterpret_cast<const u32x4 *>(hll_in + j * 256 + 16 * c);
-        hll_post<T0 + 1>(h, hll_in, my_nb, c);
+        const int nbt = row_bcast<T0>(my_nb);
+        if constexpr (BUF) {
+            h.x[T0] = buffer_load16(src.rsrc, ((uint32_t)nbt << 8) | c16);  // (node ids are < 2^31, and < 2^24 for a describable table)
+        } else {
+            h.x[T0] = u32x4{0u, 0u, 0u, 0u};
+            if (T0 < h.total) h.x[T0] = *reinterpret_cast<const u32x4 *>(src.base + (int64_t)nbt * 256 + c16);
+        }
+        hll_post<BUF, T0 + 1>(h, src, my_nb, c16);
     }
 }
 
 // neighbour rows kHllInFlight .. kHllInFlight + kHllLds - 1 of every lane group travel into LDS instead of registers
-// (global_load_lds_dwordx4: no VGPR destination; one instruction = one neighbour of each of the wavefront's four rows, landing as
-// 64 lanes x 16 B = 1 KiB at the wave-uniform LDS address): rows of up to 16 neighbours need no load after the MinHash walk
+// (global_load_lds_dwordx4 / buffer_load_dwordx4 ... lds: no VGPR destination; one instruction = one neighbour of each of the
+// wavefront's four rows, landing as 64 lanes x 16 B = 1 KiB at the wave-uniform LDS address): rows of up to 16 neighbours need no load
+// after the MinHash walk.  A slot that none of the wavefront's four rows reaches is not posted (one compare and a scalar branch), nor
+// any slot after it; the fold leaves the same slots out.  What an out-of-range lane of the buffer form leaves in its 16 bytes of the
+// slot is not relied on: the fold masks the slots beyond a row's total in both forms.
 constexpr int kHllLds = 7;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(1))) const uint32_t global_u32;
+typedef __attribute__((address_space(1))) const int64_t global_i64;
 
-template <int T>
-__device__ __forceinline__ void hll_post_lds(const HllPosted &h, const uint8_t *__restrict__ hll_in, int my_nb, int c, uint32_t lds_wave)
+template <bool BUF, int T>
+__device__ __forceinline__ void hll_post_lds(const HllPosted &h, const HllSource &src, int my_nb, uint32_t c16, uint32_t lds_wave)
 {
     if constexpr (T < kHllInFlight + kHllLds) {
-        const int nbt = __builtin_amdgcn_update_dpp(0, my_nb, 0x150 + T, 0xF, 0xF, false);
-        const int64_t j = T < h.deg ? (int64_t)nbt : h.i;
-        if (T < h.total)
-            __builtin_amdgcn_global_load_lds((global_u32 *)(uintptr_t)(hll_in + j * 256 + 16 * c),
-                                             (lds_u32 *)(uintptr_t)(lds_wave + 1024u * (T - kHllInFlight)), 16, 0, 0);
-        hll_post_lds<T + 1>(h, hll_in, my_nb, c, lds_wave);
+        if (!__any(T < h.total)) return;  // wave-uniform
+        const int nbt = row_bcast<T>(my_nb);
+        lds_u32 *const slot = (lds_u32 *)(uintptr_t)(lds_wave + 1024u * (T - kHllInFlight));
+        if constexpr (BUF) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(src.rsrc, slot, 16, (int)(((uint32_t)nbt << 8) | c16), 0, 0, 0);
+        } else {
+            if (T < h.total) __builtin_amdgcn_global_load_lds((global_u32 *)(uintptr_t)(src.base + (int64_t)nbt * 256 + c16), slot, 16, 0, 0);
+        }
+        hll_post_lds<BUF, T + 1>(h, src, my_nb, c16, lds_wave);
     }
 }
 
@@ -101,7 +144,7 @@ __device__ __forceinline__ void hll_fold(const HllPosted &h, u32x4 &ae, u32x4 &a
 // A second use of the register landings -- folded before the LAST MinHash row and sent out again for neighbours 14 .. 20 (ids from a
 // second id word per lane), coverage 21 -- needs the accumulators alive through that row's walk: 96 / 64 / 32 bytes of scratch with
 // 7 / 6 / 5 register landings and 197 / 177 / 154 us; with 4 (no scratch, coverage 15) 146 us, the same as without.  Not shipped.
-template <int PPL>
+template <int PPL, bool BUF>
 __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
                                                uint32_t *__restrict__ mh_out, int p, const uint8_t *__restrict__ hll_in,
                                                uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride,
@@ -124,14 +167,35 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
     MinhashRows<PPL, R> m;
     m.setup(g, pa, pb, p, skip_hubs);
     const int lane = m.lane, grp = lane >> 4, c = lane & (kRow - 1);
+    const uint32_t c16 = 16u * (uint32_t)c;
+    const HllSource src = hll_source<BUF>(hll_in, g.N);
     const bool skip_self = g.skip_self && *g.skip_self != 0;  // HLL side only (one scalar load per wavefront); the first hop keeps its self loop
 
     auto chunk_rows = [&](int64_t q) -> int { return q < n_chunks ? (int)(g.row1 - (g.row0 + q * R) < R ? g.row1 - (g.row0 + q * R) : R) : 0; };
     auto load_bounds = [&](int64_t q) -> int64_t {  // lane l: rowptr[first row of chunk q + l]
         const int nr = chunk_rows(q);
-        return (nr > 0 && lane <= nr) ? g.rowptr[g.row0 + q * R + lane] : 0;
+        // a scalar base and a 32-bit lane offset.  (The empty asm hides the base from hipcc, which otherwise splits the address into a
+        // per-lane 64-bit rowptr + 8 * lane, kept in two VGPRs for the whole kernel, and a scalar rest: the two registers this
+        // kernel does not have)
+        const int64_t *first_bound = g.rowptr + (g.row0 + q * R);
+        asm volatile("" : "+s"(first_bound));
+        return (nr > 0 && lane <= nr) ? ((global_i64 *)first_bound)[(uint32_t)lane] : 0;  // (global, not flat: a flat load counts in lgkmcnt too)
     };
-    // what a lane fetches for a chunk whose bounds have arrived: its batch id (MinHash side) and its lane group's neighbour id (HLL side)
+    // the row of this lane group in a chunk of `nr` rows from row `first` whose bounds have arrived (rel: lane l holds the chunk-relative
+    // rowptr[first + l]); total = 0: no row to write (past the end, or a hub row left to the hub pass)
+    struct GroupRow { int64_t i; int rel0, deg, total; bool write; };
+    auto group_row = [&](int64_t first, int nr, int rel) -> GroupRow {
+        GroupRow w;
+        const bool ok = grp < nr;
+        w.rel0 = __shfl(rel, ok ? grp : 0);
+        w.deg = ok ? __shfl(rel, ok ? grp + 1 : 0) - w.rel0 : 0;
+        w.i = first + (ok ? grp : 0);
+        w.write = ok && !(skip_hubs && w.deg > g.hub_threshold);
+        w.total = w.write ? table_hop_total(w.deg, w.i < m.n_self, skip_self) : 0;
+        return w;
+    };
+    // what a lane fetches for a chunk whose bounds have arrived: its batch id (MinHash side) and its lane group's neighbour id (HLL side:
+    // lane c < total the id of neighbour c, the row itself as neighbour `deg`; the other lanes N, the row after the table's last)
     // (nid stays 32 bits wide until it is used: widening it here would be a use of the load's result, and hipcc would wait
     // -- vmcnt(0): for every HLL row posted just before -- right behind the load instead of after the MinHash walk)
     struct Ids { int nid; int my_nb; };
@@ -146,9 +210,9 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
         Ids out;
         out.nid = lane >= kNb ? (int)(first + (lane - kNb)) : 0;  // node ids are < 2^31 (checked by the entry point)
         if (lane < kNb && lane < c_n) out.nid = nb[lane];
-        const bool ok = grp < nr;
-        const int rel0 = __shfl(rel, ok ? grp : 0), rel1 = __shfl(rel, ok ? grp + 1 : 0);
-        out.my_nb = (ok && c < rel1 - rel0) ? nb[rel0 + c] : 0;
+        const GroupRow w = group_row(first, nr, rel);
+        out.my_nb = c < w.total ? (int)w.i : (int)g.N;
+        if (c < (w.total < w.deg ? w.total : w.deg)) out.my_nb = nb[w.rel0 + c];
         return out;
     };
 
@@ -163,16 +227,18 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
         m.set_batch((int64_t)ids_cur.nid);
         // HLL side of this chunk: the row of this lane group
         HllPosted h;
-        const bool ok = grp < m.rows;
-        const int rel0 = __shfl(m.rel, ok ? grp : 0), rel1 = __shfl(m.rel, ok ? grp + 1 : 0);
-        h.i = m.i0 + (ok ? grp : 0);
-        h.nb = m.nb + rel0;
-        h.deg = ok ? rel1 - rel0 : 0;
-        const bool hub = skip_hubs && h.deg > g.hub_threshold;
-        h.write = ok && !hub;
-        h.total = h.write ? table_hop_total(h.deg, h.i < m.n_self, skip_self) : 0;
-        hll_post<0>(h, hll_in, ids_cur.my_nb, c);              // HLL rows of chunk k
-        hll_post_lds<kHllInFlight>(h, hll_in, ids_cur.my_nb, c, lds_wave);
+        const GroupRow w = group_row(m.i0, m.rows, m.rel);
+        h.i = w.i;
+        h.nb = m.nb + w.rel0;
+        h.deg = w.deg;
+        h.write = w.write;
+        h.total = w.total;
+        hll_post<BUF, 0>(h, src, ids_cur.my_nb, c16);          // HLL rows of chunk k
+        // (the slots' addresses go to m0; hidden from hipcc here, they are one s_add each -- known to be loop constants, the seven of
+        // them are kept in spilled SGPRs and cost a v_readlane per post)
+        uint32_t lds_slots = lds_wave;
+        asm volatile("" : "+s"(lds_slots));
+        hll_post_lds<BUF, kHllInFlight>(h, src, ids_cur.my_nb, c16, lds_slots);
         const Ids ids_next = load_ids(chunk + stride, rp_next); // ids of chunk k + 1 (its bounds arrived during the last walk)
         const int64_t rp_after = load_bounds(chunk + 2 * stride);  // bounds of chunk k + 2
 #pragma unroll 1
@@ -186,13 +252,24 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
             for (int k = 0; k < kHllLds; ++k) {
+                if (!__any(kHllInFlight + k < h.total)) break;  // wave-uniform: not posted either
                 u32x4 v = *reinterpret_cast<const u32x4 *>(&landing[wave][k][16 * lane]);
                 if (!(kHllInFlight + k < h.total)) v = u32x4{0u, 0u, 0u, 0u};  // slot not written this round (stale bytes)
                 hll_acc(ae, ao, v);
             }
         }
         const u32x4 acc = hll_acc_result(ae, ao);
-        hll_row16_finish<false>(h.i, h.write, h.nb, h.deg, h.total, acc, kHllInFlight + kHllLds, hll_in, hll_out, cards_out, cards_stride, est, want_cards, c, Mirrors{});  // (the fused stage is the unsharded build's: no peers)
+        // (the fused stage is the unsharded build's: no peers)
+        if constexpr (BUF) {
+            hll_row16_finish_by<false>(h.i, h.write, h.nb, h.deg, h.total, acc, kHllInFlight + kHllLds,
+                                       [&](const int32_t *nb, int deg, int total, int64_t self_row, int first, int stride) {
+                                           return hll_walk_buffer(src.rsrc, (uint32_t)(g.N * 256), reinterpret_cast<const int32_t *>(hll_in), nb, deg,
+                                                                  total, self_row, first, stride, c16);
+                                       },
+                                       hll_out, cards_out, cards_stride, est, want_cards, c, Mirrors{});
+        } else {
+            hll_row16_finish<false>(h.i, h.write, h.nb, h.deg, h.total, acc, kHllInFlight + kHllLds, hll_in, hll_out, cards_out, cards_stride, est, want_cards, c, Mirrors{});
+        }
         rp_cur = rp_next;
         rp_next = rp_after;
         ids_cur = ids_next;
@@ -201,13 +278,13 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
 
 // P = 64 / 128: the register allocator is held to 96 VGPRs (amdgpu_waves_per_eu: at least FIVE wavefronts per SIMD; it gets there
 // without scratch -- left alone it spreads to ~125 and four wavefronts).  P = 192 / 256 would spill at 96 and keep the default budget.
-template <int PPL>
+template <int PPL, bool BUF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PPL <= 2 ? 5 : 1))) void fused_hop_persistent_kernel(
     GraphArgs g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ mh_out, int p,
     const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm,
     bool skip_hubs)
 {
-    fused_hop_body<PPL>(g, pa, pb, mh_out, p, hll_in, hll_out, cards_out, cards_stride, prm, skip_hubs);
+    fused_hop_body<PPL, BUF>(g, pa, pb, mh_out, p, hll_in, hll_out, cards_out, cards_stride, prm, skip_hubs);
 }
 
 }  // namespace ss
@@ -265,14 +342,24 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
     const int wg_per_cu = blocks > 256u * 128u ? 64 : 20;
     const unsigned grid = blocks < (unsigned)(256 * wg_per_cu) ? blocks : (unsigned)(256 * wg_per_cu);
     g.skip_self = own_hop1 ? skip_word : nullptr;
+    // how the kernel posts its hop-1 HLL rows: through a buffer descriptor when the table and the row after it fit the descriptor's
+    // 32-bit byte count, with flat addresses otherwise.  SS_FUSED_POSTS=flat, read at every launch, forces the flat form at any size
+    // (test hook; any other value, `buffer` included, leaves the choice to the size: a larger table cannot be described)
+    const char *posts_env = getenv("SS_FUSED_POSTS");
+    const bool buf_posts = buffer_describable(N * 256, 2 * 256) && !(posts_env && !strcmp(posts_env, "flat"));  // (lanes with nothing to fetch ask for row N)
     {
         ProfileSpan span(s, SS_PROF_FUSED, true);
-        switch (P / kWave) {
-            case 1: span.launch(fused_hop_persistent_kernel<1>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-            case 2: span.launch(fused_hop_persistent_kernel<2>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-            case 3: span.launch(fused_hop_persistent_kernel<3>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-            default: span.launch(fused_hop_persistent_kernel<4>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-        }
+        auto launch = [&](auto buf) {
+            constexpr bool B = decltype(buf)::value;
+            switch (P / kWave) {
+                case 1: span.launch(fused_hop_persistent_kernel<1, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
+                case 2: span.launch(fused_hop_persistent_kernel<2, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
+                case 3: span.launch(fused_hop_persistent_kernel<3, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
+                default: span.launch(fused_hop_persistent_kernel<4, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
+            }
+        };
+        if (buf_posts) launch(std::true_type{});
+        else launch(std::false_type{});
     }
     SS_LAUNCH_CHECK();
     g.skip_self = skip_word;  // (the MinHash table hop below; the hub launches do not look at it)

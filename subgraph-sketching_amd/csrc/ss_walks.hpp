@@ -130,6 +130,31 @@ __device__ __forceinline__ u32x4 hll_walk(const uint8_t *__restrict__ hll_in, co
     return hll_acc_result(ae, ao);
 }
 
+// the same walk of a p = 8 table through its buffer descriptor (table_rsrc, ss_common.hpp: `bytes` records): one shift-or per load for
+// a 32-bit offset instead of a 64-bit multiply-add, and the neighbours past `total` ask for the offset `bytes`, which the range check
+// answers with zeros -- no branch around the loads.  c16 = 16 * c; always_valid: a word that lanes past the row's end may load
+__device__ __forceinline__ u32x4 hll_walk_buffer(__amdgpu_buffer_rsrc_t rsrc, uint32_t bytes, const int32_t *always_valid,
+                                                 const int32_t *__restrict__ nb, int deg, int total, int64_t self_row, int first, int stride,
+                                                 uint32_t c16)
+{
+    u32x4 ae = {0u, 0u, 0u, 0u}, ao = {0u, 0u, 0u, 0u};
+    for (int t = first; t < total; t += kWalkBatch * stride) {
+        int id[kWalkBatch];
+        u32x4 x[kWalkBatch];
+#pragma unroll
+        for (int k = 0; k < kWalkBatch; ++k) id[k] = *(t + k * stride < deg ? nb + t + k * stride : always_valid);
+#pragma unroll
+        for (int k = 0; k < kWalkBatch; ++k) {
+            const int tk = t + k * stride;
+            const uint32_t j = tk < deg ? (uint32_t)id[k] : (uint32_t)self_row;
+            x[k] = buffer_load16(rsrc, tk < total ? (j << 8) | c16 : bytes);
+        }
+#pragma unroll
+        for (int k = 0; k < kWalkBatch; ++k) hll_acc(ae, ao, x[k]);
+    }
+    return hll_acc_result(ae, ao);
+}
+
 // ---- one table-hop row by one wavefront (propagate_kernel, and the update kernels of ss_update.hip: ONE body, so that a row
 // recomputed by an update carries the bits a rebuild gives it) ---------------------------------------------------------------
 // A 16-byte chunk per lane; the wavefront is split into G = 64 / SG sub-groups (SG = pow2 >= chunks per row, <= 64) that walk G
@@ -664,18 +689,19 @@ struct MinhashRows {
 // group per row, lane c = chunk c): the rest of rows up to kSolo neighbours by their own group, what is left of longer rows
 // by all four groups together, then the row's statistics, its store and its cardinality.  `total` = 0 marks a group without
 // a row to write (past the end, or a hub row left to the hub pass).
-template <bool MIR = true>
-__device__ __forceinline__ void hll_row16_finish(int64_t i, bool write, const int32_t *__restrict__ nb, int deg, int total, u32x4 acc,
-                                                 int walked, const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out,
-                                                 float *__restrict__ cards_out, int64_t cards_stride, const EstimatorTables &est,
-                                                 bool want_cards, int c /* lane & 15 */, const Mirrors &mir)
+// walk(nb, deg, total, self_row, first, stride): the fold of chunk c of those neighbours (hll_walk, or hll_walk_buffer)
+template <bool MIR, typename Walk>
+__device__ __forceinline__ void hll_row16_finish_by(int64_t i, bool write, const int32_t *__restrict__ nb, int deg, int total, u32x4 acc,
+                                                    int walked, Walk walk, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out,
+                                                    int64_t cards_stride, const EstimatorTables &est, bool want_cards, int c /* lane & 15 */,
+                                                    const Mirrors &mir)
 {
     constexpr int M = 256;
     // every lane group walks the first kSolo neighbours of its own row; what is left of longer rows is walked by the whole
     // wavefront, one row at a time (group g takes every 4th neighbour), so a wavefront lasts about sum(excess)/4 instead
     // of max(degree) iterations -- skewed graphs put rows of 10 and of 500 neighbours into the same wavefront
     constexpr int kSolo = 32;
-    if (__any(total > walked)) acc = bytemax16(acc, hll_walk(hll_in, nb, deg, total < kSolo ? total : kSolo, i, walked, 1, M, c));
+    if (__any(total > walked)) acc = bytemax16(acc, walk(nb, deg, total < kSolo ? total : kSolo, i, walked, 1));
     const unsigned long long long_rows = __ballot(total > kSolo);
     if (long_rows) {
         const int grp = (threadIdx.x & (kWave - 1)) / kRow;
@@ -688,7 +714,7 @@ __device__ __forceinline__ void hll_row16_finish(int64_t i, bool write, const in
             const int deg_g = __builtin_amdgcn_readlane(deg, kRow * gg), total_g = __builtin_amdgcn_readlane(total, kRow * gg);
             const int64_t i_g = ((int64_t)__builtin_amdgcn_readlane((int)((uint64_t)i >> 32), kRow * gg) << 32) |
                                 (uint32_t)__builtin_amdgcn_readlane((int)i, kRow * gg);
-            u32x4 part = hll_walk(hll_in, nb_g, deg_g, total_g, i_g, kSolo + grp, kWave / kRow, M, c);
+            u32x4 part = walk(nb_g, deg_g, total_g, i_g, kSolo + grp, kWave / kRow);
             part = bytemax16(part, shfl_xor4(part, 16));
             part = bytemax16(part, shfl_xor4(part, 32));
             if (grp == gg) acc = bytemax16(acc, part);
@@ -714,6 +740,19 @@ __device__ __forceinline__ void hll_row16_finish(int64_t i, bool write, const in
             if (want_cards && c == 0) cards_out[i * cards_stride] = hll_estimate(est, M - nonzero, hsum);
         }
     }
+}
+
+template <bool MIR = true>
+__device__ __forceinline__ void hll_row16_finish(int64_t i, bool write, const int32_t *__restrict__ nb, int deg, int total, u32x4 acc,
+                                                 int walked, const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out,
+                                                 float *__restrict__ cards_out, int64_t cards_stride, const EstimatorTables &est,
+                                                 bool want_cards, int c /* lane & 15 */, const Mirrors &mir)
+{
+    hll_row16_finish_by<MIR>(i, write, nb, deg, total, acc, walked,
+                             [&](const int32_t *nb_, int deg_, int total_, int64_t self_row, int first, int stride) {
+                                 return hll_walk(hll_in, nb_, deg_, total_, self_row, first, stride, 256, c);
+                             },
+                             hll_out, cards_out, cards_stride, est, want_cards, c, mir);
 }
 
 // HLL table hop for FOUR destination rows per wavefront: one 16-lane DPP row per destination, lane c owns the 16-byte
