@@ -277,9 +277,11 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
 }
 
 // P = 64 / 128: the register allocator is held to 96 VGPRs (amdgpu_waves_per_eu: at least FIVE wavefronts per SIMD; it gets there
-// without scratch -- left alone it spreads to ~125 and four wavefronts).  P = 192 / 256 would spill at 96 and keep the default budget.
+// without scratch -- left alone it spreads to ~125 and four wavefronts).  P = 192 / 256 would spill at 96: they are held to the 128
+// VGPRs of FOUR wavefronts, which they had without being asked until the row body changed shape (left alone: 139 and three; held:
+// 104 / 124, no scratch).
 template <int PPL, bool BUF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PPL <= 2 ? 5 : 1))) void fused_hop_persistent_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PPL <= 2 ? 5 : 4))) void fused_hop_persistent_kernel(
     GraphArgs g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ mh_out, int p,
     const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm,
     bool skip_hubs)
