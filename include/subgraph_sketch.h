@@ -619,6 +619,15 @@ int ss_gcn_degree(const int64_t *rowptr_c, const int32_t *order_c, const int64_t
                   float *dinv, float *loop_w, void *stream);
 int ss_sign_spmm(const int64_t *rowptr_r, const int32_t *order_r, const int64_t *col, const float *w, const float *dinv,
                  const float *loop_w, const void *scan, int64_t N, const float *x, int32_t F, float *out, void *stream);
+/* The transposed product: GCNConv's propagation with its default flow (reference models/elph.py:153-160, 214: gcn_norm, then
+ * aggregation at the TARGET), out[c] = sum over e with col_e = c, row_e != c of (dinv[row_e] * w_e * dinv[c]) * x[row_e], then
+ * + (dinv[c] * loop_w[c] * dinv[c]) * x[c].  rowptr_c / order_c: the STABLE grouping of the edge indices by COLUMN (always sorted:
+ * the order inside a group is the accumulation order here); row = edge_index[0]; dinv, loop_w, scan as for ss_sign_spmm, and the
+ * same contract: one lane per output element, ascending edge order, the remaining loop last, the norm formed left to right (the
+ * bits ss_sign_spmm forms for the same edge), products and sums rounded separately, existing self loops skipped, ids out of range
+ * not followed.  Each of the two products is the other's gradient with respect to x.  x, out fp32 [N, F], F % 4 == 0. */
+int ss_gcn_spmm_t(const int64_t *rowptr_c, const int32_t *order_c, const int64_t *row, const float *w, const float *dinv,
+                  const float *loop_w, const void *scan, int64_t N, const float *x, int32_t F, float *out, void *stream);
 
 /* 128-bit content digest of a device buffer (bytes % 16 == 0, 16-byte aligned): out[0] = sum, out[1] = xor over its 16-byte chunks
  * of a 64-bit mix of (chunk, chunk index) -- order-independent to compute, position-dependent in value.  out: device uint64[2],

@@ -11,7 +11,8 @@ from .negatives import NegativeSampler, sample_negatives
 from .wedge import WedgeGraph
 from .subgraphs import ExactSubgraphs
 from .components import Components, InducedSubgraph, connected_components, induced_subgraph, largest_component_subgraph
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs, components
+from .gcn import GCNConv, GCNGraph, gcn_propagate
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs, components, gcn
 
-__all__ = ['components', 'Components', 'InducedSubgraph', 'connected_components', 'induced_subgraph', 'largest_component_subgraph','LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
+__all__ = ['gcn', 'GCNConv', 'GCNGraph', 'gcn_propagate', 'components', 'Components', 'InducedSubgraph', 'connected_components', 'induced_subgraph', 'largest_component_subgraph','LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
            'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives', 'wedge', 'WedgeGraph', 'subgraphs', 'ExactSubgraphs']

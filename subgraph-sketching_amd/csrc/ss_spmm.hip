@@ -5,6 +5,8 @@
 // builds the CSR with a stable sort, so CSR order is the reference's edge order), multiply and add rounded separately
 // (-ffp-contract=off).  Mapping: a lane owns one float4 of the feature row; G = 64 / pow2(F/4) rows share a wavefront
 // (F = 128: two rows per wave).  HBM-bound gather of (E + N) feature rows -- the same shape as the MinHash table hop.
+// ss_gcn_spmm_t is the transposed product on the same body: GCNConv's propagation (reference models/elph.py:153-160, 214) and the
+// gradient of ss_sign_spmm, as ss_sign_spmm is its gradient (gcn.py).
 #include "ss_common.hpp"
 #include "ss_walks.hpp"
 
@@ -142,6 +144,10 @@ __global__ __launch_bounds__(256) void gcn_degree_kernel(const int64_t *__restri
 // row[e] == i; existing self loops are skipped, the node's one remaining loop comes last.  The lanes of a row first fetch one entry
 // each (edge index -> column, weight -> the column's dinv: three dependent loads, once per lanes_per_row entries instead of once
 // per batch of four) and hand them out with shuffles; the feature rows are then requested four at a time.
+// kTarget: the transposed product (GCNConv's default flow, reference models/elph.py:153-160, 214: aggregation at the TARGET) -- the
+// grouping is the one by column, `col` holds edge_index[0] (the sources), and the norm's outer factors swap places so that it stays
+// dinv[row_e] * w_e * dinv[col_e] left to right: the same bits as the other product forms for the same edge.
+template <bool kTarget>
 __global__ __launch_bounds__(256) void sign_spmm_kernel(const int64_t *__restrict__ rowptr_r, const int32_t *__restrict__ order_r,
                                                         const int64_t *__restrict__ col, const float *__restrict__ w,
                                                         const float *__restrict__ dinv, const float *__restrict__ loop_w, int64_t N,
@@ -170,7 +176,8 @@ __global__ __launch_bounds__(256) void sign_spmm_kernel(const int64_t *__restric
             const int64_t raw_c = col[e];
             const bool in_range = (uint64_t)raw_c < (uint64_t)N;  // (an id out of range is reported by ss_gcn_scan_edges; here it must only not be followed)
             const int64_t my_c = in_range ? raw_c : i;
-            const float my_nw = di * (unit ? 1.0f : w[e]) * dinv[my_c];
+            const float my_w = unit ? 1.0f : w[e], dj = dinv[my_c];
+            const float my_nw = kTarget ? dj * my_w * di : di * my_w * dj;
             const int my_use = j < e1 && in_range && my_c != i;
             const int n = (int)(e1 - j0 < lanes_per_row ? e1 - j0 : lanes_per_row);
             for (int k0 = 0; k0 < n; k0 += 4) {  // (uniform per row group)
@@ -277,8 +284,28 @@ extern "C" int ss_sign_spmm(const int64_t *rowptr_r, const int32_t *order_r, con
     if (lanes > kWave) lanes = kWave;
     const int rows_per_block = (256 / kWave) * (kWave / lanes);
     const int64_t blocks = (N + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(sign_spmm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr_r, order_r, col, w, dinv, loop_w, N, x,
-                       (int)F, out, lanes, reinterpret_cast<const GcnScan *>(scan));
+    hipLaunchKernelGGL(sign_spmm_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr_r, order_r, col, w, dinv, loop_w, N,
+                       x, (int)F, out, lanes, reinterpret_cast<const GcnScan *>(scan));
+    SS_LAUNCH_CHECK();
+    return SS_OK;
+}
+
+// out = gcn_norm(A)^T * x: GCNConv's propagation with its default flow (reference models/elph.py:153-160, 214), the transpose of
+// ss_sign_spmm's product and its gradient.  rowptr_c / order_c: the STABLE grouping of the edge indices by column (edge_index[1]) --
+// here the order inside a group is an accumulation order, so it is sorted whatever the weights; row = edge_index[0] (device int64[E]).
+extern "C" int ss_gcn_spmm_t(const int64_t *rowptr_c, const int32_t *order_c, const int64_t *row, const float *w, const float *dinv,
+                             const float *loop_w, const void *scan, int64_t N, const float *x, int32_t F, float *out, void *stream)
+{
+    using namespace ss;
+    if (N < 0 || F <= 0 || (F & 3) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
+    if (N == 0) return SS_OK;
+    if (!rowptr_c || !order_c || !row || !w || !dinv || !loop_w || !scan || !x || !out) return SS_ERR_INVALID_ARG;
+    int lanes = pow2_ceil(F >> 2);
+    if (lanes > kWave) lanes = kWave;
+    const int rows_per_block = (256 / kWave) * (kWave / lanes);
+    const int64_t blocks = (N + rows_per_block - 1) / rows_per_block;
+    hipLaunchKernelGGL(sign_spmm_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr_c, order_c, row, w, dinv, loop_w, N,
+                       x, (int)F, out, lanes, reinterpret_cast<const GcnScan *>(scan));
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

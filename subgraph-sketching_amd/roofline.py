@@ -207,6 +207,24 @@ def cn_features_bytes(links, row_entries, hits, F, weighted=False):
             'pool': rows + values + hits * 4 * F + links * 4 * F}
 
 
+def gcn_spmm_bytes(N, E, F, self_loops=0, unit=True):
+    """algorithmic bytes of one product of gcn.gcn_propagate (ss_gcn_spmm_t or ss_sign_spmm, csrc/ss_spmm.hip) -- the
+    same for both flows -- over N nodes and E edges of which `self_loops` are existing self loops (E' = E - self_loops entries
+    gather a row; every node's remaining loop gathers its own), F fp32 columns, rounded up to a multiple of 4.
+      'gathered'  (E' + N) * 4F from x          'written'  N * 4F
+      'entries'   per edge the order word (4), the other endpoint (8) and its dinv (4), the weight (4) unless all are 1;
+                  per node two row-pointer words (16), dinv and loop_w (8)
+    F > 256 re-reads the entry words once per 256 columns: ceil(F / 256) times."""
+    F = (F + 3) // 4 * 4
+    if N == 0 or F == 0:
+        return {'gathered': 0, 'written': 0, 'entries': 0, 'total': 0}
+    passes = (F + 255) // 256
+    gathered = (E - self_loops + N) * 4 * F
+    written = N * 4 * F
+    entries = passes * E * (16 if unit else 20) + N * 24
+    return {'gathered': gathered, 'written': written, 'entries': entries, 'total': gathered + written + entries}
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
