@@ -629,6 +629,48 @@ int ss_sign_spmm(const int64_t *rowptr_r, const int32_t *order_r, const int64_t 
 int ss_gcn_spmm_t(const int64_t *rowptr_c, const int32_t *order_c, const int64_t *row, const float *w, const float *dinv,
                   const float *loop_w, const void *scan, int64_t N, const float *x, int32_t F, float *out, void *stream);
 
+/* Graph readouts over a disjoint-union batch of subgraphs (csrc/ss_pool.hip; reference models/seal.py: global_sort_pool :245,
+ * global_add_pool / global_mean_pool :42-45, :101-106, :161, centre pooling :88-95, :149-156) [PyG semantics restated].
+ * Shared by every entry: graph q owns the rows rowptr[q] .. rowptr[q + 1] of x (rowptr: device int64 [L + 1], non-decreasing,
+ * inside [0, T]); x: device fp32 [T, F] row-major; every offset is 64-bit (T * F and L * k * F may pass 2^31); float4 accesses
+ * when F % 4 == 0 and the float bases are 16-byte aligned, scalar ones otherwise; no float atomics, no workspace.  A graph whose
+ * rowptr pair leaves [0, T] or descends, and an id or root outside its graph, is not followed: its places are not written
+ * (ss_pool_select: its row of perm is all -1) and *err_flag (device int32, nullable) is set.  Returns -1 before any launch for a
+ * null pointer (a float pointer may be null where it has no elements), k < 1, negative L, T or F, L >= 2^31; L == 0 returns 0.
+ * ss_pool_sort_capacity() = C = 1024: the words the on-chip sort of ss_pool_select holds; k <= C.
+ *   ss_pool_select   perm[q, j] (device int32 [L, k]) = the position inside graph q of its j-th row in the order: LAST channel
+ *                    x[., F - 1] descending, NaN (any sign) first, -0.0 ties with +0.0, ties by ascending position; -1 for
+ *                    j >= n.  The order is that of the 64-bit words (key << 32 | position) ascending, key = ~(monotone u32
+ *                    image of the float), NaN -> 0: all distinct, so a row of perm depends on its graph alone -- not on the
+ *                    tier (n <= C sorted in LDS; larger, any n < 2^31: radix select of the k-th key over the key column re-read
+ *                    with stride F, ordered compaction, the same sort), on L or on other graphs.  F >= 1.  One workgroup per graph.
+ *   ss_pool_gather   out[q, j * F .. (j + 1) * F) = x[rowptr[q] + perm[q, j]], zeros for perm -1 (out: device fp32 [L, k * F]).
+ *   ss_pool_scatter  its gradient: grad_x (device fp32 [T, F]) is cleared by the call, then grad_x[rowptr[q] + perm[q, j]] =
+ *                    g[q, j * F ..) for perm >= 0 (g: device fp32 [L, k * F]); perm must not name a row twice (ss_pool_select's does not).
+ *   ss_segment_pool  out[q, f] (device fp32 [L, F]) = the fp32 sum from +0.0 of x[t, f], t ascending over the graph, by ONE
+ *                    lane: the sequential loop bit for bit; mean != 0: then one division by (float)max(n, 1).  An empty graph
+ *                    gives 0.  A graph of 10^5 rows runs on one lane group (no hub tier).
+ *   ss_segment_pool_grad  grad_x[t] = g[q(t)] (mean != 0: / (float)max(n, 1)), q(t) by bisection of rowptr; rows in no graph get
+ *                    zeros; every row of grad_x [T, F] is written exactly once (g: device fp32 [L, F]).
+ *   ss_center_pool   out[q] (device fp32 [L, F]) = x[rowptr[q] + roots[q, 0]] * x[rowptr[q] + roots[q, 1]]; roots: device int32
+ *                    [L, 2], local indices read on the device; (-1, -1) gives zeros.
+ *   ss_center_pool_grad  grad_x [T, F] is cleared by the call, then with a, b the two root rows of link q: grad_x[a] = g[q] * x[b],
+ *                    grad_x[b] = g[q] * x[a]; a == b: grad_x[a] = g[q] * x[a] + g[q] * x[a], each product rounded first. */
+int ss_pool_sort_capacity(void);
+int ss_pool_select(const int64_t *rowptr, int64_t L, const float *x, int64_t T, int32_t F, int32_t k, int32_t *perm, int32_t *err_flag,
+                   void *stream);
+int ss_pool_gather(const int64_t *rowptr, int64_t L, const int32_t *perm, int32_t k, const float *x, int64_t T, int32_t F, float *out,
+                   int32_t *err_flag, void *stream);
+int ss_pool_scatter(const int64_t *rowptr, int64_t L, const int32_t *perm, int32_t k, const float *g, int64_t T, int32_t F, float *grad_x,
+                    int32_t *err_flag, void *stream);
+int ss_segment_pool(const int64_t *rowptr, int64_t L, const float *x, int64_t T, int32_t F, int32_t mean, float *out, int32_t *err_flag,
+                    void *stream);
+int ss_segment_pool_grad(const int64_t *rowptr, int64_t L, const float *g, int64_t T, int32_t F, int32_t mean, float *grad_x, void *stream);
+int ss_center_pool(const int64_t *rowptr, int64_t L, const int32_t *roots, const float *x, int64_t T, int32_t F, float *out,
+                   int32_t *err_flag, void *stream);
+int ss_center_pool_grad(const int64_t *rowptr, int64_t L, const int32_t *roots, const float *x, const float *g, int64_t T, int32_t F,
+                        float *grad_x, int32_t *err_flag, void *stream);
+
 /* 128-bit content digest of a device buffer (bytes % 16 == 0, 16-byte aligned): out[0] = sum, out[1] = xor over its 16-byte chunks
  * of a 64-bit mix of (chunk, chunk index) -- order-independent to compute, position-dependent in value.  out: device uint64[2],
  * overwritten (the call clears it first).  One streaming pass at HBM rate.  For the multi-GPU builds: the reference has ONE

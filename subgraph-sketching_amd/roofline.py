@@ -225,6 +225,20 @@ def gcn_spmm_bytes(N, E, F, self_loops=0, unit=True):
     return {'gathered': gathered, 'written': written, 'entries': entries, 'total': gathered + written + entries}
 
 
+def segment_pool_bytes(T, L, F):
+    """algorithmic bytes of pooling.global_add_pool / global_mean_pool forward (ss_segment_pool, csrc/ss_pool.hip)
+    over T node rows in L graphs, F fp32 columns: every row of x read once (T * 4F), the output written (L * 4F), the L + 1 offsets.
+    The backward moves the same bytes the other way (g read, grad_x written)."""
+    return T * 4 * F + L * 4 * F + 8 * (L + 1)
+
+
+def sort_pool_bytes(T, L, F, k):
+    """algorithmic bytes of pooling.global_sort_pool forward (ss_pool_select + ss_pool_gather): the key column once (T * 4: one
+    channel of x; the large tier re-reads it, which the model does not count), the selected rows (at most L * k * 4F), perm written
+    and read (2 * L * k * 4), the output (L * k * 4F) and the L + 1 offsets twice."""
+    return T * 4 + 2 * L * k * 4 * F + 2 * L * k * 4 + 16 * (L + 1)
+
+
 def pair_bytes_grouped(pairs, runs, P=128, p=8, h=2):
     """bytes of a query over `pairs` links walked grouped by their first node (ss_pair_features_grouped, hashing.GROUP_LINKS_MIN):
     the first node's h rows are fetched once per RUN of pairs that share it (`runs` = distinct first nodes of a grouped list),
