@@ -629,6 +629,45 @@ int ss_sign_spmm(const int64_t *rowptr_r, const int32_t *order_r, const int64_t 
 int ss_gcn_spmm_t(const int64_t *rowptr_c, const int32_t *order_c, const int64_t *row, const float *w, const float *dinv,
                   const float *loop_w, const void *scan, int64_t N, const float *x, int32_t F, float *out, void *stream);
 
+/* Unnormalised neighbour aggregation (csrc/ss_aggr.hip; reference models/seal.py:116-173 SEALSAGE, :259-328 SEALGIN, models/gnn.py:90-113
+ * SAGE) [PyG semantics restated]: out[dst_e] (+)= w_e * x[src_e] over the edges as they are -- no gcn_norm, existing self loops are
+ * ordinary entries, no loop is added, duplicates count once per copy -- for SAGEConv (sum or mean) and GINConv (sum + root term).
+ * One grouping serves one product: rowptr / order = the STABLE grouping of the edge indices by the endpoint that receives (always
+ * sorted: the order inside a group is the accumulation order), other = the other endpoint of every edge (device int64 [E]),
+ * w = the weights (device fp32 [E]) or NULL for unit weights (w is then never gathered; the bits are those of a multiplication by 1).
+ * The accumulation order is the contract.  Row i with the entries e_0 < e_1 < ... in chunks of C = ss_aggr_chunk() = 256 (the
+ * unit's SS_AGGR_CHUNK define):
+ *   p_c = the sequential fp32 sum from +0 of the terms t_e of chunk c, ascending;  s = ((0 + p_0) + p_1) + ...;  no entries: +0
+ *   t_e = fl(w_e * v_e),  v_e = x[other_e], or fl(x[other_e] / gather_den[other_e]) when gather_den is given (the mean's backward)
+ *   out_i = s,  then fl(s / den[i]) when den is given (the mean),  then + fl(*root * root_x[i]) when root is given (GIN: 1 + eps,
+ *   one fp32 word read on the device; root_x is x in the forward and the incoming gradient in the backward)
+ * products, quotients (IEEE, correctly rounded) and sums rounded separately; every output element is accumulated by one lane per
+ * chunk; no float atomics, no inter-workgroup waits; an id outside [0, N) is not followed.  A row of at most C entries
+ * is the plain sequential sum.  Since a row is its chunk sums added in chunk order, its bits do not depend on the tier:
+ *   ss_aggr_rows          the regular tier: one row group walks a whole row and stores it; rows of more than hub_entries (>= 1)
+ *                         entries are left untouched
+ *   ss_aggr_hub_partials  one row group per (hub row, chunk): p_c of chunk g goes to row g of the workspace [n_chunks, F].  hub_rows
+ *                         (int32 [n_hubs]) lists the rows of more than hub_entries entries, hub_chunk (int32 [n_hubs + 1]) where each
+ *                         hub's chunks start, chunk_hub (int32 [n_chunks]) the hub of every chunk
+ *   ss_aggr_hub_finish    per hub row: its partials added in chunk order, the same epilogue (den, root), the row stored
+ *   ss_aggr_workspace_bytes(hub_chunks, F) = hub_chunks * F * 4, 0 for a shape that is refused
+ *   ss_aggr_degree        den [N]: the same chunked sum over w_e alone (w NULL: the count, exact up to 2^24); 1 for a row without entries
+ * x, out, root_x: device fp32 [N, F] row-major, F % 4 == 0, 64-bit offsets.  SS_ERR_INVALID_ARG before any launch for a null pointer
+ * (w, gather_den, den, root may be null; root_x only with root), negative sizes, F <= 0, F % 4 != 0, N >= 2^31, hub_entries < 1, a
+ * workspace smaller than ss_aggr_workspace_bytes; N == 0 (hub launches: or no chunks / hubs) returns SS_OK without a launch. */
+int ss_aggr_chunk(void);
+size_t ss_aggr_workspace_bytes(int64_t hub_chunks, int32_t F);
+int ss_aggr_degree(const int64_t *rowptr, const int32_t *order, const float *w, int64_t N, float *den, void *stream);
+int ss_aggr_rows(const int64_t *rowptr, const int32_t *order, const int64_t *other, const float *w, int64_t N, int64_t hub_entries,
+                 const float *x, int32_t F, const float *gather_den, const float *den, const float *root, const float *root_x,
+                 float *out, void *stream);
+int ss_aggr_hub_partials(const int64_t *rowptr, const int32_t *order, const int64_t *other, const float *w, int64_t N,
+                         const int32_t *hub_rows, const int32_t *hub_chunk, const int32_t *chunk_hub, int64_t n_hubs, int64_t n_chunks,
+                         const float *x, int32_t F, const float *gather_den, void *workspace, size_t workspace_bytes, void *stream);
+int ss_aggr_hub_finish(const int32_t *hub_rows, const int32_t *hub_chunk, int64_t n_hubs, int64_t n_chunks, int64_t N,
+                       const void *workspace, size_t workspace_bytes, int32_t F, const float *den, const float *root,
+                       const float *root_x, float *out, void *stream);
+
 /* Graph readouts over a disjoint-union batch of subgraphs (csrc/ss_pool.hip; reference models/seal.py: global_sort_pool :245,
  * global_add_pool / global_mean_pool :42-45, :101-106, :161, centre pooling :88-95, :149-156) [PyG semantics restated].
  * Shared by every entry: graph q owns the rows rowptr[q] .. rowptr[q + 1] of x (rowptr: device int64 [L + 1], non-decreasing,

@@ -12,8 +12,9 @@ from .wedge import WedgeGraph
 from .subgraphs import ExactSubgraphs
 from .components import Components, InducedSubgraph, connected_components, induced_subgraph, largest_component_subgraph
 from .gcn import GCNConv, GCNGraph, gcn_propagate
+from .aggr import AggrGraph, GINConv, SAGEConv, aggregate
 from .pooling import center_pool, global_add_pool, global_mean_pool, global_sort_pool, sort_pool_k
-from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs, components, gcn, pooling
+from . import _native, hll_tables, knobs, dist, heuristics, sign, roofline, lsh, negatives, wedge, subgraphs, components, gcn, pooling, aggr
 
-__all__ = ['pooling', 'global_sort_pool', 'global_add_pool', 'global_mean_pool', 'center_pool', 'sort_pool_k', 'gcn', 'GCNConv', 'GCNGraph', 'gcn_propagate', 'components', 'Components', 'InducedSubgraph', 'connected_components', 'induced_subgraph', 'largest_component_subgraph','LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
+__all__ = ['aggr', 'AggrGraph', 'aggregate', 'SAGEConv', 'GINConv', 'pooling', 'global_sort_pool', 'global_add_pool', 'global_mean_pool', 'center_pool', 'sort_pool_k', 'gcn', 'GCNConv', 'GCNGraph', 'gcn_propagate', 'components', 'Components', 'InducedSubgraph', 'connected_components', 'induced_subgraph', 'largest_component_subgraph','LABEL_LOOKUP', 'ElphHashes', 'HllPropagation', 'MinhashPropagation', 'SketchTable', 'HopSketch',
            'build_csr', 'DeviceFeatureStore', 'StructureHead', 'pack_minhash', 'unpack_minhash', 'save_sketches', 'load_sketches', 'hll_tables', 'knobs', 'dist', 'heuristics', 'sign', 'roofline', 'lsh', 'negatives', 'NegativeSampler', 'sample_negatives', 'wedge', 'WedgeGraph', 'subgraphs', 'ExactSubgraphs']

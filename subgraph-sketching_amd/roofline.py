@@ -225,6 +225,28 @@ def gcn_spmm_bytes(N, E, F, self_loops=0, unit=True):
     return {'gathered': gathered, 'written': written, 'entries': entries, 'total': gathered + written + entries}
 
 
+def aggr_bytes(N, E, F, unit=True, mean=False, root=False, hub_chunks=0):
+    """algorithmic bytes of one product of aggr.aggregate (ss_aggr_rows with the hub launches, csrc/ss_aggr.hip) -- the
+    same for both flows -- over N nodes and E edges (every edge is an entry: self loops too), F fp32 columns rounded up to a multiple of 4.
+      'gathered'   E * 4F from x, and N * 4F more with a root term (the node's own row)
+      'written'    N * 4F
+      'entries'    per edge the order word (4) and the other endpoint (8), the weight (4) unless unit; per node two row-pointer
+                   words (16), and den (4) for the mean
+      'workspace'  hub_chunks * 4F written by the partials launch and read again by the finish launch
+    F > 256 re-reads the edge words once per 256 columns: ceil(F / 256) times.  The mean's backward gathers one den word (4) per
+    edge on top of this, which the model does not count."""
+    F = (F + 3) // 4 * 4
+    if N == 0 or F == 0:
+        return {'gathered': 0, 'written': 0, 'entries': 0, 'workspace': 0, 'total': 0}
+    passes = (F + 255) // 256
+    gathered = (E + (N if root else 0)) * 4 * F
+    written = N * 4 * F
+    entries = passes * E * (12 if unit else 16) + N * (20 if mean else 16)
+    workspace = 2 * hub_chunks * 4 * F
+    return {'gathered': gathered, 'written': written, 'entries': entries, 'workspace': workspace,
+            'total': gathered + written + entries + workspace}
+
+
 def segment_pool_bytes(T, L, F):
     """algorithmic bytes of pooling.global_add_pool / global_mean_pool forward (ss_segment_pool, csrc/ss_pool.hip)
     over T node rows in L graphs, F fp32 columns: every row of x read once (T * 4F), the output written (L * 4F), the L + 1 offsets.
