@@ -668,6 +668,51 @@ int ss_aggr_hub_finish(const int32_t *hub_rows, const int32_t *hub_chunk, int64_
                        const void *workspace, size_t workspace_bytes, int32_t F, const float *den, const float *root,
                        const float *root_x, float *out, void *stream);
 
+/* The link decoder's endpoint gather and Hadamard product, forward and backward (csrc/ss_link_decoder.hip).  Replaces the torch
+ * indexing `x[curr_links]` of reference runners/train.py:56, :63, :200, :201 and the product `x[:, 0, :] * x[:, 1, :]` of
+ * models/elph.py:54 (`x_i * x_j`, models/gnn.py:212), whose backward is an index_put with float atomics.
+ * links: device int64 [L, 2] row-major, L < 2^30; slot q = 2l + s is endpoint s of link l.  x: device fp32 [N, F] row-major,
+ * N < 2^31; every offset is 64-bit (N * F and 2 * L * F may pass 2^31); float4 accesses when F % 4 == 0 and the float bases are
+ * 16-byte aligned, scalar ones otherwise -- the bits are the same either way.
+ *   ss_link_gather    out[l, s] = x[links[l, s]]                      out: device fp32 [L, 2, F]
+ *   ss_link_hadamard  out[l] = fl(x[links[l, 0]] * x[links[l, 1]])    out: device fp32 [L, F]; no [L, 2, F] tensor is made
+ *                     An id outside [0, N), negative ones included, is not followed: its row (hadamard: the link's row) is zeros and
+ *                     *err_flag (int32 the device can write, nullable) is set -- one word per launch.
+ * The backward runs on a grouping of the 2L slots by node: nodes (device int64 [M], the distinct touched nodes ascending), rowptr
+ * (device int64 [M + 1]), order (device int32 [2L], the slot ids of every node ascending: a STABLE grouping).  Only the M listed
+ * rows of grad_x (device fp32 [N, F]) are written; the caller clears the others.  mode 0 (gather): g is device fp32 [L, 2, F], x is
+ * not read and may be null; mode 1 (product): g is device fp32 [L, F].  The accumulation order is the contract, the one ss_aggr_rows is
+ * pinned to.  Row nodes[r] with the slots q_0 < q_1 < ... in chunks of C = ss_link_chunk() = 256:
+ *   p_c = the sequential fp32 sum from +0 of the terms t_q of chunk c, ascending;  s = ((0 + p_0) + p_1) + ...
+ *   t_q = g[l, s, :] (mode 0),  fl(g[l, :] * x[links[l, 1 - s], :]) (mode 1),  l = q >> 1, s = q & 1;  a self link is two slots
+ * products and sums rounded separately, one lane per output element and chunk, no float atomics, no inter-workgroup waits; a slot
+ * id outside [0, 2L) and a partner id outside [0, N) are not followed.  A row's bits depend on its own slots and their order, not
+ * on the tier, on hub_entries or on the other links of the batch:
+ *   ss_link_grad_rows          the regular tier: one row group per listed node; rows of more than hub_entries (>= 1) slots are left
+ *                              untouched
+ *   ss_link_grad_hub_partials  one row group per (hub row, chunk): p_c of chunk t goes to row t of the workspace [n_chunks, F].
+ *                              hub_rows (int32 [n_hubs]) lists the POSITIONS in nodes of the rows of more than hub_entries slots,
+ *                              hub_chunk (int32 [n_hubs + 1]) where each hub's chunks start, chunk_hub (int32 [n_chunks]) the hub of
+ *                              every chunk
+ *   ss_link_grad_hub_finish    per hub row: its partials added in chunk order, the row of grad_x stored
+ *   ss_link_workspace_bytes(hub_chunks, F) = hub_chunks * F * 4, 0 for a shape that is refused
+ * SS_ERR_INVALID_ARG before any launch for a null pointer (err_flag may be null; x in mode 0), negative sizes, L >= 2^30, N >= 2^31,
+ * M > N or M > 2L, hub_entries < 1, a mode other than 0 or 1, n_hubs > n_chunks, a workspace smaller than ss_link_workspace_bytes;
+ * L == 0, M == 0, F == 0 (hub launches: or no chunks / hubs) return SS_OK without a launch. */
+int ss_link_chunk(void);
+size_t ss_link_workspace_bytes(int64_t hub_chunks, int32_t F);
+int ss_link_gather(const int64_t *links, int64_t L, const float *x, int64_t N, int32_t F, float *out, int32_t *err_flag, void *stream);
+int ss_link_hadamard(const int64_t *links, int64_t L, const float *x, int64_t N, int32_t F, float *out, int32_t *err_flag, void *stream);
+int ss_link_grad_rows(const int64_t *nodes, const int64_t *rowptr, const int32_t *order, int64_t M, const int64_t *links, int64_t L,
+                      int64_t N, int64_t hub_entries, int32_t mode, const float *g, const float *x, int32_t F, float *grad_x, void *stream);
+int ss_link_grad_hub_partials(const int64_t *rowptr, const int32_t *order, int64_t M, const int64_t *links, int64_t L, int64_t N,
+                              const int32_t *hub_rows, const int32_t *hub_chunk, const int32_t *chunk_hub, int64_t n_hubs, int64_t n_chunks,
+                              int32_t mode, const float *g, const float *x, int32_t F, void *workspace, size_t workspace_bytes,
+                              void *stream);
+int ss_link_grad_hub_finish(const int64_t *nodes, int64_t M, const int32_t *hub_rows, const int32_t *hub_chunk, int64_t n_hubs,
+                            int64_t n_chunks, int64_t N, const void *workspace, size_t workspace_bytes, int32_t F, float *grad_x,
+                            void *stream);
+
 /* Graph readouts over a disjoint-union batch of subgraphs (csrc/ss_pool.hip; reference models/seal.py: global_sort_pool :245,
  * global_add_pool / global_mean_pool :42-45, :101-106, :161, centre pooling :88-95, :149-156) [PyG semantics restated].
  * Shared by every entry: graph q owns the rows rowptr[q] .. rowptr[q + 1] of x (rowptr: device int64 [L + 1], non-decreasing,

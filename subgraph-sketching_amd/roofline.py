@@ -247,6 +247,36 @@ def aggr_bytes(N, E, F, unit=True, mean=False, root=False, hub_chunks=0):
             'total': gathered + written + entries + workspace}
 
 
+def link_decoder_bytes(N, L, F, product=False, backward=False, M=None, hub_chunks=0):
+    """algorithmic bytes of one launch family of link_decoder (csrc/ss_link_decoder.hip) for L links over N nodes and F
+    fp32 columns: link_gather (product=False) or link_hadamard (product=True), forward or backward; M = the distinct nodes the batch
+    touches (default: as many as there can be, min(N, 2L)).
+      forward    'ids' the 2L endpoint ids (8 each); 'gathered' 2L rows of x (4F each); 'written' 2L rows (gather) or L rows (product)
+      backward   'cleared' the zero fill of grad_x, N * 4F; 'gathered' per slot a row of g, and for the product the partner's row of x
+                 as well; 'written' the M touched rows; 'entries' per slot the order word (4) and, for the product, the partner id
+                 (8), re-read once per pass over the columns -- ceil(F / 256) passes with float4 pieces, ceil(F / 64) when F % 4 != 0 --
+                 and per touched node its id (8) and two row-pointer words (16); 'workspace' hub_chunks * 4F written by the partials
+                 launch and read again by the finish launch
+    The plan's own build (a stable grouping of 2L ids and a few passes over N counters) is not part of a product and not counted."""
+    zero = {'ids': 0, 'gathered': 0, 'written': 0, 'cleared': 0, 'entries': 0, 'workspace': 0, 'total': 0}
+    if F == 0 or (L == 0 and not backward) or (N == 0 and backward):
+        return zero
+    row = 4 * F
+    b = dict(zero)
+    if not backward:
+        b['ids'], b['gathered'], b['written'] = 2 * L * 8, 2 * L * row, (L if product else 2 * L) * row
+    else:
+        M = min(N, 2 * L) if M is None else M
+        passes = (F + 255) // 256 if F % 4 == 0 else (F + 63) // 64
+        b['cleared'] = N * row
+        b['gathered'] = (2 if product else 1) * 2 * L * row
+        b['written'] = M * row
+        b['entries'] = passes * 2 * L * (12 if product else 4) + M * 24
+        b['workspace'] = 2 * hub_chunks * row
+    b['total'] = sum(v for k, v in b.items() if k != 'total')
+    return b
+
+
 def segment_pool_bytes(T, L, F):
     """algorithmic bytes of pooling.global_add_pool / global_mean_pool forward (ss_segment_pool, csrc/ss_pool.hip)
     over T node rows in L graphs, F fp32 columns: every row of x read once (T * 4F), the output written (L * 4F), the L + 1 offsets.
