@@ -130,7 +130,8 @@ class _DeferredErrors(object):
     def flag(self, device, what):
         key = str(device)
         if key not in self._flags:
-            self._flags[key] = torch.zeros(1, dtype=torch.int32).pin_memory()
+            with torch.inference_mode(False):  # (made inside an inference_mode block the word could not be cleared outside it)
+                self._flags[key] = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._calls.append(what)
         del self._calls[:-8]
         return self._flags[key]

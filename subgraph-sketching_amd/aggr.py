@@ -204,7 +204,11 @@ _CACHE = {'key': None, 'graph': None}
 
 
 def _identity(t):
-    return None if t is None else (weakref.ref(t), t.data_ptr(), tuple(t.shape), t._version)
+    # (as gcn._identity) an inference tensor tracks no version -- reading t._version raises -- and is keyed on object, address and
+    # shape alone: outside inference mode torch refuses every in-place edit of it; an edit inside an inference_mode block goes unseen
+    if t is None:
+        return None
+    return (weakref.ref(t), t.data_ptr(), tuple(t.shape), None if t.is_inference() else t._version)
 
 
 def _same(a, b):

@@ -125,7 +125,13 @@ _CACHE = {'key': None, 'graph': None}
 
 
 def _identity(t):
-    return None if t is None else (weakref.ref(t), t.data_ptr(), tuple(t.shape), t._version)
+    # A tensor made under torch.inference_mode() tracks no version (reading t._version raises).  It is still cached, keyed on
+    # object, address and shape alone: outside inference mode torch refuses every in-place edit of it, so there the key cannot go
+    # stale; an edit INSIDE an inference_mode block goes unseen -- pass a GCNGraph, or a fresh tensor, after such an edit.  Not
+    # caching it instead would rebuild the plan in every conv of an evaluation loop, which is what the cache exists to avoid.
+    if t is None:
+        return None
+    return (weakref.ref(t), t.data_ptr(), tuple(t.shape), None if t.is_inference() else t._version)
 
 
 def _same(a, b):

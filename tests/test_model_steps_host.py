@@ -1,0 +1,268 @@
+"""tests/model_steps_reference.py pinned on the CPU, so that the yardstick of tests/test_model_steps_gpu.py is not itself wrong:
+the plain-torch forms against dense float64 matrices and torch.autograd.gradcheck on graphs of 5 to 12 nodes; the twin Functions'
+backward against autograd through the plain forms on the ELPH-shaped model at a reduced size; e_32 > 0 for every compared tensor at
+the shapes and seeds the GPU test uses (the twin model standing in for the package model: it has the bits the GPU run must have);
+and the CPU part of the inference-tensor regression of gcn._identity / aggr._identity."""
+import copy
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import model_steps_reference as ms
+import subgraph_restatement as sr
+from conftest import oracle_params
+from test_exact_nodes_host import _ba40
+
+GRAPH_SEEDS = (0, 1, 2, 3)
+
+
+def _tiny_graph(seed):
+    """5 to 12 nodes, directed, duplicates, explicit loops (one node has two), a node without entries, random weights"""
+    rng = np.random.RandomState(seed)
+    n = (5, 7, 9, 12)[seed % 4]
+    ei = rng.randint(0, n - 1, size=(2, 3 * n)).astype(np.int64)  # node n - 1 has no edge
+    ei[:, :3] = [[1, 1, 2], [1, 1, 2]]
+    ei[:, 3] = ei[:, 4]                                            # a duplicate edge
+    w = rng.uniform(0.25, 2.0, size=ei.shape[1]).astype(np.float32)
+    return ms.HostGraph(n, ei, w), torch.from_numpy(rng.standard_normal((n, 3)))
+
+
+def _dense(g, loops_as_gcn):
+    """float64 [n, n] A[row, col] += w; with loops_as_gcn the explicit loops are replaced by one loop per node: weight 1, or the
+    weight of the node's last explicit loop"""
+    A = np.zeros((g.n, g.n))
+    w = g.weights().astype(np.float64)
+    loop = np.ones(g.n)
+    for e in range(g.ei.shape[1]):
+        r, c = g.ei[:, e]
+        if r == c and loops_as_gcn:
+            loop[r] = w[e]
+        else:
+            A[r, c] += w[e]
+    return A + np.diag(loop) if loops_as_gcn else A
+
+
+@pytest.mark.parametrize('seed', GRAPH_SEEDS)
+def test_plain_propagations_equal_their_dense_forms(seed):
+    g, x = _tiny_graph(seed)
+    A = _dense(g, True)
+    deg = A.sum(axis=0)  # weighted in-degree over edge_index[1]
+    dinv = np.where(deg > 0, 1.0 / np.sqrt(np.where(deg > 0, deg, 1.0)), 0.0)
+    gcn = (dinv[:, None] * A * dinv[None, :]).T @ x.numpy()
+    np.testing.assert_allclose(ms.plain_propagate(x, g).numpy(), gcn, rtol=1e-12, atol=1e-14)
+    B = _dense(g, False)
+    count = np.bincount(g.ei[1], minlength=g.n)
+    assert count[g.n - 1] == 0
+    den = np.where(count == 0, 1.0, B.sum(axis=0))
+    np.testing.assert_allclose(ms.plain_aggregate(x, g, True, None).numpy(), (B.T @ x.numpy()) / den[:, None], rtol=1e-12, atol=1e-14)
+    root = torch.tensor([1.375], dtype=torch.float64)
+    np.testing.assert_allclose(ms.plain_aggregate(x, g, False, root).numpy(), B.T @ x.numpy() + 1.375 * x.numpy(), rtol=1e-12, atol=1e-14)
+    xg = x.clone().requires_grad_(True)
+    assert torch.autograd.gradcheck(lambda t: ms.plain_propagate(t, g), (xg,))
+    assert torch.autograd.gradcheck(lambda t: ms.plain_aggregate(t, g, True, None), (xg,))
+    assert torch.autograd.gradcheck(lambda t, r: ms.plain_aggregate(t, g, False, r), (xg, root.clone().requires_grad_(True)))
+
+
+def test_a_zero_degree_node_is_normalised_to_zero():
+    g = ms.HostGraph(5, [[0, 1, 3], [1, 2, 3]], [1.0, 2.0, 0.0])  # node 3: a loop of weight 0 and nothing else
+    x = torch.ones((5, 2), dtype=torch.float64)
+    out = ms.plain_propagate(x, g)
+    assert torch.isfinite(out).all() and bool((out[3] == 0).all()) and bool((out[4] == 1).all())
+
+
+@pytest.mark.parametrize('seed', GRAPH_SEEDS)
+def test_plain_decoder_and_readouts_equal_their_dense_forms(seed):
+    rng = np.random.RandomState(10 + seed)
+    n = (5, 7, 9, 12)[seed % 4]
+    x = torch.from_numpy(rng.standard_normal((n, 3)))
+    links = rng.randint(0, n, size=(6, 2))
+    links[0], links[1] = (2, 2), links[2]  # a self link, a duplicated link
+    hl = ms.HostLinks(n, links)
+    S = [np.eye(n)[links[:, s]] for s in (0, 1)]
+    np.testing.assert_array_equal(ms.plain_gather(x, hl).numpy(), np.stack([S[0] @ x.numpy(), S[1] @ x.numpy()], axis=1))
+    np.testing.assert_array_equal(ms.plain_hadamard(x, hl).numpy(), (S[0] @ x.numpy()) * (S[1] @ x.numpy()))
+    # readouts: graphs of sizes (a, 0, b) over the n rows; the empty one has roots (-1, -1)
+    a = n // 2
+    rowptr = np.array([0, a, a, n], dtype=np.int64)
+    roots = np.array([[a - 1, 0], [-1, -1], [1, 1]], dtype=np.int32)
+    k = 4
+    perm = np.full((3, k), -1, dtype=np.int32)
+    perm[0, :min(a, k)] = rng.permutation(a)[:k]
+    perm[2, :min(n - a, k)] = rng.permutation(n - a)[:k]
+    pools = ms.HostPools(rowptr, roots, k, perm)
+    M = np.zeros((3, n))
+    M[0, :a], M[2, a:] = 1.0 / a, 1.0 / (n - a)
+    np.testing.assert_allclose(ms.plain_mean_pool(x, pools).numpy(), M @ x.numpy(), rtol=1e-12, atol=1e-14)
+    Ra, Rb = np.zeros((3, n)), np.zeros((3, n))
+    Ra[0, a - 1], Rb[0, 0], Ra[2, a + 1], Rb[2, a + 1] = 1, 1, 1, 1
+    np.testing.assert_array_equal(ms.plain_center_pool(x, pools).numpy(), (Ra @ x.numpy()) * (Rb @ x.numpy()))
+    P = np.zeros((3 * k, n))
+    for q in range(3):
+        for j in range(k):
+            if perm[q, j] >= 0:
+                P[q * k + j, rowptr[q] + perm[q, j]] = 1
+    np.testing.assert_array_equal(ms.plain_sort_pool(x, pools).numpy(), (P @ x.numpy()).reshape(3, k * 3))
+    xg = x.clone().requires_grad_(True)
+    for f in (ms.plain_gather, ms.plain_hadamard):
+        assert torch.autograd.gradcheck(lambda t: f(t, hl), (xg,))
+    for f in (ms.plain_mean_pool, ms.plain_center_pool, ms.plain_sort_pool):
+        assert torch.autograd.gradcheck(lambda t: f(t, pools), (xg,))
+
+
+@pytest.mark.parametrize('seed', GRAPH_SEEDS[:2])
+def test_the_twins_forwards_are_the_plain_forms_rounded(seed):
+    """every twin Function against its plain form in float64 on a tiny case: forward and gradient within float32 rounding"""
+    g, x64 = _tiny_graph(seed)
+    x = x64.float()
+    n = g.n
+    links = ms.HostLinks(n, np.array([[0, 1], [2, 2], [1, 0], [n - 1, 3]]))
+    a = n // 2
+    pools = ms.HostPools(np.array([0, a, a, n]), np.array([[0, a - 1], [-1, -1], [1, 1]], dtype=np.int32), 3)
+    pools.perm = ms.pr.sort_pool(x.numpy(), pools.rowptr, 3)[1]
+    twin, plain = ms.twin_ops(), ms.plain_ops()
+    root = torch.tensor([1.375])
+    cases = [(lambda o, t, r: o.gcn(3, 3)._propagate(t, g)), (lambda o, t, r: o.sage(3, 3)._aggregate(t, g, True, None)),
+             (lambda o, t, r: o.gin(None)._aggregate(t, g, False, r)), (lambda o, t, r: o.gather(t, links)),
+             (lambda o, t, r: o.hadamard(t, links)), (lambda o, t, r: o.sort_pool(t, pools)), (lambda o, t, r: o.mean_pool(t, pools)),
+             (lambda o, t, r: o.center_pool(t, pools))]
+    for i, f in enumerate(cases):
+        xt, rt = x.clone().requires_grad_(True), root.clone().requires_grad_(True)
+        xp, rp = x.double().requires_grad_(True), root.double().requires_grad_(True)
+        yt, yp = f(twin, xt, rt), f(plain, xp, rp)
+        G = torch.from_numpy(np.random.RandomState(i).standard_normal(tuple(yp.shape)))
+        (yt * G.float()).sum().backward()
+        (yp * G).sum().backward()
+        np.testing.assert_allclose(yt.detach().numpy(), yp.detach().numpy(), rtol=1e-5, atol=1e-6, err_msg=f'op {i} forward')
+        np.testing.assert_allclose(xt.grad.numpy(), xp.grad.numpy(), rtol=1e-5, atol=1e-5, err_msg=f'op {i} gradient')
+        if rp.grad is not None:
+            np.testing.assert_allclose(rt.grad.numpy(), rp.grad.numpy(), rtol=1e-5, atol=1e-5, err_msg=f'op {i} root gradient')
+
+
+def _oracle_sf(n, ei, links, prm):
+    """the engine's structure features restated by the oracle (a constant input of the ELPH-shaped model)"""
+    from oracle import oracle
+    tables, cards = oracle.build_hash_tables(n, ei, 2, 128, prm)
+    return torch.from_numpy(np.ascontiguousarray(oracle.pair_features(links, tables, cards, 2, prm), dtype=np.float32))
+
+
+def _elph_tables(inp, prm, variant, seed):
+    sf = _oracle_sf(inp.n, inp.ei, inp.links, prm)
+    batch = types.SimpleNamespace(x=torch.from_numpy(inp.x), graph=ms.HostGraph(inp.n, inp.ei, inp.w), links=ms.HostLinks(inp.n, inp.links),
+                                  sf=sf, num_links=len(inp.links))
+    make = lambda ops: ms.Elph(ops, sf.size(1), variant)
+    twin = ms.build(make, ms.twin_ops(), seed)
+    labels = ms.labels_for(batch.num_links, ms.STEP_SEED)
+    got = ms.step(twin, batch, labels)
+    r64, r32 = ms.float64_runs(make, twin, batch, labels)
+    return ms.error_table(twin, got, r64, r32)
+
+
+def _check(title, rows):
+    print(ms.format_table(title, rows))
+    assert all(e_32 > 0 for _, _, _, e_32, _, _ in rows), 'a float32 yardstick of zero: the bound would be its floor alone'
+    assert all(ok for *_, ok in rows), [key for key, *_, ok in rows if not ok]
+
+
+@pytest.mark.parametrize('variant', ['gather', 'hadamard'])
+def test_twin_backward_against_the_plain_form_at_a_reduced_size(regenerated_tables, variant):
+    rows = _elph_tables(ms.small_elph_inputs(), oracle_params(regenerated_tables[8]), variant, ms.ELPH_SEED)
+    assert len(rows) == 2 + 16 + 1  # loss, logits, sixteen parameters, x
+    _check(f'ELPH-shaped ({variant}), 40 nodes, the twin standing in', rows)
+
+
+@pytest.mark.parametrize('variant', ['gather', 'hadamard'])
+def test_the_float32_yardstick_is_positive_for_the_elph_step(regenerated_tables, variant):
+    inp = ms.elph_inputs()
+    counts = np.bincount(inp.links.reshape(-1), minlength=inp.n)
+    assert 690 <= len(inp.links) <= 710 and counts[ms.HOT] > 256 and counts[ms.gr.ZERO_LOOP] >= 2
+    assert (inp.links[:, 0] == inp.links[:, 1]).any() and len(np.unique(inp.links, axis=0)) < len(inp.links)
+    _check(f'ELPH-shaped ({variant}), N = 601, the twin standing in', _elph_tables(inp, oracle_params(regenerated_tables[8]), variant, ms.ELPH_SEED))
+
+
+def _seal_batch(links, max_nodes=None):
+    n, ei, _ = _ba40()
+    sub = sr.restate(n, ei, links, 2, max_nodes=max_nodes)
+    z = sr.labels(sub, 'drnl')
+    T = len(sub.ids)
+    sei = ms.subgraph_edges(sub.rowptr, sub.adj_ptr, sub.nbr)
+    k = ms.pr.sort_pool_k(np.diff(sub.rowptr).tolist())
+    return types.SimpleNamespace(z=ms.clamp_z(torch.from_numpy(np.asarray(z, dtype=np.int64))), graph=ms.HostGraph(T, sei, sub.weight.astype(np.float32)),
+                                 pools=ms.HostPools(sub.rowptr, sub.roots, k), num_links=len(sub.rowptr) - 1, sizes=np.diff(sub.rowptr))
+
+
+@pytest.mark.parametrize('kind', ['sage', 'gin', 'dgcnn'])
+def test_the_float32_yardstick_is_positive_for_the_seal_steps(kind):
+    batch = _seal_batch(_ba40()[2])
+    max_z = ms.MAX_Z
+    make = {'sage': lambda ops: ms.SealSage(ops, max_z), 'gin': lambda ops: ms.SealGin(ops, max_z),
+            'dgcnn': lambda ops: ms.SealDgcnn(ops, max_z, batch.pools.k)}[kind]
+    twin = ms.build(make, ms.twin_ops(), ms.SEAL_SEED)
+    labels = ms.labels_for(batch.num_links, ms.STEP_SEED)
+    got = ms.step(twin, batch, labels)
+    if kind == 'dgcnn':  # the order of the float32 run, as the GPU test takes it from the package
+        taps = {}
+        with torch.no_grad():
+            twin(batch, taps)
+        batch.pools.perm = ms.pr.sort_pool(taps['stack'].numpy(), batch.pools.rowptr, batch.pools.k)[1]
+    r64, r32 = ms.float64_runs(make, twin, batch, labels)
+    _check(f'SEAL-shaped {kind}, BA-40, the twin standing in', ms.error_table(twin, got, r64, r32))
+
+
+def test_a_subgraph_emptied_by_max_nodes_goes_through_a_step():
+    links = _ba40()[2][:4]
+    sizes = _seal_batch(links).sizes
+    cap = int(min(sizes))  # rows of more nodes than this are emptied
+    batch = _seal_batch(links, max_nodes=cap)
+    assert (batch.sizes == 0).any() and (batch.sizes > 0).any() and bool((batch.pools.roots[batch.sizes == 0] == -1).all())
+    max_z = ms.MAX_Z
+    make = lambda ops: ms.SealSage(ops, max_z)
+    twin = ms.build(make, ms.twin_ops(), ms.SEAL_SEED)
+    labels = ms.labels_for(batch.num_links, ms.STEP_SEED)
+    got = ms.step(twin, batch, labels)
+    r64, r32 = ms.float64_runs(make, twin, batch, labels)
+    _check('SEALSAGE with an emptied subgraph, the twin standing in', ms.error_table(twin, got, r64, r32))
+
+
+def test_sgd_steps_and_deepcopy_repeat_on_the_twin():
+    """the harness itself: a deep copy of a model takes the same three SGD steps bit for bit, and differing() sees one flipped bit"""
+    inp = ms.small_elph_inputs()
+    torch.manual_seed(5)
+    batch = types.SimpleNamespace(x=torch.from_numpy(inp.x), graph=ms.HostGraph(inp.n, inp.ei, inp.w), links=ms.HostLinks(inp.n, inp.links),
+                                  sf=torch.randn(len(inp.links), 8), num_links=len(inp.links))
+    a = ms.Elph(ms.twin_ops(), 8, 'hadamard')
+    b = ms.copy_state(a, ms.Elph(ms.twin_ops(), 8, 'hadamard'))
+    ta, tb = ms.sgd_steps(a, batch), ms.sgd_steps(b, batch)
+    assert len(ta) == 3 and all(ms.differing(x, y) == [] for x, y in zip(ta, tb))
+    assert ms.differing(ta[0], ta[1]) != []
+    flipped = copy.copy(ta[2])
+    flipped['loss'] = (ta[2]['loss'].view(torch.int32) ^ 1).view(torch.float32)
+    assert ms.differing(flipped, ta[2]) == ['loss: 1 of 1 elements differ, max |difference| ' + f'{float((flipped["loss"].double() - ta[2]["loss"].double()).abs()):.3e}']
+
+
+@pytest.mark.parametrize('module', ['gcn', 'aggr'])
+def test_identity_of_an_inference_tensor(module):
+    """a tensor made under torch.inference_mode() has no version counter: _identity must return, keyed on object, address and
+    shape, and _same must tell the same object from another of equal content"""
+    import importlib
+    m = importlib.import_module('subgraph_sketching_amd.' + module)
+    with torch.inference_mode():
+        t = torch.arange(6).view(2, 3)
+        u = t.clone()
+    assert t.is_inference()
+    with pytest.raises(RuntimeError):
+        t._version
+    a, b, c = m._identity(t), m._identity(t), m._identity(u)
+    assert a[3] is None and a[1:3] == (t.data_ptr(), (2, 3))
+    assert m._same(a, b) and not m._same(a, c) and not m._same(a, None) and m._same(None, None) and m._identity(None) is None
+    # ordinary tensors keep the rule test_cache pins: the version counter is part of the key
+    o = torch.arange(6).view(2, 3)
+    before = m._identity(o)
+    assert before[3] == o._version and m._same(before, m._identity(o))
+    o[0, 0] = 5
+    assert not m._same(before, m._identity(o))
+    v = t.view(3, 2)  # another object over the same storage
+    assert not m._same(a, m._identity(v))
+    del u
+    assert c[0]() is None and not m._same(c, c)  # a dead tensor matches nothing, not even its own key
