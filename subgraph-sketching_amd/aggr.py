@@ -13,11 +13,10 @@ regular tier (one lane group walks the row) or the hub tier (one lane group per 
 `AggrGraph` is the plan, `aggregate` the differentiable product, `SAGEConv` / `GINConv` the layers with PyG's parameter names.
 There is no CPU fallback.
 """
-import weakref
-
 import torch
 
 from . import _native
+from ._plans import _PlanCache, check_edge_list, device_edge_list, finish_hubs, list_hubs, padded_rows
 from ._runtime import _compute_device, _ptr, _stream
 from .sign import group_ids_stable
 
@@ -45,19 +44,9 @@ class AggrGraph(object):
     builds = 0  # plans built so far (the layer cache's tests count them)
 
     def __init__(self, num_nodes, edge_index, edge_weight=None, hub_entries=None, device=None):
-        if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
-            raise ValueError('edge_index must be an int64 tensor [2, E]')
-        n = int(num_nodes)
-        if n < 1 or n >= 1 << 31:
-            raise ValueError(f'num_nodes must lie in [1, 2^31), got {num_nodes}')
-        E = edge_index.size(1)
+        n, E = check_edge_list(num_nodes, edge_index, edge_weight)
         if E >= 1 << 31:
             raise ValueError('edge lists of 2^31 edges or more are not supported')
-        if edge_weight is not None:
-            if not isinstance(edge_weight, torch.Tensor) or edge_weight.shape != (E,) or not edge_weight.is_floating_point():
-                raise ValueError('edge_weight must be a floating-point tensor [E]')
-            if edge_weight.requires_grad:
-                raise ValueError('edge_weight is not differentiable here: pass edge_weight.detach()')
         hub = DEFAULT_HUB_ENTRIES if hub_entries is None else hub_entries
         if isinstance(hub, bool) or not isinstance(hub, int) or hub < 1:
             raise ValueError(f'hub_entries must be a positive integer, got {hub_entries!r}')
@@ -65,47 +54,31 @@ class AggrGraph(object):
         if lib.ss_aggr_chunk() != AGGR_CHUNK:
             raise RuntimeError(f'the library sums chunks of {lib.ss_aggr_chunk()} entries, this module lists chunks of {AGGR_CHUNK}')
         device = torch.device(device) if device is not None else _compute_device(edge_index, edge_weight)  # (host tensors: the current GPU)
-        ei = edge_index.detach().to(device=device, copy=True).contiguous()
-        self.row, self.col = ei[0], ei[1]
-        self.w = None if edge_weight is None else edge_weight.detach().to(device=device, dtype=torch.float32, copy=True)
-        if E == 0:  # (kernels never dereference an empty edge list, but the pointers must exist)
-            self.row = self.col = torch.zeros(1, dtype=torch.int64, device=device)
-            self.w = None if self.w is None else torch.zeros(1, dtype=torch.float32, device=device)
+        ei, self.row, self.col, self.w, no_order = device_edge_list(edge_index, edge_weight, device, lambda E: None)  # (unit weights are never gathered)
         self.num_nodes, self.num_edges, self.device, self.hub_entries = n, E, device, hub
         err = torch.zeros(1, dtype=torch.int32, device=device)
         # negative ids: the groupings wrap them torch-style, PyG does not -- they are refused with the ones past the end
         bad = ((ei < 0) | (ei >= n)).any().to(torch.int64).reshape(1)
         cap = E // (hub + 1)  # a row of more than `hub` entries: there are at most this many
-        sides, totals = [], []
+        sides, lists, totals = [], [], []
         for ids, other in ((self.col, self.row), (self.row, self.col)):
             s = _Side()
             s.rowptr, s.order = group_ids_stable(ids[:E], n, err)
-            if E == 0:  # (an empty slice has no address)
-                s.order = torch.zeros(1, dtype=torch.int32, device=device)
+            if E == 0:
+                s.order = no_order
             s.other = other
             s.den = torch.empty(n, dtype=torch.float32, device=device)
             _native.check(lib.ss_aggr_degree(_ptr(s.rowptr), _ptr(s.order), _ptr(self.w), n, _ptr(s.den), _stream(device)), 'ss_aggr_degree')
-            # the hub rows ascending and where their chunks start, without a host read: a slot per possible hub, the spare one collects the rest
-            m = s.rowptr[1:] - s.rowptr[:-1]
-            is_hub = m > hub
-            slot = torch.where(is_hub, torch.cumsum(is_hub, 0) - 1, torch.full_like(m, cap))
-            rows = torch.zeros(cap + 1, dtype=torch.int32, device=device).scatter_(0, slot, torch.arange(n, dtype=torch.int32, device=device))
-            chunks = torch.zeros(cap + 1, dtype=torch.int64, device=device).scatter_(0, slot, (m + (AGGR_CHUNK - 1)) // AGGR_CHUNK)
-            chunks[cap] = 0
-            s.hub_rows, s.hub_chunk = rows, torch.zeros(cap + 1, dtype=torch.int64, device=device)
-            torch.cumsum(chunks[:cap], 0, out=s.hub_chunk[1:])
-            totals += [is_hub.sum().reshape(1), s.hub_chunk[-1:], chunks]
+            # the hub rows ascending and where their chunks start, without a host read
+            *listed, n_hubs, n_chunks = list_hubs(s.rowptr[1:] - s.rowptr[:-1], hub, AGGR_CHUNK, cap)
             sides.append(s)
+            lists.append(listed)
+            totals += [n_hubs, n_chunks]
         # (the one host read) the groupings' flag and the sign test, with the four totals the hub launches are sized by
-        flag, bad, h_t, c_t, h_s, c_s = torch.cat([err.to(torch.int64), bad, totals[0], totals[1], totals[3], totals[4]]).tolist()
-        for s, H, C, chunks in ((sides[0], h_t, c_t, totals[2]), (sides[1], h_s, c_s, totals[5])):
+        flag, bad, h_t, c_t, h_s, c_s = torch.cat([err.to(torch.int64), bad] + totals).tolist()
+        for s, listed, H, C in zip(sides, lists, (h_t, h_s), (c_t, c_s)):
             s.n_hubs, s.n_chunks = H, C
-            if C >= 1 << 31:
-                raise ValueError('the hub rows have 2^31 chunks or more')
-            s.chunk_hub = torch.repeat_interleave(torch.arange(H, dtype=torch.int32, device=device), chunks[:H], output_size=C) if H else \
-                torch.zeros(1, dtype=torch.int32, device=device)
-            s.hub_rows = s.hub_rows[:max(H, 1)].contiguous()
-            s.hub_chunk = s.hub_chunk[:H + 1].to(torch.int32)
+            s.hub_rows, s.hub_chunk, s.chunk_hub = finish_hubs(*listed, H, C)
         self.target, self.source = sides
         if flag or bad:  # (the plan is complete all the same: the kernels do not follow such an id)
             raise IndexError('edge_index refers to nodes outside [0, num_nodes)')
@@ -124,27 +97,27 @@ class AggrGraph(object):
         n, F = self.num_nodes, x.size(1)
         if F == 0:
             return torch.empty((n, F), dtype=torch.float32, device=self.device)
-        root_x = x if root_x is None else root_x
-        pad = (-F) % 4
-        if pad:
-            x = torch.nn.functional.pad(x, (0, pad))
-            root_x = x if root is None else torch.nn.functional.pad(root_x, (0, pad))
-        Fp = F + pad
         s = self.target if target else self.source
-        out = torch.empty((n, Fp), dtype=torch.float32, device=self.device)
         lib, stream = _native.lib(), _stream(self.device)
         den = s.den if mean else None
-        _native.check(lib.ss_aggr_rows(_ptr(s.rowptr), _ptr(s.order), _ptr(s.other), _ptr(self.w), n, self.hub_entries, _ptr(x), Fp, _ptr(gather_den),
-                                       _ptr(den), _ptr(root), _ptr(root_x) if root is not None else None, _ptr(out), stream), 'ss_aggr_rows')
-        if s.n_hubs:
-            ws_bytes = lib.ss_aggr_workspace_bytes(s.n_chunks, Fp)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-            _native.check(lib.ss_aggr_hub_partials(_ptr(s.rowptr), _ptr(s.order), _ptr(s.other), _ptr(self.w), n, _ptr(s.hub_rows), _ptr(s.hub_chunk),
-                                                   _ptr(s.chunk_hub), s.n_hubs, s.n_chunks, _ptr(x), Fp, _ptr(gather_den), _ptr(ws), ws_bytes, stream),
-                          'ss_aggr_hub_partials')
-            _native.check(lib.ss_aggr_hub_finish(_ptr(s.hub_rows), _ptr(s.hub_chunk), s.n_hubs, s.n_chunks, n, _ptr(ws), ws_bytes, Fp, _ptr(den),
-                                                 _ptr(root), _ptr(root_x) if root is not None else None, _ptr(out), stream), 'ss_aggr_hub_finish')
-        return out[:, :F] if pad else out
+
+        def run(Fp, x, root_x):
+            if root is not None and root_x is None:
+                root_x = x
+            out = torch.empty((n, Fp), dtype=torch.float32, device=self.device)
+            _native.check(lib.ss_aggr_rows(_ptr(s.rowptr), _ptr(s.order), _ptr(s.other), _ptr(self.w), n, self.hub_entries, _ptr(x), Fp, _ptr(gather_den),
+                                           _ptr(den), _ptr(root), _ptr(root_x), _ptr(out), stream), 'ss_aggr_rows')
+            if s.n_hubs:
+                ws_bytes = lib.ss_aggr_workspace_bytes(s.n_chunks, Fp)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                _native.check(lib.ss_aggr_hub_partials(_ptr(s.rowptr), _ptr(s.order), _ptr(s.other), _ptr(self.w), n, _ptr(s.hub_rows),
+                                                       _ptr(s.hub_chunk), _ptr(s.chunk_hub), s.n_hubs, s.n_chunks, _ptr(x), Fp, _ptr(gather_den), _ptr(ws),
+                                                       ws_bytes, stream), 'ss_aggr_hub_partials')
+                _native.check(lib.ss_aggr_hub_finish(_ptr(s.hub_rows), _ptr(s.hub_chunk), s.n_hubs, s.n_chunks, n, _ptr(ws), ws_bytes, Fp, _ptr(den),
+                                                     _ptr(root), _ptr(root_x), _ptr(out), stream), 'ss_aggr_hub_finish')
+            return out
+
+        return padded_rows(run, F, x, root_x if root is not None else None)  # (without a root no root row is read, or padded)
 
 
 class _Aggregate(torch.autograd.Function):
@@ -198,33 +171,9 @@ def aggregate(x, graph, aggr='sum', flow='target', root=None):
     return _Aggregate.apply(x, root, graph, aggr == 'mean', flow == 'target')
 
 
-# the plan of the edge_index tensor seen last, shared by the layers of this module (gcn.py keeps its own): the convs of one forward do
-# one build.  Keyed on identity -- the same tensor object, storage address, shape and version counter -- never on content.
-_CACHE = {'key': None, 'graph': None}
-
-
-def _identity(t):
-    # (as gcn._identity) an inference tensor tracks no version -- reading t._version raises -- and is keyed on object, address and
-    # shape alone: outside inference mode torch refuses every in-place edit of it; an edit inside an inference_mode block goes unseen
-    if t is None:
-        return None
-    return (weakref.ref(t), t.data_ptr(), tuple(t.shape), None if t.is_inference() else t._version)
-
-
-def _same(a, b):
-    if a is None or b is None:
-        return a is b
-    return a[0]() is not None and a[0]() is b[0]() and a[1:] == b[1:]
-
-
-def _cached_graph(num_nodes, edge_index, device):
-    key = ((num_nodes, device), _identity(edge_index))
-    old = _CACHE['key']
-    if old is None or old[0] != key[0] or not _same(old[1], key[1]):
-        _CACHE['key'], _CACHE['graph'] = None, None
-        _CACHE['graph'] = AggrGraph(num_nodes, edge_index, device=device)
-        _CACHE['key'] = key
-    return _CACHE['graph']
+# the plan of the edge_index tensor seen last, shared by the layers of this module (gcn.py keeps its own: a GCNGraph and an AggrGraph
+# of one tensor are different plans)
+_CACHE = _PlanCache()
 
 
 def _graph_of(layer, x, edge_index, edge_weight):
@@ -241,7 +190,8 @@ def _graph_of(layer, x, edge_index, edge_weight):
         raise NotImplementedError(f"{layer}: PyG's layer takes no edge_weight; multiplicities come in through an AggrGraph")
     if hasattr(edge_index, 'adj_ptr') and hasattr(edge_index, 'edge_index'):  # an ExactSubgraphs / SampledSubgraphs batch
         return AggrGraph.from_subgraphs(edge_index)
-    return _cached_graph(x.size(0), edge_index, x.device if x.is_cuda else None)
+    device = x.device if x.is_cuda else None
+    return _CACHE.get((x.size(0), device), (edge_index,), lambda: AggrGraph(x.size(0), edge_index, device=device))
 
 
 class SAGEConv(torch.nn.Module):

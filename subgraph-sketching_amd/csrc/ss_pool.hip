@@ -7,10 +7,10 @@
 //            All words of a graph are distinct, so neither the tier nor the sorting network can show in the result.
 //   gather / scatter   move the selected rows (forward / backward of sort pool): a node is selected at most once -- no atomics.
 //   segment pool       one lane owns one output element and adds the graph's rows in ascending order (ss_spmm.hip's loop shape).
+// Rows are moved and added as the pieces of ss_feature_rows.hpp (a float4 per lane, or a single float), in its launch shape.
 //   centre pool        the product of the two root rows of each link, roots read on the device.
 // Offsets are 64-bit everywhere; ids that point outside their graph are not followed and set *err_flag.
-#include "ss_common.hpp"
-#include "ss_walks.hpp"
+#include "ss_feature_rows.hpp"
 
 namespace ss {
 
@@ -149,20 +149,6 @@ __global__ __launch_bounds__(kPoolThreads) void pool_select_kernel(const int64_t
     }
 }
 
-// ---- rows as float4 pieces (F % 4 == 0, 16-byte aligned bases) or single floats ---------------------------------------------------
-template <class V> __device__ __forceinline__ V pool_zero();
-template <> __device__ __forceinline__ float pool_zero<float>() { return 0.0f; }
-template <> __device__ __forceinline__ float4 pool_zero<float4>() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-__device__ __forceinline__ float pool_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float4 pool_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float pool_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float4 pool_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float pool_div(float a, float d) { return a / d; }
-__device__ __forceinline__ float4 pool_div(float4 a, float d) { return make_float4(a.x / d, a.y / d, a.z / d, a.w / d); }
-template <class V> __device__ __forceinline__ int pool_width(int F) { return F / (int)(sizeof(V) / sizeof(float)); }
-template <class V> __device__ __forceinline__ V pool_load(const float *row, int c) { return reinterpret_cast<const V *>(row)[c]; }
-template <class V> __device__ __forceinline__ void pool_store(float *row, int c, V v) { reinterpret_cast<V *>(row)[c] = v; }
-
 // which item (a row of `lanes` lanes) this lane works on, and its lane inside the item
 __device__ __forceinline__ int64_t pool_item(int lanes, int &cl)
 {
@@ -192,8 +178,8 @@ __global__ __launch_bounds__(256) void pool_gather_kernel(const int64_t *__restr
     }
     const float *__restrict__ src = x + (zero ? 0 : r0 + p) * F;
     float *__restrict__ dst = out + item * F;
-    const int W = pool_width<V>(F);
-    for (int c = cl; c < W; c += lanes) pool_store<V>(dst, c, zero ? pool_zero<V>() : pool_load<V>(src, c));
+    const int W = piece_width<V>(F);
+    for (int c = cl; c < W; c += lanes) piece_store<V>(dst, c, zero ? piece_zero<V>() : piece_load<V>(src, c));
 }
 
 // grad_x[rowptr[q] + perm[q, j]] = g[q, j] for perm >= 0 (the entry has cleared grad_x before)
@@ -214,8 +200,8 @@ __global__ __launch_bounds__(256) void pool_scatter_kernel(const int64_t *__rest
     }
     const float *__restrict__ src = g + item * F;
     float *__restrict__ dst = grad_x + (r0 + p) * F;
-    const int W = pool_width<V>(F);
-    for (int c = cl; c < W; c += lanes) pool_store<V>(dst, c, pool_load<V>(src, c));
+    const int W = piece_width<V>(F);
+    for (int c = cl; c < W; c += lanes) piece_store<V>(dst, c, piece_load<V>(src, c));
 }
 
 // out[q] = the rows of graph q added in ascending order from +0.0 by one lane per element (four rows requested before the first is
@@ -234,19 +220,19 @@ __global__ __launch_bounds__(256) void pool_segment_kernel(const int64_t *__rest
     }
     const int64_t n = r1 - r0;
     const float d = (float)(n > 1 ? n : 1);
-    const int W = pool_width<V>(F);
+    const int W = piece_width<V>(F);
     for (int c = cl; c < W; c += lanes) {
-        V acc = pool_zero<V>();
+        V acc = piece_zero<V>();
         int64_t t = r0;
         for (; t + 3 < r1; t += 4) {
             V r[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = pool_load<V>(x + (t + j) * F, c);
+            for (int j = 0; j < 4; ++j) r[j] = piece_load<V>(x + (t + j) * F, c);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc = pool_add(acc, r[j]);
+            for (int j = 0; j < 4; ++j) acc = piece_add(acc, r[j]);
         }
-        for (; t < r1; ++t) acc = pool_add(acc, pool_load<V>(x + t * F, c));
-        pool_store<V>(out + q * F, c, mean ? pool_div(acc, d) : acc);
+        for (; t < r1; ++t) acc = piece_add(acc, piece_load<V>(x + t * F, c));
+        piece_store<V>(out + q * F, c, mean ? piece_div(acc, d) : acc);
     }
 }
 
@@ -268,14 +254,14 @@ __global__ __launch_bounds__(256) void pool_segment_grad_kernel(const int64_t *_
     const int64_t q = inside ? lo - 1 : 0;
     const int64_t n = rowptr[q + 1] - rowptr[q];
     const float d = (float)(n > 1 ? n : 1);
-    const int W = pool_width<V>(F);
+    const int W = piece_width<V>(F);
     for (int c = cl; c < W; c += lanes) {
-        V v = pool_zero<V>();
+        V v = piece_zero<V>();
         if (inside) {
-            v = pool_load<V>(g + q * F, c);
-            if (mean) v = pool_div(v, d);
+            v = piece_load<V>(g + q * F, c);
+            if (mean) v = piece_div(v, d);
         }
-        pool_store<V>(grad_x + t * F, c, v);
+        piece_store<V>(grad_x + t * F, c, v);
     }
 }
 
@@ -305,9 +291,9 @@ __global__ __launch_bounds__(256) void pool_center_kernel(const int64_t *__restr
         if (cl == 0 && err_flag) *err_flag = 1;
         return;
     }
-    const int W = pool_width<V>(F);
+    const int W = piece_width<V>(F);
     for (int c = cl; c < W; c += lanes)
-        pool_store<V>(out + q * F, c, kind ? pool_zero<V>() : pool_mul(pool_load<V>(x + ra * F, c), pool_load<V>(x + rb * F, c)));
+        piece_store<V>(out + q * F, c, kind ? piece_zero<V>() : piece_mul(piece_load<V>(x + ra * F, c), piece_load<V>(x + rb * F, c)));
 }
 
 // grad_x[a] = g * x[b], grad_x[b] = g * x[a]; a == b: the sum of the two (the entry has cleared grad_x before)
@@ -323,50 +309,22 @@ __global__ __launch_bounds__(256) void pool_center_grad_kernel(const int64_t *__
     const int kind = pool_roots(rowptr, roots, q, T, ra, rb);
     if (kind < 0 && cl == 0 && err_flag) *err_flag = 1;
     if (kind != 0) return;
-    const int W = pool_width<V>(F);
+    const int W = piece_width<V>(F);
     for (int c = cl; c < W; c += lanes) {
-        const V gg = pool_load<V>(g + q * F, c);
-        const V ga = pool_mul(gg, pool_load<V>(x + rb * F, c)), gb = pool_mul(gg, pool_load<V>(x + ra * F, c));
+        const V gg = piece_load<V>(g + q * F, c);
+        const V ga = piece_mul(gg, piece_load<V>(x + rb * F, c)), gb = piece_mul(gg, piece_load<V>(x + ra * F, c));
         if (ra == rb) {
-            pool_store<V>(grad_x + ra * F, c, pool_add(ga, gb));
+            piece_store<V>(grad_x + ra * F, c, piece_add(ga, gb));
         } else {
-            pool_store<V>(grad_x + ra * F, c, ga);
-            pool_store<V>(grad_x + rb * F, c, gb);
+            piece_store<V>(grad_x + ra * F, c, ga);
+            piece_store<V>(grad_x + rb * F, c, gb);
         }
     }
 }
 
-// the launch shape of `items` rows of F floats: float4 pieces when every base is 16-byte aligned and F % 4 == 0
-struct PoolShape {
-    bool vec;
-    int lanes;
-    int64_t blocks;
-};
-inline PoolShape pool_shape(int64_t items, int F, uintptr_t bases)
-{
-    PoolShape s;
-    s.vec = (F & 3) == 0 && (bases & 15) == 0;
-    s.lanes = pow2_ceil(s.vec ? F >> 2 : F);
-    s.lanes = s.lanes > kWave ? kWave : (s.lanes < 1 ? 1 : s.lanes);
-    const int per_block = (256 / kWave) * (kWave / s.lanes);
-    s.blocks = (items + per_block - 1) / per_block;
-    return s;
-}
 inline bool pool_sizes_ok(int64_t L, int64_t T, int F) { return L >= 0 && T >= 0 && F >= 0 && L < ((int64_t)1 << 31); }
 
 }  // namespace ss
-
-#define SS_POOL_LAUNCH(kernel, shape, ...)                                                                                        \
-    do {                                                                                                                          \
-        if ((shape).blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;                                                      \
-        if ((shape).vec)                                                                                                          \
-            hipLaunchKernelGGL(kernel<float4>, dim3((unsigned)(shape).blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__,    \
-                               (shape).lanes);                                                                                    \
-        else                                                                                                                      \
-            hipLaunchKernelGGL(kernel<float>, dim3((unsigned)(shape).blocks), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__,     \
-                               (shape).lanes);                                                                                    \
-        SS_LAUNCH_CHECK();                                                                                                        \
-    } while (0)
 
 extern "C" int ss_pool_sort_capacity(void) { return ss::kPoolCap; }
 
@@ -390,8 +348,8 @@ extern "C" int ss_pool_gather(const int64_t *rowptr, int64_t L, const int32_t *p
     if (!pool_sizes_ok(L, T, F) || k < 1) return SS_ERR_INVALID_ARG;
     if (!rowptr || !perm || (F > 0 && (!out || (T > 0 && !x)))) return SS_ERR_INVALID_ARG;
     if (L == 0 || F == 0) return SS_OK;
-    const PoolShape sh = pool_shape(L * k, F, (uintptr_t)x | (uintptr_t)out);
-    SS_POOL_LAUNCH(pool_gather_kernel, sh, rowptr, L, perm, (int)k, x, T, (int)F, out, err_flag);
+    const RowShape sh = row_shape(L * k, F, (uintptr_t)x | (uintptr_t)out);
+    SS_ROWS_LAUNCH(sh, pool_gather_kernel<float4>, pool_gather_kernel<float>, rowptr, L, perm, (int)k, x, T, (int)F, out, err_flag, sh.lanes);
     return SS_OK;
 }
 
@@ -403,8 +361,8 @@ extern "C" int ss_pool_scatter(const int64_t *rowptr, int64_t L, const int32_t *
     if (!rowptr || !perm || (F > 0 && ((T > 0 && !grad_x) || (L > 0 && !g)))) return SS_ERR_INVALID_ARG;
     if (T > 0 && F > 0 && hipMemsetAsync(grad_x, 0, (size_t)T * F * sizeof(float), (hipStream_t)stream) != hipSuccess) return SS_ERR_LAUNCH;
     if (L == 0 || F == 0 || T == 0) return SS_OK;
-    const PoolShape sh = pool_shape(L * k, F, (uintptr_t)g | (uintptr_t)grad_x);
-    SS_POOL_LAUNCH(pool_scatter_kernel, sh, rowptr, L, perm, (int)k, g, T, (int)F, grad_x, err_flag);
+    const RowShape sh = row_shape(L * k, F, (uintptr_t)g | (uintptr_t)grad_x);
+    SS_ROWS_LAUNCH(sh, pool_scatter_kernel<float4>, pool_scatter_kernel<float>, rowptr, L, perm, (int)k, g, T, (int)F, grad_x, err_flag, sh.lanes);
     return SS_OK;
 }
 
@@ -415,8 +373,8 @@ extern "C" int ss_segment_pool(const int64_t *rowptr, int64_t L, const float *x,
     if (!pool_sizes_ok(L, T, F)) return SS_ERR_INVALID_ARG;
     if (!rowptr || (F > 0 && ((L > 0 && !out) || (T > 0 && !x)))) return SS_ERR_INVALID_ARG;
     if (L == 0 || F == 0) return SS_OK;
-    const PoolShape sh = pool_shape(L, F, (uintptr_t)x | (uintptr_t)out);
-    SS_POOL_LAUNCH(pool_segment_kernel, sh, rowptr, L, x, T, (int)F, (int)(mean != 0), out, err_flag);
+    const RowShape sh = row_shape(L, F, (uintptr_t)x | (uintptr_t)out);
+    SS_ROWS_LAUNCH(sh, pool_segment_kernel<float4>, pool_segment_kernel<float>, rowptr, L, x, T, (int)F, (int)(mean != 0), out, err_flag, sh.lanes);
     return SS_OK;
 }
 
@@ -428,8 +386,8 @@ extern "C" int ss_segment_pool_grad(const int64_t *rowptr, int64_t L, const floa
     if (!rowptr || (F > 0 && ((T > 0 && !grad_x) || (L > 0 && !g)))) return SS_ERR_INVALID_ARG;
     if (T == 0 || F == 0) return SS_OK;
     if (L == 0) return hipMemsetAsync(grad_x, 0, (size_t)T * F * sizeof(float), (hipStream_t)stream) == hipSuccess ? SS_OK : SS_ERR_LAUNCH;
-    const PoolShape sh = pool_shape(T, F, (uintptr_t)g | (uintptr_t)grad_x);
-    SS_POOL_LAUNCH(pool_segment_grad_kernel, sh, rowptr, L, g, T, (int)F, (int)(mean != 0), grad_x);
+    const RowShape sh = row_shape(T, F, (uintptr_t)g | (uintptr_t)grad_x);
+    SS_ROWS_LAUNCH(sh, pool_segment_grad_kernel<float4>, pool_segment_grad_kernel<float>, rowptr, L, g, T, (int)F, (int)(mean != 0), grad_x, sh.lanes);
     return SS_OK;
 }
 
@@ -440,8 +398,8 @@ extern "C" int ss_center_pool(const int64_t *rowptr, int64_t L, const int32_t *r
     if (!pool_sizes_ok(L, T, F)) return SS_ERR_INVALID_ARG;
     if (!rowptr || (L > 0 && !roots) || (F > 0 && ((L > 0 && !out) || (T > 0 && !x)))) return SS_ERR_INVALID_ARG;
     if (L == 0 || F == 0) return SS_OK;
-    const PoolShape sh = pool_shape(L, F, (uintptr_t)x | (uintptr_t)out);
-    SS_POOL_LAUNCH(pool_center_kernel, sh, rowptr, L, roots, x, T, (int)F, out, err_flag);
+    const RowShape sh = row_shape(L, F, (uintptr_t)x | (uintptr_t)out);
+    SS_ROWS_LAUNCH(sh, pool_center_kernel<float4>, pool_center_kernel<float>, rowptr, L, roots, x, T, (int)F, out, err_flag, sh.lanes);
     return SS_OK;
 }
 
@@ -453,7 +411,7 @@ extern "C" int ss_center_pool_grad(const int64_t *rowptr, int64_t L, const int32
     if (!rowptr || (L > 0 && !roots) || (F > 0 && ((T > 0 && (!grad_x || !x)) || (L > 0 && !g)))) return SS_ERR_INVALID_ARG;
     if (T > 0 && F > 0 && hipMemsetAsync(grad_x, 0, (size_t)T * F * sizeof(float), (hipStream_t)stream) != hipSuccess) return SS_ERR_LAUNCH;
     if (L == 0 || F == 0 || T == 0) return SS_OK;
-    const PoolShape sh = pool_shape(L, F, (uintptr_t)x | (uintptr_t)g | (uintptr_t)grad_x);
-    SS_POOL_LAUNCH(pool_center_grad_kernel, sh, rowptr, L, roots, x, g, T, (int)F, grad_x, err_flag);
+    const RowShape sh = row_shape(L, F, (uintptr_t)x | (uintptr_t)g | (uintptr_t)grad_x);
+    SS_ROWS_LAUNCH(sh, pool_center_grad_kernel<float4>, pool_center_grad_kernel<float>, rowptr, L, roots, x, g, T, (int)F, grad_x, err_flag, sh.lanes);
     return SS_OK;
 }

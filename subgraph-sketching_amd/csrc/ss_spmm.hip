@@ -7,8 +7,7 @@
 // (F = 128: two rows per wave).  HBM-bound gather of (E + N) feature rows -- the same shape as the MinHash table hop.
 // ss_gcn_spmm_t is the transposed product on the same body: GCNConv's propagation (reference models/elph.py:153-160, 214) and the
 // gradient of ss_sign_spmm, as ss_sign_spmm is its gradient (gcn.py).
-#include "ss_common.hpp"
-#include "ss_walks.hpp"
+#include "ss_feature_rows.hpp"
 
 namespace ss {
 
@@ -16,12 +15,10 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(const int64_t *__restric
                                                         const float *__restrict__ val, int64_t N, const float *__restrict__ x, int F,
                                                         float *__restrict__ out, int lanes_per_row)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int rows_per_wave = kWave / lanes_per_row;
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    const int64_t i = wave * rows_per_wave + lane / lanes_per_row;
-    if (i >= N) return;
-    const int cl = lane % lanes_per_row;
+    const RowGroup rg = row_group(lanes_per_row, N);
+    const int64_t i = rg.item_raw;
+    if (i >= N) return;  // (no shuffles here: a row group past the end simply leaves)
+    const int cl = rg.cl;
     const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
     const int CF = F >> 2;  // float4 chunks per row
     for (int c = cl; c < CF; c += lanes_per_row) {
@@ -36,20 +33,11 @@ __global__ __launch_bounds__(256) void spmm_rows_kernel(const int64_t *__restric
                 r[k] = *reinterpret_cast<const float4 *>(x + (int64_t)col[e + k] * F + 4 * c);
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc.x += r[k].x * w[k];
-                acc.y += r[k].y * w[k];
-                acc.z += r[k].z * w[k];
-                acc.w += r[k].w * w[k];
-            }
+            for (int k = 0; k < 4; ++k) acc = piece_add(acc, piece_mul(r[k], w[k]));
         }
         for (; e < e1; ++e) {
             const float w = val[e];
-            const float4 r = *reinterpret_cast<const float4 *>(x + (int64_t)col[e] * F + 4 * c);
-            acc.x += r.x * w;
-            acc.y += r.y * w;
-            acc.z += r.z * w;
-            acc.w += r.w * w;
+            acc = piece_add(acc, piece_mul(piece_load<float4>(x + (int64_t)col[e] * F, c), w));
         }
         *reinterpret_cast<float4 *>(out + i * F + 4 * c) = acc;
     }
@@ -155,6 +143,9 @@ __global__ __launch_bounds__(256) void sign_spmm_kernel(const int64_t *__restric
                                                         const GcnScan *__restrict__ scan)
 {
     const bool unit = scan->not_unit == 0;  // (uniform) all weights are 1: w[e] need not be gathered (a 64-byte sector per entry)
+    // (row_group()'s preamble and gather_sum()'s loop of ss_feature_rows.hpp, written out: this kernel walks a hub row of the GCN product
+    // as ONE serial stretch, and that loop answered the shared forms, whose hot loop has the same instructions, with 0.5 and 2.5 - 5 %
+    // on the rank^-0.9 graph -- profiles/feature_rows_refactor.txt)
     const int lane = threadIdx.x & (kWave - 1);
     const int rows_per_wave = kWave / lanes_per_row;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
@@ -187,27 +178,19 @@ __global__ __launch_bounds__(256) void sign_spmm_kernel(const int64_t *__restric
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int src = base + (k0 + k < lanes_per_row ? k0 + k : 0);
-                    const int64_t cj = ((int64_t)__shfl((int)(my_c >> 32), src) << 32) | (uint32_t)__shfl((int)my_c, src);
+                    const int64_t cj = shfl64(my_c, src);
                     nw[k] = __shfl(my_nw, src);
                     use[k] = k0 + k < n ? __shfl(my_use, src) : 0;
                     r[k] = *reinterpret_cast<const float4 *>(x + (use[k] ? cj : i) * F + 4 * c);
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (use[k]) {
-                        a.x += r[k].x * nw[k];
-                        a.y += r[k].y * nw[k];
-                        a.z += r[k].z * nw[k];
-                        a.w += r[k].w * nw[k];
-                    }
+                    if (use[k]) a = piece_add(a, piece_mul(r[k], nw[k]));
             }
         }
         const float nl = di * loop_w[i] * di;
         const float4 rs = *reinterpret_cast<const float4 *>(x + i * F + 4 * c);
-        a.x += rs.x * nl;
-        a.y += rs.y * nl;
-        a.z += rs.z * nl;
-        a.w += rs.w * nl;
+        a = piece_add(a, piece_mul(rs, nl));
         if (i_raw < N && cbase + cl < CF) *reinterpret_cast<float4 *>(out + i * F + 4 * c) = a;
     }
 }
@@ -221,12 +204,9 @@ extern "C" int ss_spmm_csr(const int64_t *rowptr, const int32_t *col, const floa
     if (N < 0 || F <= 0 || (F & 3) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
     if (N == 0) return SS_OK;
     if (!rowptr || !col || !val || !x || !out) return SS_ERR_INVALID_ARG;
-    int lanes = pow2_ceil(F >> 2);
-    if (lanes > kWave) lanes = kWave;
-    const int rows_per_block = (256 / kWave) * (kWave / lanes);
-    const int64_t blocks = (N + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(spmm_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, N, x, (int)F, out,
-                       lanes);
+    const RowShape sh = row_shape(N, F, 0);
+    hipLaunchKernelGGL(spmm_rows_kernel, dim3((unsigned)sh.blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, N, x, (int)F,
+                       out, sh.lanes);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -280,12 +260,9 @@ extern "C" int ss_sign_spmm(const int64_t *rowptr_r, const int32_t *order_r, con
     if (N < 0 || F <= 0 || (F & 3) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
     if (N == 0) return SS_OK;
     if (!rowptr_r || !order_r || !col || !w || !dinv || !loop_w || !scan || !x || !out) return SS_ERR_INVALID_ARG;
-    int lanes = pow2_ceil(F >> 2);
-    if (lanes > kWave) lanes = kWave;
-    const int rows_per_block = (256 / kWave) * (kWave / lanes);
-    const int64_t blocks = (N + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(sign_spmm_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr_r, order_r, col, w, dinv, loop_w, N,
-                       x, (int)F, out, lanes, reinterpret_cast<const GcnScan *>(scan));
+    const RowShape sh = row_shape(N, F, 0);
+    hipLaunchKernelGGL(sign_spmm_kernel<false>, dim3((unsigned)sh.blocks), dim3(256), 0, (hipStream_t)stream, rowptr_r, order_r, col, w, dinv, loop_w, N,
+                       x, (int)F, out, sh.lanes, reinterpret_cast<const GcnScan *>(scan));
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -300,12 +277,9 @@ extern "C" int ss_gcn_spmm_t(const int64_t *rowptr_c, const int32_t *order_c, co
     if (N < 0 || F <= 0 || (F & 3) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
     if (N == 0) return SS_OK;
     if (!rowptr_c || !order_c || !row || !w || !dinv || !loop_w || !scan || !x || !out) return SS_ERR_INVALID_ARG;
-    int lanes = pow2_ceil(F >> 2);
-    if (lanes > kWave) lanes = kWave;
-    const int rows_per_block = (256 / kWave) * (kWave / lanes);
-    const int64_t blocks = (N + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(sign_spmm_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr_c, order_c, row, w, dinv, loop_w, N,
-                       x, (int)F, out, lanes, reinterpret_cast<const GcnScan *>(scan));
+    const RowShape sh = row_shape(N, F, 0);
+    hipLaunchKernelGGL(sign_spmm_kernel<true>, dim3((unsigned)sh.blocks), dim3(256), 0, (hipStream_t)stream, rowptr_c, order_c, row, w, dinv, loop_w, N,
+                       x, (int)F, out, sh.lanes, reinterpret_cast<const GcnScan *>(scan));
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

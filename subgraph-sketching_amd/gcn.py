@@ -13,11 +13,11 @@ backward are reproducible bit for bit (no float atomics) and equal the sequentia
 differentiable product; `GCNConv` the layer with PyG's parameter names.  There is no CPU fallback.
 """
 import math
-import weakref
 
 import torch
 
 from . import _native
+from ._plans import _PlanCache, check_edge_list, device_edge_list, padded_rows
 from ._runtime import _compute_device, _ptr, _stream
 from .sign import group_ids_stable
 
@@ -32,28 +32,11 @@ class GCNGraph(object):
     builds = 0  # plans built so far (the layer cache's tests count them)
 
     def __init__(self, num_nodes, edge_index, edge_weight=None, device=None):
-        if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.dtype != torch.int64:
-            raise ValueError('edge_index must be an int64 tensor [2, E]')
-        n = int(num_nodes)
-        if n < 1 or n >= 1 << 31:
-            raise ValueError(f'num_nodes must lie in [1, 2^31), got {num_nodes}')
-        E = edge_index.size(1)
-        if edge_weight is not None:
-            if not isinstance(edge_weight, torch.Tensor) or edge_weight.shape != (E,) or not edge_weight.is_floating_point():
-                raise ValueError('edge_weight must be a floating-point tensor [E]')
-            if edge_weight.requires_grad:
-                raise ValueError('edge_weight is not differentiable here: pass edge_weight.detach()')
+        n, E = check_edge_list(num_nodes, edge_index, edge_weight)
         lib = _native.lib()
         device = torch.device(device) if device is not None else _compute_device(edge_index, edge_weight)  # (host tensors: the current GPU)
-        ei = edge_index.detach().to(device=device, copy=True).contiguous()
-        self.row, self.col = ei[0], ei[1]
-        if edge_weight is None:
-            self.w = torch.ones(max(E, 1), dtype=torch.float32, device=device)
-        else:
-            self.w = edge_weight.detach().to(device=device, dtype=torch.float32, copy=True)
-        if E == 0:  # (kernels never dereference an empty edge list, but the pointers must exist)
-            self.w = torch.zeros(1, dtype=torch.float32, device=device)
-            self.row = self.col = torch.zeros(1, dtype=torch.int64, device=device)
+        ei, self.row, self.col, self.w, no_order = device_edge_list(edge_index, edge_weight, device,
+                                                                     lambda E: torch.ones(max(E, 1), dtype=torch.float32, device=device))
         self.num_nodes, self.num_edges, self.device = n, E, device
         err = torch.zeros(1, dtype=torch.int32, device=device)
         self.scan = torch.empty(lib.ss_gcn_scan_bytes(n), dtype=torch.uint8, device=device)
@@ -61,8 +44,8 @@ class GCNGraph(object):
                       'ss_gcn_scan_edges')
         self.rowptr_c, self.order_c = group_ids_stable(ei[1], n, err)
         self.rowptr_r, self.order_r = group_ids_stable(ei[0], n, err)
-        if E == 0:  # (an empty slice has no address)
-            self.order_c = self.order_r = torch.zeros(1, dtype=torch.int32, device=device)
+        if E == 0:
+            self.order_c = self.order_r = no_order
         self.dinv = torch.empty(n, dtype=torch.float32, device=device)
         self.loop_w = torch.empty(n, dtype=torch.float32, device=device)
         _native.check(lib.ss_gcn_degree(_ptr(self.rowptr_c), _ptr(self.order_c), _ptr(self.row), _ptr(self.w), n, _ptr(self.scan), _ptr(self.dinv),
@@ -78,18 +61,19 @@ class GCNGraph(object):
         n, F = self.num_nodes, x.size(1)
         if F == 0:
             return torch.empty((n, F), dtype=torch.float32, device=self.device)
-        pad = (-F) % 4
-        if pad:
-            x = torch.nn.functional.pad(x, (0, pad))
-        out = torch.empty((n, F + pad), dtype=torch.float32, device=self.device)
         lib = _native.lib()
-        if target:
-            _native.check(lib.ss_gcn_spmm_t(_ptr(self.rowptr_c), _ptr(self.order_c), _ptr(self.row), _ptr(self.w), _ptr(self.dinv), _ptr(self.loop_w),
-                                            _ptr(self.scan), n, _ptr(x), F + pad, _ptr(out), _stream(self.device)), 'ss_gcn_spmm_t')
-        else:
-            _native.check(lib.ss_sign_spmm(_ptr(self.rowptr_r), _ptr(self.order_r), _ptr(self.col), _ptr(self.w), _ptr(self.dinv), _ptr(self.loop_w),
-                                           _ptr(self.scan), n, _ptr(x), F + pad, _ptr(out), _stream(self.device)), 'ss_sign_spmm')
-        return out[:, :F] if pad else out
+
+        def run(Fp, x):
+            out = torch.empty((n, Fp), dtype=torch.float32, device=self.device)
+            if target:
+                _native.check(lib.ss_gcn_spmm_t(_ptr(self.rowptr_c), _ptr(self.order_c), _ptr(self.row), _ptr(self.w), _ptr(self.dinv), _ptr(self.loop_w),
+                                                _ptr(self.scan), n, _ptr(x), Fp, _ptr(out), _stream(self.device)), 'ss_gcn_spmm_t')
+            else:
+                _native.check(lib.ss_sign_spmm(_ptr(self.rowptr_r), _ptr(self.order_r), _ptr(self.col), _ptr(self.w), _ptr(self.dinv), _ptr(self.loop_w),
+                                               _ptr(self.scan), n, _ptr(x), Fp, _ptr(out), _stream(self.device)), 'ss_sign_spmm')
+            return out
+
+        return padded_rows(run, F, x)
 
 
 class _Propagate(torch.autograd.Function):
@@ -119,35 +103,7 @@ def gcn_propagate(x, graph, flow='target'):
     return _Propagate.apply(x, graph, flow == 'target')
 
 
-# the plan of the edge_index tensor seen last, shared by every layer: the h convs of one forward do one build.  Keyed on identity --
-# the same tensor object, storage address, shape and version counter (an in-place edit bumps it) -- never on content.
-_CACHE = {'key': None, 'graph': None}
-
-
-def _identity(t):
-    # A tensor made under torch.inference_mode() tracks no version (reading t._version raises).  It is still cached, keyed on
-    # object, address and shape alone: outside inference mode torch refuses every in-place edit of it, so there the key cannot go
-    # stale; an edit INSIDE an inference_mode block goes unseen -- pass a GCNGraph, or a fresh tensor, after such an edit.  Not
-    # caching it instead would rebuild the plan in every conv of an evaluation loop, which is what the cache exists to avoid.
-    if t is None:
-        return None
-    return (weakref.ref(t), t.data_ptr(), tuple(t.shape), None if t.is_inference() else t._version)
-
-
-def _same(a, b):
-    if a is None or b is None:
-        return a is b
-    return a[0]() is not None and a[0]() is b[0]() and a[1:] == b[1:]
-
-
-def _cached_graph(num_nodes, edge_index, edge_weight, device):
-    key = ((num_nodes, device), _identity(edge_index), _identity(edge_weight))
-    old = _CACHE['key']
-    if old is None or old[0] != key[0] or not _same(old[1], key[1]) or not _same(old[2], key[2]):
-        _CACHE['key'], _CACHE['graph'] = None, None
-        _CACHE['graph'] = GCNGraph(num_nodes, edge_index, edge_weight, device=device)
-        _CACHE['key'] = key
-    return _CACHE['graph']
+_CACHE = _PlanCache()  # the plan of the edge_index tensor seen last, shared by every layer: the h convs of one forward do one build
 
 
 class GCNConv(torch.nn.Module):
@@ -190,7 +146,9 @@ class GCNConv(torch.nn.Module):
         else:
             if not isinstance(x, torch.Tensor) or x.dim() != 2:
                 raise ValueError('x must be a float32 tensor [N, in_channels]')
-            graph = _cached_graph(x.size(0), edge_index, edge_weight, x.device if x.is_cuda else None)
+            device = x.device if x.is_cuda else None
+            graph = _CACHE.get((x.size(0), device), (edge_index, edge_weight),
+                               lambda: GCNGraph(x.size(0), edge_index, edge_weight, device=device))
         out = gcn_propagate(torch.nn.functional.linear(x, self.lin.weight), graph)  # PyG's order: transform, then propagate
         return out if self.bias is None else out + self.bias
 

@@ -24,6 +24,7 @@ curr_links) builds ONE LinkBatch and passes it to every call.
 import torch
 
 from . import _native
+from ._plans import finish_hubs, list_hubs
 from ._runtime import _DeferredErrors, _compute_device, _ptr, _stream
 from .sign import group_ids_stable
 
@@ -105,25 +106,15 @@ class LinkBatch(object):
         place = torch.where(touched, pos, torch.full_like(pos, cap_m))
         nodes = torch.zeros(cap_m + 1, dtype=torch.int64, device=device).scatter_(0, place, ids)
         starts = torch.zeros(cap_m + 1, dtype=torch.int64, device=device).scatter_(0, place, full[:-1])
-        # the hub rows likewise (as AggrGraph lists them), named by their position in `nodes`
-        cap = 2 * L // (hub + 1)  # a row of more than `hub` slots: there are at most this many
-        is_hub = m > hub
-        place = torch.where(is_hub, torch.cumsum(is_hub, 0) - 1, torch.full_like(m, cap))
-        rows = i32(cap + 1).scatter_(0, place, pos.to(torch.int32))
-        chunks = torch.zeros(cap + 1, dtype=torch.int64, device=device).scatter_(0, place, (m + (LINK_CHUNK - 1)) // LINK_CHUNK)
-        chunks[cap] = 0
-        hub_chunk = torch.zeros(cap + 1, dtype=torch.int64, device=device)
-        torch.cumsum(chunks[:cap], 0, out=hub_chunk[1:])
+        # the hub rows likewise, named by their position in `nodes`; a row of more than `hub` slots: there are at most 2L // (hub + 1)
+        *listed, n_hubs, n_chunks = list_hubs(m, hub, LINK_CHUNK, 2 * L // (hub + 1), names=pos.to(torch.int32))
         # (the one host read) the grouping's flag and the sign test, M, and the two totals the hub launches are sized by
-        flag, bad, M, H, C = torch.cat([err.to(torch.int64), bad, touched.sum().reshape(1), is_hub.sum().reshape(1), hub_chunk[-1:]]).tolist()
-        if C >= 1 << 31:
-            raise ValueError('the hub rows have 2^31 chunks or more')
+        flag, bad, M, H, C = torch.cat([err.to(torch.int64), bad, touched.sum().reshape(1), n_hubs, n_chunks]).tolist()
+        hub_lists = finish_hubs(*listed, H, C)
         self.num_touched, self.n_hubs, self.n_chunks = M, H, C
         self.nodes = nodes[:M].contiguous()
         self.rowptr = torch.cat([starts[:M], full[-1:]])
-        self.chunk_hub = torch.repeat_interleave(torch.arange(H, dtype=torch.int32, device=device), chunks[:H], output_size=C) if H else i32(1)
-        self.hub_rows = rows[:max(H, 1)].contiguous()
-        self.hub_chunk = hub_chunk[:H + 1].to(torch.int32)
+        self.hub_rows, self.hub_chunk, self.chunk_hub = hub_lists
         if flag or bad:
             raise IndexError('links refers to nodes outside [0, num_nodes)')
         LinkBatch.builds += 1

@@ -15,6 +15,7 @@ reference calls, for callers that want them separately.
 import torch
 
 from . import _native
+from ._plans import padded_rows
 from .hashing import _compute_device, _ptr, _stream
 
 
@@ -66,22 +67,21 @@ def spmm(index, value, m, n, matrix):
     device = _compute_device(matrix, index)
     home = matrix.device
     x = matrix.to(device=device, dtype=torch.float32).contiguous()
-    F = x.size(1)
-    pad = (-F) % 4
-    if pad:
-        x = torch.nn.functional.pad(x, (0, pad))
     row = index[0].to(device).contiguous()
     rowptr, order = group_ids_stable(row, m)  # CSR order == the reference's edge order inside every row
     order = order.to(torch.int64)
     col = index[1].to(device)[order].to(torch.int32).contiguous()
     val = value.to(device=device, dtype=torch.float32)[order].contiguous()
-    out = torch.empty((m, F + pad), dtype=torch.float32, device=device)
     if col.numel() == 0:
         col = torch.zeros(1, dtype=torch.int32, device=device)
         val = torch.zeros(1, dtype=torch.float32, device=device)
-    _native.check(_native.lib().ss_spmm_csr(_ptr(rowptr), _ptr(col), _ptr(val), m, _ptr(x), F + pad, _ptr(out), _stream(device)),
-                  'ss_spmm_csr')
-    out = out[:, :F] if pad else out
+
+    def run(Fp, x):
+        out = torch.empty((m, Fp), dtype=torch.float32, device=device)
+        _native.check(_native.lib().ss_spmm_csr(_ptr(rowptr), _ptr(col), _ptr(val), m, _ptr(x), Fp, _ptr(out), _stream(device)), 'ss_spmm_csr')
+        return out
+
+    out = padded_rows(run, x.size(1), x)
     return out if home == device else out.to(home)
 
 
@@ -94,10 +94,6 @@ def generate_sign_features(x, edge_index, edge_weight, sign_k):
     device = _compute_device(x, edge_index)
     home = x.device
     xd = x.to(device=device, dtype=torch.float32).contiguous()
-    F = xd.size(1)
-    pad = (-F) % 4
-    if pad:
-        xd = torch.nn.functional.pad(xd, (0, pad))
     row = edge_index[0].to(device).contiguous()
     col = edge_index[1].to(device).contiguous()
     w = edge_weight.to(device=device, dtype=torch.float32).contiguous()
@@ -112,18 +108,22 @@ def generate_sign_features(x, edge_index, edge_weight, sign_k):
     rowptr_r, order_r = group_ids_stable(row, n, err)  # for the product: scatter-add over `row` in edge order
     dinv = torch.empty(n, dtype=torch.float32, device=device)
     loop_w = torch.empty(n, dtype=torch.float32, device=device)
-    out = torch.empty((n, F + pad), dtype=torch.float32, device=device)
     if E == 0:
         row = col = torch.zeros(1, dtype=torch.int64, device=device)
     _native.check(lib.ss_gcn_degree(_ptr(rowptr_c), _ptr(order_c), _ptr(row), _ptr(w), n, _ptr(scan), _ptr(dinv), _ptr(loop_w), _stream(device)),
                   'ss_gcn_degree')
-    _native.check(lib.ss_sign_spmm(_ptr(rowptr_r), _ptr(order_r), _ptr(col), _ptr(w), _ptr(dinv), _ptr(loop_w), _ptr(scan), n, _ptr(xd), F + pad, _ptr(out),
-                                   _stream(device)), 'ss_sign_spmm')
+
+    def run(Fp, xp):
+        out = torch.empty((n, Fp), dtype=torch.float32, device=device)
+        _native.check(lib.ss_sign_spmm(_ptr(rowptr_r), _ptr(order_r), _ptr(col), _ptr(w), _ptr(dinv), _ptr(loop_w), _ptr(scan), n, _ptr(xp), Fp, _ptr(out),
+                                       _stream(device)), 'ss_sign_spmm')
+        return out
+
+    ax = padded_rows(run, xd.size(1), xd)
     # (the one host read of the chain) the groupings' flag, or ss_gcn_scan_edges' own word for ids outside [0, N) -- negative ones
     # included, which the groupings wrap torch-style; the product kernel does not follow an id out of range
     if int((err + scan[4:8].view(torch.int32)).item()):
         raise IndexError('edge_index refers to nodes outside [0, num_nodes)')
-    ax = out[:, :F] if pad else out
     ax = ax if home == device else ax.to(home)
     if sign_k == 0:
         return ax

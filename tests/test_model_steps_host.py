@@ -2,7 +2,7 @@
 the plain-torch forms against dense float64 matrices and torch.autograd.gradcheck on graphs of 5 to 12 nodes; the twin Functions'
 backward against autograd through the plain forms on the ELPH-shaped model at a reduced size; e_32 > 0 for every compared tensor at
 the shapes and seeds the GPU test uses (the twin model standing in for the package model: it has the bits the GPU run must have);
-and the CPU part of the inference-tensor regression of gcn._identity / aggr._identity."""
+and the CPU part of the inference-tensor regression of _plans._identity (the key of the plan caches of gcn and aggr)."""
 import copy
 import types
 
@@ -241,12 +241,10 @@ def test_sgd_steps_and_deepcopy_repeat_on_the_twin():
     assert ms.differing(flipped, ta[2]) == ['loss: 1 of 1 elements differ, max |difference| ' + f'{float((flipped["loss"].double() - ta[2]["loss"].double()).abs()):.3e}']
 
 
-@pytest.mark.parametrize('module', ['gcn', 'aggr'])
-def test_identity_of_an_inference_tensor(module):
-    """a tensor made under torch.inference_mode() has no version counter: _identity must return, keyed on object, address and
-    shape, and _same must tell the same object from another of equal content"""
-    import importlib
-    m = importlib.import_module('subgraph_sketching_amd.' + module)
+def test_identity_of_an_inference_tensor():
+    """a tensor made under torch.inference_mode() has no version counter: _identity (the one key of the plan caches of gcn and aggr)
+    must return, keyed on object, address and shape, and _same must tell the same object from another of equal content"""
+    from subgraph_sketching_amd import _plans as m
     with torch.inference_mode():
         t = torch.arange(6).view(2, 3)
         u = t.clone()
