@@ -226,6 +226,19 @@ int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, const uint6
                        uint32_t *mh2_out, int32_t p, uint8_t *hll1, float *cards1_out, uint8_t *hll2_out, float *cards2_out,
                        int64_t cards_stride, const ss_hll_params *prm, void *stream);
 
+/* ss_fused_hop_stage with a workspace for the RECORDS form of its fused kernel (csrc/ss_fused_hop.hip): records, device uint32[N][16]
+ * (nullable: then this is ss_fused_hop_stage), and num_edges = E, the length of graph->col (negative: unknown).  Where the stage
+ * computes the hop-1 HLL table itself (cards1_out != NULL) for the whole graph on one device, the table fits a buffer descriptor
+ * and the graph lists no hub rows (hub_rows == NULL) and E + N <= 24 * N, the HLL first hop also writes a 64-byte code record per node -- dword l = code(l) | code(l + 16) << 16 of the
+ * node's neighbours l and l + 16 (its own id among them as the implicit self loop), code = register << 2 | rank << 10, 0 = none;
+ * 0xFFFFFFFF in every dword of a node with more than 32 neighbours or a hub row: "read the dense row" -- and the fused kernel builds
+ * the hop-2 HLL rows by scatter-max of those codes instead of folding dense 256-byte rows.  Same tables and cardinalities, bit for
+ * bit; `records` holds the records afterwards (contents unspecified where the dense form ran).  SS_FUSED_RECORDS in the environment,
+ * read at every call: 0 forces the dense form, 1 the records form wherever it is legal whatever E. */
+int ss_fused_hop_stage_records(const ss_csr_graph *graph, const uint64_t *a, const uint64_t *b, int32_t P, uint32_t *mh1_out,
+                               uint32_t *mh2_out, int32_t p, uint8_t *hll1, float *cards1_out, uint8_t *hll2_out, float *cards2_out,
+                               int64_t cards_stride, const ss_hll_params *prm, uint32_t *records, int64_t num_edges, void *stream);
+
 /* HLL++ cardinality of n register rows.  Replaces ElphHashes.hll_count (+ _linearcounting,
  * _estimate_bias, _refine_hll_count_estimate; hashing.py:194-232).  regs: device uint8[n, m];
  * out: device fp32, element i written to out[i*out_stride]. */

@@ -57,10 +57,13 @@ constexpr int kHllRows = 4;  // (2, 6 and 8 measured the same 25 us on the bench
 // PPL only matters to the leading workgroups (hub units, ss_hub.hpp): with hub_mh_out they also serve the hop-1 MinHash table
 // (P = 64 * PPL) -- ss_fused_hop_stage's row kernel has no register to spare for them.  The register allocator is held to the 64
 // VGPRs of the row path's eight wavefronts per SIMD; what the MinHash units spill they spill on their own, cold, path.
-template <int PPL>
+// REC: every lane group also stores its rows' code records (hll_first_hop_row16; `records`: uint32[N][16]) -- an instantiation of its
+// own, so that the kernel without records keeps its registers.
+template <int PPL, bool REC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void hll_first_hop_kernel(
     GraphArgs g, int p, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm, bool skip_hubs,
-    int hub_blocks, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ hub_mh_out)
+    int hub_blocks, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ hub_mh_out,
+    uint32_t *__restrict__ records)
 {
     // only the linear-counting table is staged (this kernel is only launched for p = 8: 257 entries): a hop-1 row leaves the
     // linear-counting range at 147 neighbours, and those few read raw / bias from global memory.  17 KB of LDS and 60 VGPRs
@@ -128,8 +131,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void h
         const int deg = degs[r];
         const bool hub = skip_hubs && deg > g.hub_threshold;
         const int total = hub ? 0 : deg + (i < n_self ? 1 : 0);
-        hll_first_hop_row16<true>(row, g.col + rbs[r], deg, total, i, nid0[r], always_valid, p, ok && !hub, hll_out, cards_out, cards_stride, est,
-                                  want_cards, l, g.mir);
+        if constexpr (REC)  // (no mirrors: the records form belongs to the unsharded build)
+            hll_first_hop_row16<false, true>(row, g.col + rbs[r], deg, total, i, nid0[r], always_valid, p, ok && !hub, hll_out, cards_out,
+                                             cards_stride, est, want_cards, l, g.mir, records, ok && hub);
+        else
+            hll_first_hop_row16<true>(row, g.col + rbs[r], deg, total, i, nid0[r], always_valid, p, ok && !hub, hll_out, cards_out, cards_stride, est,
+                                      want_cards, l, g.mir);
     }
 }
 
@@ -195,25 +202,34 @@ int launch_first_hop_mh(const GraphArgs &g, const uint64_t *a, const uint64_t *b
 // permutations a / b -- of the hop-1 MinHash table, ss_hub.hpp; 0: the caller launches first_hop_hub_kernel)
 template <int PPL>
 static int launch_hll_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
-                           bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, hipStream_t s)
+                           bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, hipStream_t s,
+                           uint32_t *records)
 {
     ProfileSpan span(s, SS_PROF_FIRST_HOP_HLL);
-    hipLaunchKernelGGL((hll_first_hop_kernel<PPL>), dim3((unsigned)((g.rows() + 16 * kHllRows - 1) / (16 * kHllRows) + lead)), dim3(256), 0, s, g,
-                       p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out);
+    const dim3 grid((unsigned)((g.rows() + 16 * kHllRows - 1) / (16 * kHllRows) + lead));
+    if (records)
+        hipLaunchKernelGGL((hll_first_hop_kernel<PPL, true>), grid, dim3(256), 0, s, g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a,
+                           b, hub_mh_out, records);
+    else
+        hipLaunchKernelGGL((hll_first_hop_kernel<PPL, false>), grid, dim3(256), 0, s, g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a,
+                           b, hub_mh_out, (uint32_t *)nullptr);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
 int launch_hll_first_hop_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
-                              bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, int P, hipStream_t s)
+                              bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, int P, hipStream_t s,
+                              uint32_t *records)
 {
-    if (lead == 0 || !hub_mh_out) return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, nullptr, nullptr, nullptr, s);
+    if (g.mir.n > 0) records = nullptr;  // (the records instantiation stores no mirrors; ss_fused_hop_stage_records never asks for both)
+    if (lead == 0 || !hub_mh_out)
+        return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, nullptr, nullptr, nullptr, s, records);
     lead *= 2;  // (a quarter for the HLL units, the rest for the MinHash units)
     switch (P / kWave) {
-        case 1: return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s);
-        case 2: return launch_hll_rows<2>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s);
-        case 3: return launch_hll_rows<3>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s);
-        default: return launch_hll_rows<4>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s);
+        case 1: return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
+        case 2: return launch_hll_rows<2>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
+        case 3: return launch_hll_rows<3>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
+        default: return launch_hll_rows<4>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
     }
 }
 

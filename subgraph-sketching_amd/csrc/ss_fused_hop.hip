@@ -27,6 +27,13 @@
 // they are hub units (ss_hub.hpp) hosted by the launches before and after this one -- not by this one: the kernel sits exactly at its
 // 96-VGPR budget, and a hub branch, whatever it contained, cost the row path 64 bytes of scratch and 30 us (round 4).
 // P = 64 * PPL, M = 256 (p = 8) only -- the shapes ss_first_hop has a kernel for.
+//
+// The RECORDS form of the HLL side (third template flag, with buffer posts only; "the records form" below): on sparse graphs without
+// hub rows the stage's HLL first hop also leaves a 64-byte code record per node, the posts fetch one dword of it per lane and slot, and
+// the fold is a scatter-max of (register, rank) codes into a 1 KB row image per lane group in LDS -- on the LDS pipe, which is idle
+// here, instead of the byte-wise max of mostly empty 256-byte rows on the VALU pipe, which is what the kernel waits for.  Same rows
+// bit for bit: a record that cannot hold its node's neighbourhood says so and that slot is folded from the dense row.  Which form a
+// launch takes is decided in ss_fused_hop_stage_records; the dense instantiations are the object code they were.
 #include <cstring>
 #include <type_traits>
 
@@ -98,6 +105,7 @@ __device__ __forceinline__ void hll_post(HllPosted &h, const HllSource &src, int
 // slot is not relied on: the fold masks the slots beyond a row's total in both forms.
 constexpr int kHllLds = 7;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 typedef __attribute__((address_space(1))) const uint32_t global_u32;
 typedef __attribute__((address_space(1))) const int64_t global_i64;
 
@@ -123,6 +131,116 @@ __device__ __forceinline__ void hll_fold(const HllPosted &h, u32x4 &ae, u32x4 &a
     for (int k = 0; k < kHllInFlight; ++k) hll_acc(ae, ao, h.x[k]);
 }
 
+// ---- the records form of the HLL side (REC) ---------------------------------------------------------------------------------------
+// A hop-1 HLL row of node j has at most deg(j) + 1 non-zero registers of 256, and the dense fold spends VALU issue slots -- the one
+// thing this kernel is short of -- on the max of zeros.  In the records form the fold moves to the LDS pipe: the HLL first hop leaves a
+// 64-byte CODE RECORD per node (hll_first_hop_row16, ss_walks.hpp: up to 32 codes register << 2 | rank << 10, two per dword), a post
+// fetches ONE dword per lane -- lane c of a group dword c of neighbour t's record, 64 contiguous bytes per group, one VGPR per slot --
+// and after the MinHash rows every lane scatters its two codes into its group's private 1 KB row image with LDS atomic max, exactly as
+// hll_first_hop_row16 builds a hop-1 row.  Lane c then packs registers 16c .. 16c + 15 of the image into the 16 bytes the dense fold
+// would have produced, and everything after it (rows beyond the posted slots, the statistics, the estimator, the stores) is the dense
+// form's code on the dense table.
+// Exact by construction: a record holds EVERY neighbour of its node or says so -- a node of more than 32 neighbours, and a hub row
+// the first hop left to the hub units, carries kRecordDense in every dword.  Lane 0 of a group sees dword 0 of the slot's record: a
+// flagged slot is folded from the node's dense row (byte-wise max into a dense accumulator that joins the packed image), and the flagged
+// lanes scatter nothing.
+// kRecSlots = 16 slots are posted, the ids a lane group hands out by DPP, two at a time: a pair of slots that none of the wavefront's
+// rows reaches is neither posted nor scattered (one scalar compare against the largest of the four totals; the odd slot of a pair
+// that is reached by half asks for the row N like every lane with nothing to fetch).
+// What a slot costs in VALU issue: the post is ONE instruction (the ids are shifted once per chunk, and v_or_b32 takes the DPP
+// broadcast as its operand); whether any record of the chunk is flagged is asked once, of the maximum over the slots (v_max3_u32,
+// half an instruction per slot), and the slot-by-slot test runs only then; a dword's first code is a compare (most dwords are empty,
+// and their lanes would all meet at register 0), the address and the rank; the second code -- neighbours 16 .. 31 of a node -- is
+// looked at only where some lane of the wavefront has one.
+constexpr int kRecSlots = kRow;
+
+__device__ __forceinline__ uint32_t buffer_load4(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_offset)
+{
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)byte_offset, 0, 0);
+}
+
+__device__ __forceinline__ void lds_max(uint32_t addr, uint32_t v)  // (no return value asked for: ds_max_u32, not ds_max_rtn_u32)
+{
+    __hip_atomic_fetch_max((lds_u32 *)(uintptr_t)addr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+// my_nb64 = 64 * the id the lane hands out (Ids::my_nb), c4 = 4 * (lane & 15): lane c fetches dword c of the record
+template <int T>
+__device__ __forceinline__ void rec_post(uint32_t (&x)[kRecSlots], __amdgpu_buffer_rsrc_t rec, int my_nb64, uint32_t c4, int reach)
+{
+    if constexpr (T < kRecSlots) {
+        if (T >= reach) return;  // scalar
+        x[T] = buffer_load4(rec, (uint32_t)row_bcast<T>(my_nb64) | c4);  // (the id N of a lane with nothing to fetch: zeros)
+        x[T + 1] = buffer_load4(rec, (uint32_t)row_bcast<T + 1>(my_nb64) | c4);
+        rec_post<T + 2>(x, rec, my_nb64, c4, reach);
+    }
+}
+
+// the largest dword among the posted slots: kRecordDense where a record is flagged
+template <int T>
+__device__ __forceinline__ void rec_max(const uint32_t (&x)[kRecSlots], int reach, uint32_t &mx)
+{
+    if constexpr (T < kRecSlots) {
+        if (T >= reach) return;  // scalar
+        mx = max(mx, max(x[T], x[T + 1]));
+        rec_max<T + 2>(x, reach, mx);
+    }
+}
+
+// the two codes of one dword into the image at LDS byte address `img` (1 KB-aligned: the word offset is OR-ed in)
+__device__ __forceinline__ void rec_scatter_codes(uint32_t v, uint32_t img)
+{
+    if (v) lds_max(img | (v & 0x3FCu), (v >> 10) & 63u);
+    // a scalar branch, which hipcc would merge into the lanes' condition: under an exec mask alone the three instructions of the
+    // second code issue for nobody
+    if (__any(v > 0xFFFFu)) {
+        asm volatile("");  // (keeps the two conditions apart)
+        if (v > 0xFFFFu) lds_max(img | ((v >> 16) & 0x3FCu), v >> 26);
+    }
+}
+
+// What a lane group needs of its row to fold a flagged slot: nb / deg / self_row, `bytes` = the row after the dense table's last
+struct RecRow {
+    const int32_t *nb;
+    int deg;
+    int64_t self_row;
+    uint32_t bytes;
+};
+
+// slot T of every lane group; img = the group's image, c16 = 16 * (lane & 15).  FLAGS (some record of the chunk is flagged): a slot
+// with a flagged record in any group also fetches chunk c of the flagged nodes' dense rows -- `bytes` for the other groups: zeros --
+// into the dense accumulator `dacc`, which joins the packed image at the end, and the lanes of a flagged record scatter nothing
+template <int T, bool FLAGS>
+__device__ __forceinline__ void rec_slot(uint32_t v, uint32_t img, const HllSource &src, const RecRow &w, uint32_t c16, u32x4 &dacc)
+{
+    if constexpr (FLAGS) {
+        // dword 0 of a record sits in lane 0 of its group
+        const bool dense = (uint32_t)row_bcast<0>((int)v) == kRecordDense;
+        if (__any(dense)) {
+            // (a flagged slot is a neighbour of the row: T < total.  Its id comes from the CSR again -- the lanes' ids left their
+            // register when the next chunk's arrived)
+            uint32_t off = w.bytes;
+            if (dense) off = ((T < w.deg ? (uint32_t)w.nb[T] : (uint32_t)w.self_row) << 8) | c16;
+            dacc = bytemax16(dacc, buffer_load16(src.rsrc, off));
+        }
+        if (!dense) rec_scatter_codes(v, img);
+    } else {
+        rec_scatter_codes(v, img);
+    }
+}
+
+template <int T, bool FLAGS>
+__device__ __forceinline__ void rec_scatter(const uint32_t (&x)[kRecSlots], uint32_t img, int reach, const HllSource &src, const RecRow &w,
+                                            uint32_t c16, u32x4 &dacc)
+{
+    if constexpr (T < kRecSlots) {
+        if (T >= reach) return;  // scalar: not posted either
+        rec_slot<T, FLAGS>(x[T], img, src, w, c16, dacc);
+        rec_slot<T + 1, FLAGS>(x[T + 1], img, src, w, c16, dacc);
+        rec_scatter<T + 2, FLAGS>(x, img, reach, src, w, c16, dacc);
+    }
+}
+
 // ---- the kernel: persistent, software-pipelined -------------------------------------------------------------------------------
 // Four or five wavefronts per SIMD are too few to hide the three dependent round trips at the head of a chunk (row
 // bounds -> neighbour ids -> HLL rows): a one-chunk-per-wavefront form of this kernel gained 6 % over the two separate launches
@@ -144,17 +262,19 @@ __device__ __forceinline__ void hll_fold(const HllPosted &h, u32x4 &ae, u32x4 &a
 // A second use of the register landings -- folded before the LAST MinHash row and sent out again for neighbours 14 .. 20 (ids from a
 // second id word per lane), coverage 21 -- needs the accumulators alive through that row's walk: 96 / 64 / 32 bytes of scratch with
 // 7 / 6 / 5 register landings and 197 / 177 / 154 us; with 4 (no scratch, coverage 15) 146 us, the same as without.  Not shipped.
-template <int PPL, bool BUF>
+template <int PPL, bool BUF, bool REC>
 __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb,
                                                uint32_t *__restrict__ mh_out, int p, const uint8_t *__restrict__ hll_in,
                                                uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride,
-                                               const ss_hll_params &prm, bool skip_hubs)
+                                               const ss_hll_params &prm, bool skip_hubs, const uint32_t *__restrict__ records)
 {
+    static_assert(BUF || !REC, "the records form posts through buffer descriptors");
     constexpr int R = kFusedRows, kNb = kWave - R;
     // 3 KB of estimator tables (the kernel is p = 8 only: 257 linear-counting entries; raw / bias up to 256 entries, longer tables stay
-    // in global memory) + 7 KB of landings per wavefront = 31 KB: five workgroups per CU
+    // in global memory) + 7 KB of landings per wavefront = 31 KB: five workgroups per CU.  REC: four 1 KB row images per wavefront
+    // in place of the landings, 19 KB
     __shared__ CompactEstimatorLds<257, 256> lds;
-    __shared__ __attribute__((aligned(16))) uint8_t landing[256 / kWave][kHllLds > 0 ? kHllLds : 1][1024];
+    __shared__ __attribute__((aligned(REC ? 1024 : 16))) uint8_t landing[256 / kWave][REC ? kWave / kRow : (kHllLds > 0 ? kHllLds : 1)][1024];
     const bool want_cards = cards_out != nullptr;
     EstimatorTables est = {};
     if (want_cards) est = stage_tables_compact(lds, prm);
@@ -169,6 +289,8 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
     const int lane = m.lane, grp = lane >> 4, c = lane & (kRow - 1);
     const uint32_t c16 = 16u * (uint32_t)c;
     const HllSource src = hll_source<BUF>(hll_in, g.N);
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rec_rsrc;
+    if constexpr (REC) rec_rsrc = table_rsrc(records, (uint32_t)(g.N * 4 * kRow));
     const bool skip_self = g.skip_self && *g.skip_self != 0;  // HLL side only (one scalar load per wavefront); the first hop keeps its self loop
 
     auto chunk_rows = [&](int64_t q) -> int { return q < n_chunks ? (int)(g.row1 - (g.row0 + q * R) < R ? g.row1 - (g.row0 + q * R) : R) : 0; };
@@ -233,19 +355,56 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
         h.deg = w.deg;
         h.write = w.write;
         h.total = w.total;
+        [[maybe_unused]] uint32_t rx[kRecSlots];
+        [[maybe_unused]] int reach = 0;  // REC: the slots some row of the wavefront reaches, at most kRecSlots
+        if constexpr (REC) {
+            const int t01 = max(__builtin_amdgcn_readlane(h.total, 0), __builtin_amdgcn_readlane(h.total, kRow));
+            const int t23 = max(__builtin_amdgcn_readlane(h.total, 2 * kRow), __builtin_amdgcn_readlane(h.total, 3 * kRow));
+            reach = max(t01, t23);
+            rec_post<0>(rx, rec_rsrc, ids_cur.my_nb << 6, c16 >> 2, reach);  // code records of chunk k
+        } else {
         hll_post<BUF, 0>(h, src, ids_cur.my_nb, c16);          // HLL rows of chunk k
         // (the slots' addresses go to m0; hidden from hipcc here, they are one s_add each -- known to be loop constants, the seven of
         // them are kept in spilled SGPRs and cost a v_readlane per post)
         uint32_t lds_slots = lds_wave;
         asm volatile("" : "+s"(lds_slots));
         hll_post_lds<BUF, kHllInFlight>(h, src, ids_cur.my_nb, c16, lds_slots);
+        }
         const Ids ids_next = load_ids(chunk + stride, rp_next); // ids of chunk k + 1 (its bounds arrived during the last walk)
         const int64_t rp_after = load_bounds(chunk + 2 * stride);  // bounds of chunk k + 2
 #pragma unroll 1
         for (int r = 0; r < m.rows; ++r) m.row(r, mh_out);       // MinHash first hop of chunk k: VALU work under all of the above
         u32x4 ae = {0u, 0u, 0u, 0u}, ao = {0u, 0u, 0u, 0u};
+        [[maybe_unused]] u32x4 packed;
+        if constexpr (REC) {
+            // the group's row image: zeroed, fed with the codes, packed -- fenced as hll_first_hop_row16 fences its image
+            // (its LDS byte address is formed here, chunk by chunk, hidden from hipcc: as loop constants the image's addresses are
+            // hoisted out of the chunk loop and live in VGPRs through the MinHash walk -- registers the kernel does not have)
+            uint32_t img = lds_wave + 1024u * (uint32_t)grp, z = 0u;
+            asm volatile("" : "+v"(img), "+v"(z));  // (the zero too: four registers of zeros otherwise)
+            const u32x4 zero = {z, z, z, z};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) *(lds_u32x4 *)(uintptr_t)(img + c16 + 256u * k) = zero;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            uint32_t mx = 0u;
+            rec_max<0>(rx, reach, mx);
+            const bool flags = (__ballot(mx == kRecordDense) & 0x0001000100010001ull) != 0ull;  // wave-uniform, rare
+            u32x4 dacc = zero;
+            if (flags) rec_scatter<0, true>(rx, img, reach, src, RecRow{h.nb, h.deg, h.i, (uint32_t)(g.N * 256)}, c16, dacc);
+            else rec_scatter<0, false>(rx, img, reach, src, RecRow{}, c16, dacc);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            uint32_t *pw = reinterpret_cast<uint32_t *>(&packed);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {  // lane c: registers 16 c .. 16 c + 15, a byte each
+                const u32x4 r4 = *(const lds_u32x4 *)(uintptr_t)(img + 4u * c16 + 16u * k);
+                pw[k] = r4.x | (r4.y << 8) | (r4.z << 16) | (r4.w << 24);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (flags) packed = bytemax16(packed, dacc);
+        } else {
         hll_fold(h, ae, ao);
-        if constexpr (kHllLds > 0) {
+        }
+        if constexpr (kHllLds > 0 && !REC) {
             // (hll_fold waited for h.x; the LDS landings were issued after them and vmcnt retires in order -- but hipcc does not
             // count a global_load_lds against the ds_read below, so the wait is spelled out; everything posted before the walk
             // is long back by now)
@@ -258,10 +417,12 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
                 hll_acc(ae, ao, v);
             }
         }
-        const u32x4 acc = hll_acc_result(ae, ao);
+        u32x4 acc;
+        if constexpr (REC) acc = packed;
+        else acc = hll_acc_result(ae, ao);
         // (the fused stage is the unsharded build's: no peers)
         if constexpr (BUF) {
-            hll_row16_finish_by<false>(h.i, h.write, h.nb, h.deg, h.total, acc, kHllInFlight + kHllLds,
+            hll_row16_finish_by<false>(h.i, h.write, h.nb, h.deg, h.total, acc, REC ? kRecSlots : kHllInFlight + kHllLds,
                                        [&](const int32_t *nb, int deg, int total, int64_t self_row, int first, int stride) {
                                            return hll_walk_buffer(src.rsrc, (uint32_t)(g.N * 256), reinterpret_cast<const int32_t *>(hll_in), nb, deg,
                                                                   total, self_row, first, stride, c16);
@@ -280,13 +441,14 @@ __device__ __forceinline__ void fused_hop_body(const GraphArgs &g, const uint64_
 // without scratch -- left alone it spreads to ~125 and four wavefronts).  P = 192 / 256 would spill at 96: they are held to the 128
 // VGPRs of FOUR wavefronts, which they had without being asked until the row body changed shape (left alone: 139 and three; held:
 // 104 / 124, no scratch).
-template <int PPL, bool BUF>
+// REC (with BUF only): the records form; `records` is the table the HLL first hop of this stage has just written, NULL otherwise.
+template <int PPL, bool BUF, bool REC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PPL <= 2 ? 5 : 4))) void fused_hop_persistent_kernel(
     GraphArgs g, const uint64_t *__restrict__ pa, const uint64_t *__restrict__ pb, uint32_t *__restrict__ mh_out, int p,
     const uint8_t *__restrict__ hll_in, uint8_t *__restrict__ hll_out, float *__restrict__ cards_out, int64_t cards_stride, ss_hll_params prm,
-    bool skip_hubs)
+    bool skip_hubs, const uint32_t *__restrict__ records)
 {
-    fused_hop_body<PPL, BUF>(g, pa, pb, mh_out, p, hll_in, hll_out, cards_out, cards_stride, prm, skip_hubs);
+    fused_hop_body<PPL, BUF, REC>(g, pa, pb, mh_out, p, hll_in, hll_out, cards_out, cards_stride, prm, skip_hubs, records);
 }
 
 }  // namespace ss
@@ -294,6 +456,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PPL <= 2 ? 
 extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, const uint64_t *b, int32_t P, uint32_t *mh1_out,
                                   uint32_t *mh2_out, int32_t p, uint8_t *hll1, float *cards1_out, uint8_t *hll2_out, float *cards2_out,
                                   int64_t cards_stride, const ss_hll_params *prm, void *stream)
+{
+    return ss_fused_hop_stage_records(graph, a, b, P, mh1_out, mh2_out, p, hll1, cards1_out, hll2_out, cards2_out, cards_stride, prm, nullptr, 0,
+                                      stream);
+}
+
+extern "C" int ss_fused_hop_stage_records(const ss_csr_graph *graph, const uint64_t *a, const uint64_t *b, int32_t P, uint32_t *mh1_out,
+                                          uint32_t *mh2_out, int32_t p, uint8_t *hll1, float *cards1_out, uint8_t *hll2_out,
+                                          float *cards2_out, int64_t cards_stride, const ss_hll_params *prm, uint32_t *records,
+                                          int64_t num_edges, void *stream)
 {
     const uint8_t *hll1_in = hll1;
     using namespace ss;
@@ -326,9 +497,29 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
     // tables (0: launches of their own, as in rounds 1-3)
     const int lead = hub_lead_blocks(hubs);
     const bool own_hop1 = cards1_out != nullptr;  // the hop-1 HLL table is computed here as well (build_hash_tables)
+    // how the kernel posts its hop-1 HLL rows: through a buffer descriptor when the table and the row after it fit the descriptor's
+    // 32-bit byte count, with flat addresses otherwise.  SS_FUSED_POSTS=flat, read at every launch, forces the flat form at any size
+    // (test hook; any other value, `buffer` included, leaves the choice to the size: a larger table cannot be described)
+    const char *posts_env = getenv("SS_FUSED_POSTS");
+    const bool buf_posts = buffer_describable(N * 256, 2 * 256) && !(posts_env && !strcmp(posts_env, "flat"));  // (lanes with nothing to fetch ask for row N)
+    // the records form (fused_hop_body, REC): where the caller gave a workspace, the stage writes the hop-1 HLL table itself -- the
+    // records are a by-product of that launch -- for the whole graph on one device, and the posts go through descriptors; and only on
+    // graphs whose mean closed neighbourhood fills at most three quarters of a record, E + N <= 24 N, and that list no hub rows.
+    // (Measured at 11 codes per node, the bench graph: 0.3958 -> 0.3875 ms per step, and at 21.8, citation2 size, where 2 % of the
+    // gathered slots are flagged: 17.61 -> 17.50 ms; not beyond.)  Denser ones flag too many of their nodes and gather 64 bytes for
+    // what a dense row answers better; on a skewed one most gathered slots name a
+    // flagged node -- 28 % on the power-law bench graph (alpha 0.9) -- and every flagged slot is a dense load issued and awaited
+    // AFTER the MinHash walk: 0.496 ms per step against 0.457 dense there.  (The caller's hub hint, csr.py / engine.py, drops the hub
+    // list of a shape whose earlier build found none: the first build of a shape runs dense.)  SS_FUSED_RECORDS, read at every
+    // launch: 0 forces the dense form, 1 the records form wherever it is legal (tests and measurements).
+    const char *rec_env = getenv("SS_FUSED_RECORDS");
+    const bool rec_legal = records && own_hop1 && whole && buf_posts;
+    const bool rec_sparse = num_edges >= 0 && num_edges + N <= 24 * N && !hubs;
+    const bool use_rec = rec_legal && (rec_env && !strcmp(rec_env, "1") ? true : rec_sparse && !(rec_env && !strcmp(rec_env, "0")));
     if (own_hop1) {
         if (!cards2_out) return SS_ERR_INVALID_ARG;
-        int rc1 = launch_hll_first_hop_rows(g, p, hll1, cards1_out, cards_stride, p0, hubs, lead, a, b, lead > 0 ? mh1_out : nullptr, P, s);
+        int rc1 = launch_hll_first_hop_rows(g, p, hll1, cards1_out, cards_stride, p0, hubs, lead, a, b, lead > 0 ? mh1_out : nullptr, P, s,
+                                            use_rec ? records : nullptr);
         if (rc1 != SS_OK) return rc1;
         // ONE hub pass from node ids for both hop-1 sketches: the MinHash hub rows are not needed before the table hop below,
         // but computing them here saves the hub launch after the fused kernel
@@ -344,24 +535,21 @@ extern "C" int ss_fused_hop_stage(const ss_csr_graph *graph, const uint64_t *a, 
     const int wg_per_cu = blocks > 256u * 128u ? 64 : 20;
     const unsigned grid = blocks < (unsigned)(256 * wg_per_cu) ? blocks : (unsigned)(256 * wg_per_cu);
     g.skip_self = own_hop1 ? skip_word : nullptr;
-    // how the kernel posts its hop-1 HLL rows: through a buffer descriptor when the table and the row after it fit the descriptor's
-    // 32-bit byte count, with flat addresses otherwise.  SS_FUSED_POSTS=flat, read at every launch, forces the flat form at any size
-    // (test hook; any other value, `buffer` included, leaves the choice to the size: a larger table cannot be described)
-    const char *posts_env = getenv("SS_FUSED_POSTS");
-    const bool buf_posts = buffer_describable(N * 256, 2 * 256) && !(posts_env && !strcmp(posts_env, "flat"));  // (lanes with nothing to fetch ask for row N)
     {
         ProfileSpan span(s, SS_PROF_FUSED, true);
-        auto launch = [&](auto buf) {
-            constexpr bool B = decltype(buf)::value;
+        const uint32_t *const rec_in = use_rec ? records : nullptr;
+        auto launch = [&](auto buf, auto rec) {
+            constexpr bool B = decltype(buf)::value, RC = decltype(rec)::value;
             switch (P / kWave) {
-                case 1: span.launch(fused_hop_persistent_kernel<1, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-                case 2: span.launch(fused_hop_persistent_kernel<2, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-                case 3: span.launch(fused_hop_persistent_kernel<3, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
-                default: span.launch(fused_hop_persistent_kernel<4, B>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs); break;
+                case 1: span.launch(fused_hop_persistent_kernel<1, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
+                case 2: span.launch(fused_hop_persistent_kernel<2, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
+                case 3: span.launch(fused_hop_persistent_kernel<3, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
+                default: span.launch(fused_hop_persistent_kernel<4, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
             }
         };
-        if (buf_posts) launch(std::true_type{});
-        else launch(std::false_type{});
+        if (use_rec) launch(std::true_type{}, std::true_type{});
+        else if (buf_posts) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
     }
     SS_LAUNCH_CHECK();
     g.skip_self = skip_word;  // (the MinHash table hop below; the hub launches do not look at it)

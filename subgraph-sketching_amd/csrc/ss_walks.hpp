@@ -458,11 +458,20 @@ __device__ __forceinline__ void first_hop_minhash_row(const int32_t *__restrict_
 // lane 0 the cardinality.  nid0: the id of the lane's first neighbour (col[l], requested by the caller, who may do so rows ahead);
 // always_valid: a word that lanes past the row's end may load; total = 0 with write = false: a group without a row to write.
 // MIR: the row also goes to the peers' tables.
-template <bool MIR>
+// REC: the group also leaves the row's CODE RECORD, 16 dwords at records + 16 * i, for the records form of the fused stage
+// (ss_fused_hop.hip): lane l stores code(l) | code(l + 16) << 16 of its neighbours t = l and l + 16, code = register << 2 | rank << 10
+// (a word offset into a row image and a rank <= 57; 0: no such neighbour -- rank 0 is a no-op under max).  No dedup, no sort, no
+// count: two neighbours in one register are two codes.  A row of more than kRecordCodes neighbours, and -- rec_flag -- a row this
+// group leaves to the hub units, gets kRecordDense in every dword: "read my dense row" (no code has its low two bits set).
+constexpr int kRecordCodes = 2 * kRow;
+constexpr uint32_t kRecordDense = 0xFFFFFFFFu;
+
+template <bool MIR, bool REC = false>
 __device__ __forceinline__ void hll_first_hop_row16(uint32_t *row, const int32_t *__restrict__ nb, int deg, int total, int64_t i, int nid0,
                                                     const int32_t *always_valid, int p, bool write, uint8_t *__restrict__ hll_out,
                                                     float *__restrict__ cards_out, int64_t cards_stride, const EstimatorTables &est,
-                                                    bool want_cards, int l /* lane & 15 */, const Mirrors &mir)
+                                                    bool want_cards, int l /* lane & 15 */, const Mirrors &mir,
+                                                    uint32_t *__restrict__ records = nullptr, bool rec_flag = false)
 {
 #pragma unroll
     for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x4 *>(row + 64 * k + 4 * l) = u32x4{0u, 0u, 0u, 0u};
@@ -471,12 +480,21 @@ __device__ __forceinline__ void hll_first_hop_row16(uint32_t *row, const int32_t
     // that always exists: rows of more than 16 neighbours otherwise pay one exposed round trip per 16 neighbours)
     int cur = nid0;
     int fresh = 0;  // registers this lane was the FIRST to set (the LDS atomic returns what was there: 0 exactly once per register)
+    [[maybe_unused]] uint32_t rec = 0u;
     for (int t = l; t < total; t += kRow) {
         const int nxt = *(t + kRow < deg ? nb + t + kRow : always_valid);
         const int64_t nid = t < deg ? (int64_t)cur : i;
         cur = nxt;
         const uint64_t hv = hash_u64((uint64_t)(nid + 1));
+        if constexpr (REC) {
+            const uint32_t code = (hll_register_of(hv, 256) << 2) | (hll_rank_of(hv, p) << 10);
+            if (t < kRow) rec = code;
+            else if (t < kRecordCodes) rec |= code << 16;
+        }
         fresh += atomicMax(&row[hll_register_of(hv, 256)], hll_rank_of(hv, p)) == 0u ? 1 : 0;  // (ranks are >= 1)
+    }
+    if constexpr (REC) {
+        if (write || rec_flag) records[i * kRow + l] = (rec_flag || total > kRecordCodes) ? kRecordDense : rec;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     // lane l owns registers 16l .. 16l+15
@@ -846,7 +864,9 @@ int launch_propagate_hub_only(const GraphArgs &g, const uint32_t *mh_in, uint32_
                               float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream);
 int launch_minhash_hop(const GraphArgs &g, const uint32_t *mh_in, uint32_t *mh_out, bool skip_hubs, int lead, const uint8_t *hub_hll_in,
                        uint8_t *hub_hll_out, float *hub_cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream);
+// (records: nullable; the regular-row groups also leave every row's code record there, hll_first_hop_row16)
 int launch_hll_first_hop_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
-                              bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, int P, hipStream_t stream);
+                              bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, int P, hipStream_t stream,
+                              uint32_t *records = nullptr);
 
 }  // namespace ss

@@ -355,10 +355,14 @@ class ElphHashes(object):
             # csrc/ss_fused_hop.hip), then hop-2 MinHash; further hops unfused
             ab = self._perms(device)
             graph = csr.struct()
+            # (the workspace of the stage's records form: 64 bytes per node, written by its HLL first hop and read by its fused kernel;
+            # the library decides per call whether it is used)
+            records = torch.empty((num_nodes, 16), dtype=torch.int32, device=device)
             with _Span('fused_hop_stage', device):
-                _native.check(_native.lib().ss_fused_hop_stage(byref(graph), _ptr(ab[0]), _ptr(ab[1]), self.num_perm, _ptr(mh[0]), _ptr(mh[1]),
-                                                               self.p, _ptr(hll[0]), _ptr(cards), _ptr(hll[1]), _ptr(cards[:, 1]), h,
-                                                               byref(params.struct), _stream(device)), 'ss_fused_hop_stage')
+                _native.check(_native.lib().ss_fused_hop_stage_records(byref(graph), _ptr(ab[0]), _ptr(ab[1]), self.num_perm, _ptr(mh[0]),
+                                                                       _ptr(mh[1]), self.p, _ptr(hll[0]), _ptr(cards), _ptr(hll[1]),
+                                                                       _ptr(cards[:, 1]), h, byref(params.struct), _ptr(records),
+                                                                       int(edge_index.shape[1]), _stream(device)), 'ss_fused_hop_stage_records')
             for k in range(3, h + 1):  # (inputs: hop k - 1 >= 2 of this build -- on a symmetric graph the rows skip their own row)
                 _propagate(csr, mh[k - 2], hll[k - 2], device, cards_out=cards[:, k - 1], cards_stride=h, params=params,
                            mh_out=mh[k - 1], hll_out=hll[k - 1], hop_tables=True)
