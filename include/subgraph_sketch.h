@@ -912,6 +912,51 @@ int ss_induced_mapper(const int64_t *nodes, int64_t n, int64_t N, int64_t *mappe
 int ss_induced_edges(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, const int64_t *mapper, const int64_t *block_incl,
                      int32_t *block_count, int64_t *out_src, int64_t *out_dst, int64_t *edge_ids, int32_t *err_flag, void *stream);
 
+/* The merge of equal (row, col) entries of an edge list, on the device: what torch_sparse.coalesce (reference src/datasets/elph.py:54-66,
+ * src/datasets/seal.py:58-60, 111-113) and PyG's to_undirected(..., reduce='add') (src/datasets/elph.py:54-66 for directed data,
+ * src/data.py:137, 174) do at the head of every dataset constructor [semantics restated; graph_prep.py].
+ * row / col: device int64 [E], the list (for to_undirected: the list followed by its reverse); perm: device int32 [E], the positions of
+ * the list sorted by (row, col, position) -- a permutation of [0, E), NOT validated: two stable groupings by ss_csr_group_ids +
+ * ss_csr_sort_rows, least significant key first.  1 <= N < 2^31, E < 2^31.  A RUN is the entries of one pair in list order.
+ *   ss_coalesce_mark        block_heads[b] (int32) = the run heads among the sorted positions [b, b + 1) * ss_coalesce_block(); position i
+ *                           is a head when i == 0 or its pair differs from position i - 1's.  An id outside [0, N) -- negative ones
+ *                           included, nothing wraps -- sets err_flag (nullable).
+ *   ss_coalesce_fill        block_incl: int64, the caller's INCLUSIVE cumulative sum of block_heads; n_runs = its last entry.  Every head
+ *                           takes slot = workgroup offset + ballot rank: out_row / out_col [n_runs] (int64) = its pair, run_start[slot]
+ *                           (int32 [n_runs + 1]) = its sorted position, run_start[n_runs] = E; rowptr (int64 [N + 1]) = where each row
+ *                           of out_row starts: where out_row steps from a to b the head fills rowptr[a + 1 .. b], the first gap starts
+ *                           at row 0 and the last ends at N.  With ids out of range (reported by the mark pass) no store leaves the
+ *                           outputs.
+ *   ss_coalesce_reduce      one lane per slot: out_count[slot] (int32) = the run's length; out_value[slot] = op over the run's values
+ *                           value[p] (p < n_values) or value[p - n_values] (the doubled list) in list order under the CHUNK RULE: the run
+ *                           is cut into chunks of ss_coalesce_chunk() entries from its start, every chunk folded sequentially from its
+ *                           first entry, the chunk results folded in chunk order.  add: the sum (int64 wraps); mean: that sum divided
+ *                           by the count in the value's type (int64: floor division); min / max: the canonical quiet NaN if any entry
+ *                           is NaN, else the extreme, of equal values (-0.0, +0.0) the one listed first.  A run of more than
+ *                           long_entries entries is not reduced but listed: long_runs (int32 [max_long], max_long >= E / long_entries),
+ *                           info[0] (int32) = how many, info[1] = the longest run; info is cleared by the call.  value null: counts and
+ *                           info[1] only.
+ *   ss_coalesce_reduce_long on the same stream after ss_coalesce_reduce: one wavefront per listed run, lane l folding chunks l, l + 64,
+ *                           ..., the chunk results joined in chunk order -- the bits ss_coalesce_reduce would have given.
+ *   ss_coalesce_symmetric   *asymmetric (int32, cleared by the call) = 1 if some output pair (u, v) has no pair (v, u) -- one lane per
+ *                           pair, a binary search of row v -- or (value given) one with another value (NaN equals NaN).
+ * dtype: 0 int64, 1 float32, 2 float64; op: 0 add, 1 mean, 2 min, 3 max; any other returns SS_ERR_UNSUPPORTED.  ss_coalesce_chunk() = 256
+ * entries per chunk of the accumulation order, ss_coalesce_block() = 2048 sorted positions per workgroup of the mark / fill passes.  Argument errors (SS_ERR_INVALID_ARG: a size out of range, a null
+ * pointer with a non-zero count) are detected before any launch; E == 0 / n_runs == 0: SS_OK, no launch.  No float atomics anywhere. */
+int ss_coalesce_chunk(void);
+int ss_coalesce_block(void);
+int ss_coalesce_mark(const int64_t *row, const int64_t *col, const int32_t *perm, int64_t E, int64_t N, int32_t *block_heads, int32_t *err_flag,
+                     void *stream);
+int ss_coalesce_fill(const int64_t *row, const int64_t *col, const int32_t *perm, int64_t E, int64_t N, const int64_t *block_incl,
+                     int64_t n_runs, int64_t *out_row, int64_t *out_col, int32_t *run_start, int64_t *rowptr, void *stream);
+int ss_coalesce_reduce(const int32_t *perm, const int32_t *run_start, int64_t n_runs, const void *value, int64_t n_values, int32_t dtype,
+                       int32_t op, int32_t long_entries, void *out_value, int32_t *out_count, int32_t *long_runs, int64_t max_long,
+                       int32_t *info, void *stream);
+int ss_coalesce_reduce_long(const int32_t *perm, const int32_t *run_start, int64_t n_runs, const void *value, int64_t n_values, int32_t dtype,
+                            int32_t op, void *out_value, const int32_t *long_runs, const int32_t *info, int64_t max_long, void *stream);
+int ss_coalesce_symmetric(const int64_t *rowptr, const int64_t *out_row, const int64_t *out_col, int64_t n_runs, int64_t N, const void *value,
+                          int32_t dtype, int32_t *asymmetric, void *stream);
+
 /* Measurement-only entry points (launch-duration probes used by bench.py and tools/) are declared in
  * subgraph_sketch_debug.h; they are not part of the drop-in boundary. */
 
