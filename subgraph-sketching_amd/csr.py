@@ -72,6 +72,17 @@ class CsrGraph(object):
                                       row_begin=begin, row_end=end)
 
 
+def _launch_build(src, dst, csr, err_flag, ws, label):
+    """the one call of ss_csr_build_symmetric: the edges (src, dst) into the buffers `csr` holds (a CsrGraph), behind the content
+    check if it has a fingerprint buffer; `label` names the builder in the error message of a failed call"""
+    device = csr.rowptr.device
+    with _Span('csr_build', device):
+        _native.check(_native.lib().ss_csr_build_symmetric(
+            _ptr(src), _ptr(dst), src.numel(), csr.num_nodes, _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.n_self_dev), csr.hub_threshold,
+            _ptr(csr.hub_rows), _ptr(csr.hub_count), _ptr(csr.mega_rows), _ptr(csr.mega_count), _ptr(err_flag), _ptr(ws), ws.numel(),
+            _ptr(csr.fingerprint), _ptr(csr.symmetric), _stream(device)), label)
+
+
 def _rebuild_csr_if_changed(csr, src, dst, err_flag):
     """ss_csr_build_cached into the buffers of `csr`: a device-side content check, then either nothing or an ordinary build"""
     lib = _native.lib()
@@ -83,14 +94,9 @@ def _rebuild_csr_if_changed(csr, src, dst, err_flag):
             lazy.resolve()
     csr.pending_lazies = []
     csr.pending_minhash = None
-    ws_bytes = lib.ss_csr_workspace_bytes(N, E)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    with _Span('csr_build', device):
-        # (content unchanged: every kernel exits and the symmetry word of the build that is kept stays)
-        _native.check(lib.ss_csr_build_symmetric(_ptr(src), _ptr(dst), E, N, _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.n_self_dev),
-                                                 csr.hub_threshold, _ptr(csr.hub_rows), _ptr(csr.hub_count), _ptr(csr.mega_rows),
-                                                 _ptr(csr.mega_count), _ptr(err_flag), _ptr(ws), ws_bytes, _ptr(csr.fingerprint),
-                                                 _ptr(csr.symmetric), _stream(device)), 'ss_csr_build_cached')
+    ws = torch.empty(lib.ss_csr_workspace_bytes(N, E), dtype=torch.uint8, device=device)
+    # (content unchanged: every kernel exits and the symmetry word of the build that is kept stays)
+    _launch_build(src, dst, csr, err_flag, ws, 'ss_csr_build_cached')
     return csr
 
 
@@ -145,17 +151,13 @@ def build_csr(edge_index, num_nodes, device, check=True, hub_threshold=None, err
     fp = None
     if fingerprint and not check and E > 0 and num_nodes > 0:
         fp = torch.zeros(_native.CSR_FINGERPRINT_BYTES, dtype=torch.uint8, device=device)
-    with _Span('csr_build', device):
-        # (fp None: the plain build; either way the level-0 pass also decides whether the edge list is symmetric)
-        _native.check(lib.ss_csr_build_symmetric(_ptr(src), _ptr(dst), E, num_nodes, _ptr(rowptr), _ptr(col), _ptr(n_self_dev),
-                                                 hub_threshold, _ptr(hub_rows), _ptr(hub_count), _ptr(mega_rows), _ptr(mega_count),
-                                                 _ptr(err), _ptr(ws), ws_bytes, _ptr(fp), _ptr(symmetric), _stream(device)),
-                      'ss_csr_build_cached' if fp is not None else 'ss_csr_build')
     csr = CsrGraph(rowptr, col, num_nodes, n_self_dev, _error_flag(device), hub_rows, hub_count, hub_threshold,
                    mega=(mega_rows, mega_count, mega_scratch))
     csr.num_edges = E
     csr.symmetric = symmetric
     csr.fingerprint = fp  # a later build_csr(..., reuse=csr) compares contents with these sums
+    # (fp None: the plain build; either way the level-0 pass also decides whether the edge list is symmetric)
+    _launch_build(src, dst, csr, err, ws, 'ss_csr_build_cached' if fp is not None else 'ss_csr_build')
     if check:
         # the one synchronising read of strict mode brings the hub / mega row counts along: a graph without such rows
         # (every unskewed graph) then serves no hub units (leading workgroups that would find nothing to do)

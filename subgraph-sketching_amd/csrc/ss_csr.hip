@@ -32,9 +32,15 @@
 // Traffic per edge at two levels: 16 + 8 (level 0) + 8 + 4 (level 1) + 4 + 4 (finish) = 44 B against 20 B algorithmic.
 // The first level also validates ids and reduces max(id)+1 (the self-loop count of add_self_loops, hashing.py:148);
 // the finish step lists hub rows.  Nothing synchronises with the host.
+//
+// In this file, in order: the level plan (make_plan); tile_sort_kernel; the three descriptor kernels; regroup_sort_kernel; the finish
+// step and its share protocol (finish_runs_kernel, "who may wait for whom"); the workspace (carve); the fingerprint kernels of the
+// cached form; the host side: CsrRequest (what a build is asked for), csr_check, csr_build_launch (one launch expression per kernel)
+// and the extern "C" builders, which fill a request.  Sorting the rows of a finished CSR is a unit of its own, ss_csr_sort_rows.hip.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "ss_common.hpp"
 
@@ -1857,8 +1863,6 @@ extern "C" int ss_debug_csr_protocol_faults(void)
     return v;
 }
 
-
-
 extern "C" size_t ss_csr_workspace_bytes(int64_t N, int64_t E)
 {
     ss::LevelPlan lp;
@@ -1866,18 +1870,36 @@ extern "C" size_t ss_csr_workspace_bytes(int64_t N, int64_t E)
     return ss::carve(lp, E, nullptr).bytes;
 }
 
+// Everything one build is asked for.  Each extern "C" builder below fills one and hands it on: a new output is one field here and
+// one name in the entry point that offers it.  A pointer left out of an initialiser is null: not asked for.
+struct CsrRequest {
+    const int64_t *src, *dst;         // src == nullptr: dst is a link list or an id array, the entry index is the payload (tile_sort_kernel)
+    int64_t E, N;
+    int key_stride;                   // int64 words from one key in dst to the next: 2 for edge and link lists, 1 for an id array
+    int64_t *rowptr;
+    int32_t *col;
+    int64_t *n_self_loops_out;        // (nullable)
+    int32_t hub_threshold;
+    int32_t *hub_rows, *hub_count;    // (nullable, both or neither)
+    int32_t *mega_rows, *mega_count;  // (nullable, both or neither, only with the hub list)
+    int32_t *err_flag, *symmetric_out;  // (nullable; the symmetry word is for edge lists only)
+    const int32_t *skip;              // cached form: the fingerprint's verdict, != 0 lets every kernel exit
+    int32_t *bad_record;              // cached form: where the build records that it met ids out of range
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
+
 // every check that can fail without a launch: arguments, plan, workspace (shared by the plain and the cached entry point -- the
 // cached one must not let its fingerprint kernels declare the outputs valid for a call that then builds nothing)
-static int csr_check(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, const int64_t *rowptr, const int32_t *col,
-                     const int32_t *hub_rows, const int32_t *hub_count, const int32_t *mega_rows, const int32_t *mega_count,
-                     const void *workspace, size_t workspace_bytes, ss::LevelPlan &lp)
+static int csr_check(const CsrRequest &r, ss::LevelPlan &lp)
 {
-    if (N < 0 || E < 0 || N >= ((int64_t)1 << 31) || !rowptr) return SS_ERR_INVALID_ARG;
-    if (E > 0 && (!dst || !col)) return SS_ERR_INVALID_ARG;
-    if ((hub_rows == nullptr) != (hub_count == nullptr)) return SS_ERR_INVALID_ARG;
-    if ((mega_rows == nullptr) != (mega_count == nullptr) || (mega_rows && !hub_rows)) return SS_ERR_INVALID_ARG;
-    if (!ss::make_plan(N, E, src ? N : E, lp)) return SS_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < ss_csr_workspace_bytes(N, E)) return SS_ERR_WORKSPACE;
+    if (r.N < 0 || r.E < 0 || r.N >= ((int64_t)1 << 31) || !r.rowptr) return SS_ERR_INVALID_ARG;
+    if (r.E > 0 && (!r.dst || !r.col)) return SS_ERR_INVALID_ARG;
+    if ((r.hub_rows == nullptr) != (r.hub_count == nullptr)) return SS_ERR_INVALID_ARG;
+    if ((r.mega_rows == nullptr) != (r.mega_count == nullptr) || (r.mega_rows && !r.hub_rows)) return SS_ERR_INVALID_ARG;
+    if (!ss::make_plan(r.N, r.E, r.src ? r.N : r.E, lp)) return SS_ERR_UNSUPPORTED;
+    if (!r.workspace || r.workspace_bytes < ss_csr_workspace_bytes(r.N, r.E)) return SS_ERR_WORKSPACE;
     return SS_OK;
 }
 
@@ -1924,66 +1946,56 @@ extern "C" int ss_csr_protocol_faults(void)
     return w ? __atomic_load_n(w, __ATOMIC_RELAXED) : -1;
 }
 
-// the launches of one build (arguments checked by csr_check)
-static int csr_build_launch(const ss::LevelPlan &lp, const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
-                            int64_t *n_self_loops_out, int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows,
-                            int32_t *mega_count, int32_t *err_flag, void *workspace, hipStream_t stream, const int32_t *skip = nullptr,
-                            int32_t *bad_record = nullptr, int key_stride = 2, int32_t *symmetric_out = nullptr)
+// the launches of one build (request checked by csr_check); each kernel template has ONE launch expression, its instantiation picked
+// by the std::true_type / std::false_type it is handed
+static int csr_build_launch(const CsrRequest &r, const ss::LevelPlan &lp)
 {
     using namespace ss;
-    if (N == 0 || E == 0) {
-        // (no edge: no row has a neighbour that could stand in for its self row -- the word says 0, "nothing to skip")
-        if (symmetric_out && hipMemsetAsync(symmetric_out, 0, 4, stream) != hipSuccess) return SS_ERR_LAUNCH;
-        if (n_self_loops_out && hipMemsetAsync(n_self_loops_out, 0, 8, stream) != hipSuccess) return SS_ERR_LAUNCH;
-        if (hub_count && hipMemsetAsync(hub_count, 0, 4, stream) != hipSuccess) return SS_ERR_LAUNCH;
-        if (mega_count && hipMemsetAsync(mega_count, 0, 8, stream) != hipSuccess) return SS_ERR_LAUNCH;
-        if (hipMemsetAsync(rowptr, 0, (size_t)(N + 1) * 8, stream) != hipSuccess) return SS_ERR_LAUNCH;
-        return SS_OK;
+    hipStream_t stream = r.stream;
+    if (r.N == 0 || r.E == 0) {  // nothing but memsets of the outputs that were asked for, in this order
+        const auto zero = [&](void *p, size_t bytes) { return !p || hipMemsetAsync(p, 0, bytes, stream) == hipSuccess; };
+        // (no edge: no row has a neighbour that could stand in for its self row -- the symmetry word says 0, "nothing to skip")
+        const bool ok = zero(r.symmetric_out, 4) && zero(r.n_self_loops_out, 8) && zero(r.hub_count, 4) && zero(r.mega_count, 8) && zero(r.rowptr, (size_t)(r.N + 1) * 8);
+        return ok ? SS_OK : SS_ERR_LAUNCH;
     }
     ProfileSpan span(stream, SS_PROF_CSR);  // all launches of this build
-    const Workspace w = carve(lp, E, workspace);
-    if (!src) symmetric_out = nullptr;  // (a link list / an id array has no symmetry to speak of)
+    const Workspace w = carve(lp, r.E, r.workspace);
+    int32_t *symmetric_out = r.src ? r.symmetric_out : nullptr;  // (a link list / an id array has no symmetry to speak of)
     unsigned long long *tile_sym = symmetric_out ? w.tile_sym : nullptr;
-    const RowOutputs rows_out = {rowptr, (int)hub_threshold, hub_rows, hub_count, mega_rows, mega_count, skip, err_flag, protocol_fault_word(), protocol_wait_ticks(), finish_walk_max(lp.groups[lp.levels]),
-                                symmetric_out, tile_sym};
-    unsigned long long *n_self = n_self_loops_out ? reinterpret_cast<unsigned long long *>(n_self_loops_out) : w.scratch;
+    const RowOutputs rows_out = {r.rowptr, (int)r.hub_threshold, r.hub_rows, r.hub_count, r.mega_rows, r.mega_count, r.skip, r.err_flag, protocol_fault_word(),
+                                protocol_wait_ticks(), finish_walk_max(lp.groups[lp.levels]), symmetric_out, tile_sym};
+    unsigned long long *n_self = r.n_self_loops_out ? reinterpret_cast<unsigned long long *>(r.n_self_loops_out) : w.scratch;
     const int tiles0 = (int)lp.tmax[0];
-    const bool packed = lp.packed;  // records of the last level (read by the finish step) are 4 bytes
-    if (lp.packed0)  // (two levels: 4-byte level-0 records, see make_plan)
-        hipLaunchKernelGGL(tile_sort_kernel<true>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits0, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
-    else if (packed && lp.levels == 1)
-        hipLaunchKernelGGL(tile_sort_kernel<true>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
-    else
-        hipLaunchKernelGGL(tile_sort_kernel<false>, dim3(tiles0), dim3(kSortThreads), 0, stream, src, dst, E, N, key_stride, lp.shift[0], lp.src_bits, lp.keys[0],
-                           tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, err_flag, hub_count, mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(E), skip, bad_record, tile_sym);
+    const auto tile_sort = [&](auto packed_out) {  // (packed0 -- two levels: 4-byte level-0 records, see make_plan -- brings its own source width)
+        hipLaunchKernelGGL(tile_sort_kernel<decltype(packed_out)::value>, dim3(tiles0), dim3(kSortThreads), 0, stream, r.src, r.dst, r.E, r.N, r.key_stride,
+                           lp.shift[0], lp.packed0 ? lp.src_bits0 : lp.src_bits, lp.keys[0], tiles0, (void *)w.staged_a, w.lv[0].off, w.tile_max, r.err_flag,
+                           r.hub_count, r.mega_count, w.dense_count, w.dense_sync, (int)max_dense_buckets(r.E), r.skip, r.bad_record, tile_sym);
+    };
+    if (lp.packed0 || (lp.packed && lp.levels == 1)) tile_sort(std::true_type{});
+    else tile_sort(std::false_type{});
     SS_LAUNCH_CHECK();
     ParentLevel par = {w.lv[0].off, nullptr, nullptr, nullptr, tiles0, tiles0, lp.keys[0], -1};
     const void *in = w.staged_a;
     for (int l = 1; l < lp.levels; ++l) {
         const LevelArrays &a = w.lv[l];
         hipLaunchKernelGGL(level_scan_kernel, dim3((unsigned)lp.groups[l]), dim3(1024), 0, stream, par, w.lv[l - 1].prefix, w.lv[l - 1].cfirst,
-                           a.gcount, a.base, skip);
+                           a.gcount, a.base, r.skip);
         SS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(level_tiles_kernel, dim3(1), dim3(1024), 0, stream, a.gcount, lp.groups[l], a.tb, a.n_tiles, skip);
+        hipLaunchKernelGGL(level_tiles_kernel, dim3(1), dim3(1024), 0, stream, a.gcount, lp.groups[l], a.tb, a.n_tiles, r.skip);
         SS_LAUNCH_CHECK();
         hipLaunchKernelGGL(level_fill_kernel, dim3((unsigned)lp.groups[l]), dim3(kWave), 0, stream, par, w.lv[l - 1].cfirst, a.tb, a.gcount, a.base,
-                           a.header, skip);
+                           a.header, r.skip);
         SS_LAUNCH_CHECK();
         void *out_buf = (l & 1) ? w.staged_b : (void *)w.staged_a;
-        const bool last = l == lp.levels - 1;
         const LevelOut out = {out_buf, a.off, a.tstart, a.header, a.n_tiles, (int)lp.tmax[l], lp.keys[l], lp.shift[l], lp.src_bits,
                               (1 << lp.node_shift) - 1};
-        if (l == 1 && lp.packed0)
-            hipLaunchKernelGGL((regroup_sort_kernel<true, true>), dim3((unsigned)lp.tmax[l]), dim3(kRegroupThreads), 0, stream, par,
-                               (const int2 *)in, w.lv[l - 1].prefix, out, skip, lp.src_bits0, lp.shift[0]);
-        else if (last && packed)
-            hipLaunchKernelGGL(regroup_sort_kernel<true>, dim3((unsigned)lp.tmax[l]), dim3(kRegroupThreads), 0, stream, par,
-                               (const int2 *)in, w.lv[l - 1].prefix, out, skip);
-        else
-            hipLaunchKernelGGL(regroup_sort_kernel<false>, dim3((unsigned)lp.tmax[l]), dim3(kRegroupThreads), 0, stream, par,
-                               (const int2 *)in, w.lv[l - 1].prefix, out, skip);
+        const auto regroup = [&](auto packed_out, auto packed_in) {  // (only 4-byte input records say how they are packed: the last two arguments)
+            hipLaunchKernelGGL((regroup_sort_kernel<decltype(packed_out)::value, decltype(packed_in)::value>), dim3((unsigned)lp.tmax[l]), dim3(kRegroupThreads),
+                               0, stream, par, (const int2 *)in, w.lv[l - 1].prefix, out, r.skip, packed_in ? lp.src_bits0 : 0, packed_in ? lp.shift[0] : 0);
+        };
+        if (l == 1 && lp.packed0) regroup(std::true_type{}, std::true_type{});
+        else if (l == lp.levels - 1 && lp.packed) regroup(std::true_type{}, std::false_type{});  // (4-byte records for the finish step)
+        else regroup(std::false_type{}, std::false_type{});
         SS_LAUNCH_CHECK();
         par = ParentLevel{a.off, a.tstart, a.tb, a.base, (int)lp.tmax[l], tiles0, lp.keys[l], lp.log2_keys[l]};
         in = out_buf;
@@ -1991,30 +2003,50 @@ static int csr_build_launch(const ss::LevelPlan &lp, const int64_t *src, const i
     const int64_t fine = lp.groups[lp.levels];
     // buckets that do not fit the LDS image are registered and worked off inside the finish launch, by every workgroup that has time
     // and by `helpers` extra ones (see "who may wait for whom"): no launches of their own, nothing to skip on an unskewed graph
-    const int64_t share_cap = max_dense_shares(E);
-    int helpers = run_helpers(packed);
+    const int64_t share_cap = max_dense_shares(r.E);
+    int helpers = run_helpers(lp.packed);
     if ((int64_t)helpers > share_cap) helpers = (int)share_cap;
     const DenseRunArgs dense = {w.dense_count, w.dense_list, w.dense_sync, w.dense_node_cnt, w.dense_share_off, w.dense_share_lo, w.dense_claim, nullptr, nullptr, 0, 0};
-    if (packed)
-        hipLaunchKernelGGL(finish_runs_kernel<true>, dim3((unsigned)(fine + helpers)), dim3(kRunThreads), 0, stream, par, in, w.tile_max, tiles0,
-                           lp.node_shift, lp.src_bits, N, col, n_self, rows_out, dense, fine);
-    else
-        hipLaunchKernelGGL(finish_runs_kernel<false>, dim3((unsigned)(fine + helpers)), dim3(kRunThreads), 0, stream, par, in, w.tile_max, tiles0,
-                           lp.node_shift, lp.src_bits, N, col, n_self, rows_out, dense, fine);
+    const auto finish = [&](auto packed_rec) {
+        hipLaunchKernelGGL(finish_runs_kernel<decltype(packed_rec)::value>, dim3((unsigned)(fine + helpers)), dim3(kRunThreads), 0, stream, par, in, w.tile_max,
+                           tiles0, lp.node_shift, lp.src_bits, r.N, r.col, n_self, rows_out, dense, fine);
+    };
+    if (lp.packed) finish(std::true_type{});  // (records of the last level are 4 bytes)
+    else finish(std::false_type{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
-static int csr_build_plain(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col, int64_t *n_self_loops_out,
-                           int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag,
-                           void *workspace, size_t workspace_bytes, int32_t *symmetric_out, void *stream_)
+// checks, then launches: the whole of a build that has no fingerprint (edge lists, link lists, id arrays)
+static int csr_build(const CsrRequest &r)
 {
-    if (E > 0 && !src) return SS_ERR_INVALID_ARG;
     ss::LevelPlan lp;
-    const int rc = csr_check(src, dst, E, N, rowptr, col, hub_rows, hub_count, mega_rows, mega_count, workspace, workspace_bytes, lp);
+    const int rc = csr_check(r, lp);
+    return rc != SS_OK ? rc : csr_build_launch(r, lp);
+}
+
+// (subgraph_sketch.h, ss_csr_build_cached) A build behind a content check: the fingerprint kernels compare (src, dst) with what the
+// previous call left in `fingerprint`; equal -> every kernel of the build exits at once (and err_flag re-reports the out-of-range ids
+// the build of the cached CSR met), different or first use -> an ordinary build.  No host synchronisation either way.
+// Every check that can fail without a launch runs BEFORE the fingerprint kernels (they declare the outputs valid for this edge
+// list); if a launch of the build itself fails after them, the fingerprint is invalidated on the stream before the error is
+// returned -- a later call with the same edges must not skip over a CSR that was never completed.
+static int csr_build_cached(CsrRequest r, void *fingerprint)
+{
+    using namespace ss;
+    if (!fingerprint || r.E <= 0 || r.N <= 0 || !r.src || !r.dst) return SS_ERR_INVALID_ARG;
+    LevelPlan lp;
+    int rc = csr_check(r, lp);
     if (rc != SS_OK) return rc;
-    return csr_build_launch(lp, src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                            workspace, (hipStream_t)stream_, nullptr, nullptr, 2, symmetric_out);
+    FingerprintWords *fp = reinterpret_cast<FingerprintWords *>(fingerprint);
+    r.skip = &fp->skip, r.bad_record = &fp->bad;  // (the two words only this form has)
+    hipLaunchKernelGGL(fingerprint_kernel, dim3(kFpBlocks), dim3(256), 0, r.stream, r.src, r.dst, r.E, fp);
+    SS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fingerprint_decide_kernel, dim3(1), dim3(kFpBlocks), 0, r.stream, fp, r.E, r.N, (int)r.hub_threshold, r.err_flag);
+    rc = hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_LAUNCH;
+    if (rc == SS_OK) rc = csr_build_launch(r, lp);
+    if (rc != SS_OK) (void)hipMemsetAsync(&fp->valid, 0, sizeof(fp->valid), r.stream);  // the outputs may be half-written
+    return rc;
 }
 
 extern "C" int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
@@ -2022,38 +2054,10 @@ extern "C" int ss_csr_build(const int64_t *src, const int64_t *dst, int64_t E, i
                             int32_t *mega_rows, int32_t *mega_count,
                             int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    return csr_build_plain(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag, workspace,
-                           workspace_bytes, nullptr, stream_);
-}
-
-// ss_csr_build that first compares a content fingerprint of (src, dst) with the one the previous call left in `fingerprint`
-// (device buffer of SS_CSR_FINGERPRINT_BYTES, zeroed by the caller before its first use, tied to THESE output buffers): equal ->
-// the outputs already hold this CSR and every kernel of the build exits at once; different (or first use) -> an ordinary build,
-// after which `fingerprint` describes the new contents.  No host synchronisation either way.  A skipped call re-reports (err_flag)
-// the out-of-range ids the build of the cached CSR met.  (reference models/elph.py:186 + runners/train.py:188-198: the same edges in a fresh tensor every step)
-// Every check that can fail without a launch runs BEFORE the fingerprint kernels (they declare the outputs valid for this edge
-// list); if a launch of the build itself fails after them, the fingerprint is invalidated on the stream before the error is
-// returned -- a later call with the same edges must not skip over a CSR that was never completed.
-static int csr_build_cached(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col, int64_t *n_self_loops_out,
-                            int32_t hub_threshold, int32_t *hub_rows, int32_t *hub_count, int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag,
-                            void *workspace, size_t workspace_bytes, void *fingerprint, int32_t *symmetric_out, void *stream_)
-{
-    using namespace ss;
-    if (!fingerprint || E <= 0 || N <= 0 || !src || !dst) return SS_ERR_INVALID_ARG;
-    LevelPlan lp;
-    int rc = csr_check(src, dst, E, N, rowptr, col, hub_rows, hub_count, mega_rows, mega_count, workspace, workspace_bytes, lp);
-    if (rc != SS_OK) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    FingerprintWords *fp = reinterpret_cast<FingerprintWords *>(fingerprint);
-    hipLaunchKernelGGL(fingerprint_kernel, dim3(kFpBlocks), dim3(256), 0, stream, src, dst, E, fp);
-    SS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fingerprint_decide_kernel, dim3(1), dim3(kFpBlocks), 0, stream, fp, E, N, (int)hub_threshold, err_flag);
-    rc = hipGetLastError() == hipSuccess ? SS_OK : SS_ERR_LAUNCH;
-    if (rc == SS_OK)
-        rc = csr_build_launch(lp, src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                              workspace, stream, &fp->skip, &fp->bad, 2, symmetric_out);
-    if (rc != SS_OK) (void)hipMemsetAsync(&fp->valid, 0, sizeof(fp->valid), stream);  // the outputs may be half-written
-    return rc;
+    const CsrRequest r = {.src = src, .dst = dst, .E = E, .N = N, .key_stride = 2, .rowptr = rowptr, .col = col, .n_self_loops_out = n_self_loops_out,
+                          .hub_threshold = hub_threshold, .hub_rows = hub_rows, .hub_count = hub_count, .mega_rows = mega_rows, .mega_count = mega_count,
+                          .err_flag = err_flag, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream_};
+    return E > 0 && !src ? SS_ERR_INVALID_ARG : csr_build(r);
 }
 
 extern "C" int ss_csr_build_cached(const int64_t *src, const int64_t *dst, int64_t E, int64_t N, int64_t *rowptr, int32_t *col,
@@ -2061,8 +2065,10 @@ extern "C" int ss_csr_build_cached(const int64_t *src, const int64_t *dst, int64
                                    int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
                                    void *fingerprint, void *stream_)
 {
-    return csr_build_cached(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag, workspace,
-                            workspace_bytes, fingerprint, nullptr, stream_);
+    const CsrRequest r = {.src = src, .dst = dst, .E = E, .N = N, .key_stride = 2, .rowptr = rowptr, .col = col, .n_self_loops_out = n_self_loops_out,
+                          .hub_threshold = hub_threshold, .hub_rows = hub_rows, .hub_count = hub_count, .mega_rows = mega_rows, .mega_count = mega_count,
+                          .err_flag = err_flag, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream_};
+    return csr_build_cached(r, fingerprint);
 }
 
 // ss_csr_build (fingerprint == NULL) or ss_csr_build_cached with one more output: *symmetric_out (device int32, nullable) <- 1 iff the
@@ -2073,204 +2079,31 @@ extern "C" int ss_csr_build_symmetric(const int64_t *src, const int64_t *dst, in
                                       int32_t *mega_rows, int32_t *mega_count, int32_t *err_flag, void *workspace, size_t workspace_bytes,
                                       void *fingerprint, int32_t *symmetric_out, void *stream_)
 {
-    if (!fingerprint)
-        return csr_build_plain(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                               workspace, workspace_bytes, symmetric_out, stream_);
-    return csr_build_cached(src, dst, E, N, rowptr, col, n_self_loops_out, hub_threshold, hub_rows, hub_count, mega_rows, mega_count, err_flag,
-                            workspace, workspace_bytes, fingerprint, symmetric_out, stream_);
+    const CsrRequest r = {.src = src, .dst = dst, .E = E, .N = N, .key_stride = 2, .rowptr = rowptr, .col = col, .n_self_loops_out = n_self_loops_out,
+                          .hub_threshold = hub_threshold, .hub_rows = hub_rows, .hub_count = hub_count, .mega_rows = mega_rows, .mega_count = mega_count,
+                          .err_flag = err_flag, .symmetric_out = symmetric_out, .workspace = workspace, .workspace_bytes = workspace_bytes,
+                          .stream = (hipStream_t)stream_};
+    if (fingerprint) return csr_build_cached(r, fingerprint);
+    return E > 0 && !src ? SS_ERR_INVALID_ARG : csr_build(r);
 }
 
-// The pairs of a query grouped by their first node (reference hashing.py:270-274 reads cards[u] / the rows of u once per PAIR;
-// BUDDY's link sets repeat every source many times -- ogbl-citation2's evaluation set lists 1 000 negatives per source): the
-// CSR builder run on (destination = first node of pair q, source = q).  order[0 .. B) is a permutation of the pair indices in
-// which all pairs of one first node are consecutive (rowptr [N + 1] says where each node's group starts).  Nothing is dropped:
-// ids out of range are keyed to node 0.  ss_pair_features_grouped walks `order` and reloads a first node's rows only when it
-// changes.  Workspace: ss_csr_workspace_bytes(N, B).
+// (subgraph_sketch.h) The pairs of a query grouped by their first node: the CSR builder run on (destination = first node of pair q,
+// source = q).  Nothing is dropped: ids out of range are keyed to node 0.
 extern "C" int ss_group_links_by_source(const int64_t *links, int64_t B, int64_t N, int32_t *order, int64_t *rowptr, void *workspace,
                                         size_t workspace_bytes, void *stream)
 {
     if (B < 0 || B >= ((int64_t)1 << 31) || N <= 0 || (B > 0 && (!links || !order))) return SS_ERR_INVALID_ARG;
-    ss::LevelPlan lp;
-    const int rc = csr_check(nullptr, links, B, N, rowptr, order, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, lp);
-    if (rc != SS_OK) return rc;
-    return csr_build_launch(lp, nullptr, links, B, N, rowptr, order, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
-                            (hipStream_t)stream);
+    return csr_build(CsrRequest{.dst = links, .E = B, .N = N, .key_stride = 2, .rowptr = rowptr, .col = order, .workspace = workspace,
+                                .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream});
 }
 
-// The entries of an id array grouped by id: order[0 .. E) is a permutation of the entry indices in which all entries with the
-// same id are consecutive (rowptr [N + 1] says where each id's group starts), in unspecified order inside a group -- follow with
-// ss_csr_sort_rows for ascending entry indices, i.e. a STABLE grouping (reference datasets/elph.py:87-110: gcn_norm's degree sums
-// and torch_sparse.spmm's scatter-add both accumulate in edge order; sign.py groups the edge list by column and by row).  Ids out
-// of [0, N) (after torch-style negative wrapping) are reported through err_flag and keyed to node 0.  Workspace: ss_csr_workspace_bytes(N, E).
+// (subgraph_sketch.h) The entries of an id array grouped by id: the builder with the entry index as payload and one key per int64
+// word; the order inside a group is unspecified until ss_csr_sort_rows makes it ascending, i.e. the grouping STABLE.
 extern "C" int ss_csr_group_ids(const int64_t *ids, int64_t E, int64_t N, int32_t *order, int64_t *rowptr, int32_t *err_flag, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
     if (E < 0 || E >= ((int64_t)1 << 31) || N <= 0 || (E > 0 && (!ids || !order))) return SS_ERR_INVALID_ARG;
-    ss::LevelPlan lp;
-    const int rc = csr_check(nullptr, ids, E, N, rowptr, order, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, lp);
-    if (rc != SS_OK) return rc;
-    return csr_build_launch(lp, nullptr, ids, E, N, rowptr, order, nullptr, 0, nullptr, nullptr, nullptr, nullptr, err_flag, workspace,
-                            (hipStream_t)stream, nullptr, nullptr, 1);
+    return csr_build(CsrRequest{.dst = ids, .E = E, .N = N, .key_stride = 1, .rowptr = rowptr, .col = order, .err_flag = err_flag,
+                                .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream});
 }
 
-namespace ss {
-
-// ---- rows of a CSR sorted ascending ----------------------------------------------------------------------------------------------
-// compare-exchange network over the low `G` lanes of a lane group (G = 16 or 64, a power of two): ascending
-template <int G>
-__device__ __forceinline__ int bitonic_lanes(int v, int lane)
-{
-#pragma unroll
-    for (int k = 2; k <= G; k <<= 1)
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j);
-            const bool up = (lane & k) == 0, low = (lane & j) == 0;
-            v = (low == up) ? (v < o ? v : o) : (v > o ? v : o);
-        }
-    return v;
-}
-
-// rows of at most 64 entries: four rows per wavefront (16 lanes each) where all four have at most 16 entries, else one after the
-// other over the whole wavefront; longer rows are listed for sort_rows_long_kernel
-__global__ __launch_bounds__(256) void sort_rows_short_kernel(const int64_t *__restrict__ rowptr, int32_t *__restrict__ col, int64_t N,
-                                                              int32_t *__restrict__ long_rows, int32_t *__restrict__ n_long,
-                                                              const int32_t *__restrict__ keep_word)
-{
-    if (keep_word && *keep_word == 0) return;  // (see ss_csr_sort_rows)
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    const int64_t r0 = wave * 4;
-    if (r0 >= N) return;
-    // lanes 0..4 read the five row bounds of this wavefront's four rows
-    const int64_t my = lane <= 4 ? rowptr[r0 + lane < N ? r0 + lane : N] : 0;
-    int64_t b[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) b[k] = __shfl(my, k);
-    const int64_t max_len = [&] { int64_t m = 0; for (int k = 0; k < 4; ++k) m = b[k + 1] - b[k] > m ? b[k + 1] - b[k] : m; return m; }();
-    if (max_len <= 16) {  // (wave-uniform)
-        const int g = lane >> 4, l = lane & 15;
-        const int64_t a = b[0] + 0 * g;  // (keep b[] in SGPRs: select by comparisons)
-        const int64_t lo = g == 0 ? b[0] : g == 1 ? b[1] : g == 2 ? b[2] : b[3];
-        const int64_t hi = g == 0 ? b[1] : g == 1 ? b[2] : g == 2 ? b[3] : b[4];
-        (void)a;
-        const int len = (int)(hi - lo);
-        int v = l < len ? col[lo + l] : 0x7FFFFFFF;
-        if (len > 1) v = bitonic_lanes<16>(v, l);  // (the whole 16-lane group takes the same branch)
-        if (l < len) col[lo + l] = v;
-        return;
-    }
-    for (int k = 0; k < 4; ++k) {
-        const int64_t lo = b[k], len = b[k + 1] - b[k];
-        if (len > kWave) {
-            if (lane == 0) long_rows[atomicAdd(n_long, 1)] = (int32_t)(r0 + k);
-            continue;
-        }
-        if (len < 2) continue;
-        int v = lane < len ? col[lo + lane] : 0x7FFFFFFF;
-        v = bitonic_lanes<kWave>(v, lane);
-        if (lane < len) col[lo + lane] = v;
-    }
-}
-
-// rows above 64 entries, one workgroup each (grid-stride over the list): bitonic sort in LDS up to 16 384 entries; longer rows (hub
-// rows of power-law graphs) are sorted in LDS chunk by chunk and the chunks merged pairwise (merge path: every thread finds where
-// its stretch of the output begins in both runs by a binary search along a diagonal, then merges sequentially), ping-ponging
-// between col and scratch (the row's own stretch of an E-entry scratch array)
-constexpr int kSortRowLds = 16384;
-
-// ascending bitonic sort of buf[0 .. n2), n2 a power of two <= kSortRowLds (all 1024 threads)
-__device__ __forceinline__ void bitonic_lds(int32_t *buf, int n2)
-{
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += 1024) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const int32_t a = buf[i], c = buf[p];
-                    if ((a > c) == ((i & k) == 0)) { buf[i] = c; buf[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__global__ __launch_bounds__(1024) void sort_rows_long_kernel(const int64_t *__restrict__ rowptr, int32_t *__restrict__ col,
-                                                              int32_t *__restrict__ scratch, const int32_t *__restrict__ long_rows,
-                                                              const int32_t *__restrict__ n_long)
-{
-    __shared__ int32_t buf[kSortRowLds];
-    const int n_rows = *n_long;
-    for (int q = blockIdx.x; q < n_rows; q += gridDim.x) {
-        const int64_t lo = rowptr[long_rows[q]], len = rowptr[long_rows[q] + 1] - lo;
-        int32_t *base = col + lo;
-        for (int64_t c0 = 0; c0 < len; c0 += kSortRowLds) {  // sorted chunks of up to 16 384 entries
-            const int n = (int)(len - c0 < kSortRowLds ? len - c0 : kSortRowLds);
-            int n2 = 1;
-            while (n2 < n) n2 <<= 1;
-            for (int i = threadIdx.x; i < n2; i += 1024) buf[i] = i < n ? base[c0 + i] : 0x7FFFFFFF;
-            __syncthreads();
-            bitonic_lds(buf, n2);
-            for (int i = threadIdx.x; i < n; i += 1024) base[c0 + i] = buf[i];
-            __syncthreads();
-        }
-        int32_t *src = base, *dst = scratch + lo;
-        for (int64_t width = kSortRowLds; width < len; width <<= 1) {  // pairwise merges of runs of `width`
-            for (int64_t s0 = 0; s0 < len; s0 += 2 * width) {
-                const int64_t na = len - s0 < width ? len - s0 : width, nb = len - s0 - na < width ? len - s0 - na : width;
-                const int32_t *A = src + s0, *Bp = A + na;
-                int32_t *O = dst + s0;
-                const int64_t m = na + nb, per = (m + 1023) / 1024;
-                const int64_t d0 = per * threadIdx.x < m ? per * threadIdx.x : m, d1 = d0 + per < m ? d0 + per : m;
-                // merge path: the number i of A's entries among the first d0 outputs (ties: A first -- the sort need not be
-                // stable, the entries of a row are distinct positions / may repeat harmlessly)
-                int64_t a_lo = d0 > nb ? d0 - nb : 0, a_hi = d0 < na ? d0 : na;
-                while (a_lo < a_hi) {
-                    const int64_t i = (a_lo + a_hi) >> 1;  // try i entries of A, d0 - i of B
-                    if (A[i] <= Bp[d0 - i - 1]) a_lo = i + 1; else a_hi = i;
-                }
-                int64_t i = a_lo, j = d0 - a_lo;
-                for (int64_t o = d0; o < d1; ++o) {
-                    const bool take_a = j >= nb || (i < na && A[i] <= Bp[j]);
-                    O[o] = take_a ? A[i++] : Bp[j++];
-                }
-            }
-            __syncthreads();
-            int32_t *t = src; src = dst; dst = t;
-        }
-        if (src != base) {
-            for (int64_t i = threadIdx.x; i < len; i += 1024) base[i] = src[i];
-        }
-        __syncthreads();
-    }
-}
-
-}  // namespace ss
-
-// Every row of a CSR sorted ascending in place (col of rows [0, N)).  With the entry indices as payload (ss_csr_group_ids,
-// ss_group_links_by_source) that makes the grouping STABLE -- the reference's edge order inside every group; with source ids it
-// gives the sorted adjacency scipy / torch_sparse hold.  Workspace: ss_csr_sort_workspace_bytes(E) device bytes.
-extern "C" size_t ss_csr_sort_workspace_bytes(int64_t E) { return E < 0 ? 0 : (size_t)(E / ss::kWave + 2) * 4 + 256 + (size_t)(E > 0 ? E : 1) * 4; }
-
-// only_if (nullable): device word; the rows are sorted only if it is NON-zero when the launches run (sign.py: the grouping by column
-// needs its order only when some edge weight differs from 1 -- ss_gcn_scan_edges leaves that in the first word of its buffer)
-extern "C" int ss_csr_sort_rows(const int64_t *rowptr, int32_t *col, int64_t N, int64_t E, const int32_t *only_if, void *workspace,
-                                size_t workspace_bytes, void *stream_)
-{
-    using namespace ss;
-    if (N < 0 || E < 0 || N >= ((int64_t)1 << 31) || E >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    if (N == 0 || E == 0) return SS_OK;
-    if (!rowptr || !col) return SS_ERR_INVALID_ARG;
-    if (!workspace || workspace_bytes < ss_csr_sort_workspace_bytes(E)) return SS_ERR_WORKSPACE;
-    hipStream_t stream = (hipStream_t)stream_;
-    int32_t *n_long = reinterpret_cast<int32_t *>(workspace);
-    int32_t *long_rows = n_long + 64;  // (its own cache lines)
-    int32_t *scratch = long_rows + (E / kWave + 2);
-    if (hipMemsetAsync(n_long, 0, 4, stream) != hipSuccess) return SS_ERR_LAUNCH;
-    const int64_t waves = (N + 3) / 4;
-    hipLaunchKernelGGL(sort_rows_short_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, rowptr, col, N, long_rows, n_long, only_if);
-    SS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_rows_long_kernel, dim3(512), dim3(1024), 0, stream, rowptr, col, scratch, long_rows, n_long);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
-}

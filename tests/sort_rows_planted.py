@@ -1,4 +1,4 @@
-"""CSRs and id arrays planted on the branches of ss_csr_sort_rows (the end of csrc/ss_csr.hip) and of sign.group_ids_stable built on
+"""CSRs and id arrays planted on the branches of ss_csr_sort_rows (csrc/ss_csr_sort_rows.hip) and of sign.group_ids_stable built on
 it, for tests/test_sort_rows_planted_host.py and tests/test_sort_rows_planted_gpu.py.  No test, no torch and no GPU code lives here,
 and nothing is imported from the kernel: the helpers below RESTATE its contract.
 
