@@ -162,138 +162,74 @@ __global__ __launch_bounds__(kHubThreads) void first_hop_hub_kernel(GraphArgs g,
                                                        want_cards, hub);
 }
 
-int launch_first_hop_hub_only(const GraphArgs &g, const uint64_t *a, const uint64_t *b, int P, uint32_t *mh_out, int p, uint8_t *hll_out,
-                              float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream);
+// ---- host: each kernel template above has ONE launch expression, its instantiation picked by the constants it is handed ------------
 
-// MinHash rows of one launch: kRowsPerWave consecutive rows per wavefront
-template <int PPL>
-void launch_minhash_rows(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, bool hubs, hipStream_t s)
+// MinHash rows: kRowsPerWave consecutive rows per wavefront
+static int launch_minhash_rows(const HopRequest &r)
 {
     constexpr int rows_per_block = 4 * kRowsPerWave;
-    const dim3 grid((unsigned)((g.rows() + rows_per_block - 1) / rows_per_block));
-    if (g.mir.n > 0)
-        hipLaunchKernelGGL((first_hop_rows_kernel<PPL, kRowsPerWave, true>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
-    else
-        hipLaunchKernelGGL((first_hop_rows_kernel<PPL, kRowsPerWave, false>), grid, dim3(256), 0, s, g, a, b, mh_out, p, hubs);
-}
-
-// MinHash alone: the row launch, then the hub units as a launch of their own
-template <int PPL>
-int launch_first_hop_mh(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, const ss_hll_params &prm,
-                        hipStream_t s)
-{
-    const bool hubs = g.hub_rows && g.hub_count;
+    const dim3 grid((unsigned)((r.g.rows() + rows_per_block - 1) / rows_per_block));
     {
-        ProfileSpan span(s, SS_PROF_FIRST_HOP_MH);
-        launch_minhash_rows<PPL>(g, a, b, mh_out, p, hubs, s);
+        ProfileSpan span(r.stream, SS_PROF_FIRST_HOP_MH);
+        for_ppl(r.P, [&](auto ppl) {
+            const auto launch = [&](auto mirrors) {
+                hipLaunchKernelGGL((first_hop_rows_kernel<decltype(ppl)::value, kRowsPerWave, decltype(mirrors)::value>), grid, dim3(256), 0, r.stream,
+                                   r.g, r.a, r.b, r.mh_out, r.p, r.hubs);
+            };
+            if (r.g.mir.n > 0) launch(std::true_type{});
+            else launch(std::false_type{});
+        });
     }
     SS_LAUNCH_CHECK();
-    if (hubs) {
-        note_hub_call();
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, true, false>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p,
-                           (uint8_t *)nullptr, (float *)nullptr, (int64_t)0, prm);
-        SS_LAUNCH_CHECK();
-    }
     return SS_OK;
 }
 
-// HLL first hop of the regular rows alone (ss_fused_hop_stage owns the hub pass that follows)
-// (`lead` leading workgroups serve the hub units of the HLL table and -- with hub_mh_out, P = 64 * PPL values per row from the
-// permutations a / b -- of the hop-1 MinHash table, ss_hub.hpp; 0: the caller launches first_hop_hub_kernel)
-template <int PPL>
-static int launch_hll_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
-                           bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, hipStream_t s,
-                           uint32_t *records)
+// HLL first hop of the regular rows (what follows for the hub rows is the caller's: ss_first_hop, ss_fused_hop_stage).  r.lead leading
+// workgroups serve the hub units of the HLL table; where r.mh_out is set as well, twice as many serve those of both hop-1 tables (a
+// quarter for the HLL units, the rest for the MinHash units, P = 64 * PPL values per row from the permutations a / b).  lead = 0: the
+// caller launches first_hop_hub_kernel
+int launch_hll_first_hop_rows(const HopRequest &r, uint32_t *records)
 {
-    ProfileSpan span(s, SS_PROF_FIRST_HOP_HLL);
-    const dim3 grid((unsigned)((g.rows() + 16 * kHllRows - 1) / (16 * kHllRows) + lead));
-    if (records)
-        hipLaunchKernelGGL((hll_first_hop_kernel<PPL, true>), grid, dim3(256), 0, s, g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a,
-                           b, hub_mh_out, records);
-    else
-        hipLaunchKernelGGL((hll_first_hop_kernel<PPL, false>), grid, dim3(256), 0, s, g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a,
-                           b, hub_mh_out, (uint32_t *)nullptr);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
-}
-
-int launch_hll_first_hop_rows(const GraphArgs &g, int p, uint8_t *hll_out, float *cards_out, int64_t cards_stride, const ss_hll_params &prm,
-                              bool skip_hubs, int lead, const uint64_t *a, const uint64_t *b, uint32_t *hub_mh_out, int P, hipStream_t s,
-                              uint32_t *records)
-{
-    if (g.mir.n > 0) records = nullptr;  // (the records instantiation stores no mirrors; ss_fused_hop_stage_records never asks for both)
-    if (lead == 0 || !hub_mh_out)
-        return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, nullptr, nullptr, nullptr, s, records);
-    lead *= 2;  // (a quarter for the HLL units, the rest for the MinHash units)
-    switch (P / kWave) {
-        case 1: return launch_hll_rows<1>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
-        case 2: return launch_hll_rows<2>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
-        case 3: return launch_hll_rows<3>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
-        default: return launch_hll_rows<4>(g, p, hll_out, cards_out, cards_stride, prm, skip_hubs, lead, a, b, hub_mh_out, s, records);
-    }
-}
-
-template <int PPL>
-int launch_first_hop(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, uint8_t *hll_out,
-                     float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t s)
-{
-    if (mh_out && hll_out) {
-        // both sketches: the latency-optimised HLL kernel + the MinHash kernel beat the combined kernel (37 + 134 us vs
-        // 184 us on the bench graph); one hub pass serves both
-        const bool hubs = g.hub_rows && g.hub_count;
-        const int lead = hub_lead_blocks(hubs);
-        const int rc = launch_hll_first_hop_rows(g, p, hll_out, cards_out, cards_stride, prm, hubs, lead, a, b, mh_out, PPL * kWave, s);
-        if (rc != SS_OK) return rc;
-        {
-            ProfileSpan span(s, SS_PROF_FIRST_HOP_MH);
-            launch_minhash_rows<PPL>(g, a, b, mh_out, p, hubs, s);
-        }
-        SS_LAUNCH_CHECK();
-        if (lead > 0) return SS_OK;  // (the hub units of both tables were hosted by the HLL launch)
-        return launch_first_hop_hub_only(g, a, b, PPL * kWave, mh_out, p, hll_out, cards_out, cards_stride, prm, s);
-    }
-    if (mh_out) return launch_first_hop_mh<PPL>(g, a, b, mh_out, p, prm, s);
-    // HLL alone: 16-lane-per-row kernel for the regular rows, the cooperative hub kernel for the rest
-    const bool hubs = g.hub_rows && g.hub_count;
-    const int lead = hub_lead_blocks(hubs);
-    const int rc = launch_hll_first_hop_rows(g, p, hll_out, cards_out, cards_stride, prm, hubs, lead, nullptr, nullptr, nullptr, 0, s);
-    if (rc != SS_OK) return rc;
-    if (hubs && lead == 0) {
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, false, true>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p,
-                           hll_out, cards_out, cards_stride, prm);
-        SS_LAUNCH_CHECK();
-    }
-    return SS_OK;
-}
-
-template <int PPL>
-static int hub_only(const GraphArgs &g, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, uint8_t *hll_out, float *cards_out,
-                    int64_t cards_stride, const ss_hll_params &prm, hipStream_t s)
-{
-    if (mh_out && hll_out)
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, true, true>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p, hll_out,
-                           cards_out, cards_stride, prm);
-    else if (mh_out)
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, true, false>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p, hll_out,
-                           cards_out, cards_stride, prm);
-    else
-        hipLaunchKernelGGL((first_hop_hub_kernel<PPL, false, true>), dim3(kHubGrid), dim3(kHubThreads), 0, s, g, a, b, mh_out, p, hll_out,
-                           cards_out, cards_stride, prm);
+    if (r.g.mir.n > 0) records = nullptr;  // (the records instantiation stores no mirrors; ss_fused_hop_stage_records never asks for both)
+    const bool host_mh = r.lead > 0 && r.mh_out;
+    const int lead = host_mh ? 2 * r.lead : r.lead;
+    ProfileSpan span(r.stream, SS_PROF_FIRST_HOP_HLL);
+    const dim3 grid((unsigned)((r.g.rows() + 16 * kHllRows - 1) / (16 * kHllRows) + lead));
+    for_ppl(host_mh ? r.P : kWave, [&](auto ppl) {  // (PPL only matters to the MinHash units)
+        const auto launch = [&](auto rec) {
+            hipLaunchKernelGGL((hll_first_hop_kernel<decltype(ppl)::value, decltype(rec)::value>), grid, dim3(256), 0, r.stream, r.g, r.p, r.hll_out,
+                               r.cards_out, r.cards_stride, r.prm, r.hubs, lead, host_mh ? r.a : nullptr, host_mh ? r.b : nullptr,
+                               host_mh ? r.mh_out : nullptr, records);
+        };
+        if (records) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
-int launch_first_hop_hub_only(const GraphArgs &g, const uint64_t *a, const uint64_t *b, int P, uint32_t *mh_out, int p, uint8_t *hll_out,
-                              float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream)
+// hub units as a launch of their own, for the tables the request names
+static int launch_first_hop_hubs(const HopRequest &r)
 {
-    if (!g.hub_rows || !g.hub_count || (!mh_out && !hll_out)) return SS_OK;
-    ProfileSpan span(stream, SS_PROF_HUB);
-    switch (P / kWave) {
-        case 1: return hub_only<1>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, prm, stream);
-        case 2: return hub_only<2>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, prm, stream);
-        case 3: return hub_only<3>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, prm, stream);
-        default: return hub_only<4>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, prm, stream);
-    }
+    for_ppl(r.P, [&](auto ppl) {
+        const auto launch = [&](auto mh, auto hll) {
+            hipLaunchKernelGGL((first_hop_hub_kernel<decltype(ppl)::value, decltype(mh)::value, decltype(hll)::value>), dim3(kHubGrid),
+                               dim3(kHubThreads), 0, r.stream, r.g, r.a, r.b, r.mh_out, r.p, r.hll_out, r.cards_out, r.cards_stride, r.prm);
+        };
+        if (r.mh_out && r.hll_out) launch(std::true_type{}, std::true_type{});
+        else if (r.mh_out) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::true_type{});
+    });
+    SS_LAUNCH_CHECK();
+    return SS_OK;
+}
+
+// ... as ONE hub pass under a span of its own: what a call that builds both hop-1 tables, or the fused stage, did not have hosted
+int launch_first_hop_hub_only(const HopRequest &r)
+{
+    if (!r.g.hub_rows || !r.g.hub_count || (!r.mh_out && !r.hll_out)) return SS_OK;
+    ProfileSpan span(r.stream, SS_PROF_HUB);
+    return launch_first_hop_hubs(r);
 }
 
 }  // namespace ss
@@ -303,29 +239,39 @@ extern "C" int ss_first_hop(const ss_csr_graph *graph, const uint64_t *a, const 
                             const ss_hll_params *prm, void *stream)
 {
     using namespace ss;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr) return SS_ERR_INVALID_ARG;
+    if (!graph_given(graph)) return SS_ERR_INVALID_ARG;
+    // written out: a shape without a kernel is answered before N is looked at (the caller falls back to init + propagate)
     // (the MinHash rows do not depend on p: a MinHash-only call is served for every hll_p; the HLL row image is 256 registers)
-    if ((hll_out && p != 8) || P <= 0 || P % kWave || P > 256) return SS_ERR_UNSUPPORTED;  // caller falls back to init + propagate
-    const int64_t N = graph->num_nodes;
-    if (N == 0) return SS_OK;
-    if ((!mh_out && !hll_out) || (mh_out && (!a || !b)) || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // either sketch may be NULL; a / b only feed MinHash
-    if ((graph->hub_rows == nullptr) != (graph->hub_count == nullptr)) return SS_ERR_INVALID_ARG;
-    ss_hll_params p0 = {};
-    if (cards_out) {
-        if (!hll_out) return SS_ERR_INVALID_ARG;
-        const int rc = check_params(prm);
-        if (rc != SS_OK) return rc;
-        if (prm->p != p) return SS_ERR_INVALID_ARG;
-        p0 = *prm;
+    if ((hll_out && p != 8) || P <= 0 || P % kWave || P > 256) return SS_ERR_UNSUPPORTED;
+    if (graph->num_nodes == 0) return SS_OK;
+    if ((!mh_out && !hll_out) || (mh_out && (!a || !b))) return SS_ERR_INVALID_ARG;  // either sketch may be NULL; a / b only feed MinHash
+    if (!graph_fits(*graph)) return SS_ERR_INVALID_ARG;
+    HopRequest r;
+    r.a = a;
+    r.b = b;
+    r.P = P;
+    r.p = p;
+    r.M = 256;
+    r.mh_out = mh_out;
+    r.hll_out = hll_out;
+    r.cards_out = cards_out;
+    r.cards_stride = cards_stride;
+    r.stream = (hipStream_t)stream;
+    int rc = take_params(r, prm);
+    if (rc != SS_OK) return rc;
+    if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;  // (here the parameters are judged before the row range)
+    r.g = to_args(*graph);
+    if (r.g.rows() == 0) return SS_OK;
+    schedule_hubs(r, true);
+    // both sketches: the latency-optimised HLL kernel + the MinHash kernel beat the combined kernel (37 + 134 us vs 184 us on the
+    // bench graph); the HLL launch hosts the hub units of both tables, or ONE hub pass serves both.  HLL alone: 16-lane-per-row
+    // kernel for the regular rows, the cooperative hub kernel for the rest
+    if (!hll_out) {  // MinHash alone: its row kernel hosts no units, the hub launch follows under either schedule (and gets no stride)
+        r.lead = 0;
+        r.cards_stride = 0;
     }
-    if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;
-    const GraphArgs g = to_args(*graph);
-    if (g.rows() == 0) return SS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    switch (P / kWave) {
-        case 1: return launch_first_hop<1>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, p0, s);
-        case 2: return launch_first_hop<2>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, p0, s);
-        case 3: return launch_first_hop<3>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, p0, s);
-        default: return launch_first_hop<4>(g, a, b, mh_out, p, hll_out, cards_out, cards_stride, p0, s);
-    }
+    if (hll_out) rc = launch_hll_first_hop_rows(r, nullptr);
+    if (rc == SS_OK && mh_out) rc = launch_minhash_rows(r);
+    if (rc != SS_OK || !r.hub_launch_follows()) return rc;
+    return mh_out && hll_out ? launch_first_hop_hub_only(r) : launch_first_hop_hubs(r);  // (a single sketch's hub launch leaves no span)
 }

@@ -466,36 +466,41 @@ extern "C" int ss_fused_hop_stage_records(const ss_csr_graph *graph, const uint6
                                           float *cards2_out, int64_t cards_stride, const ss_hll_params *prm, uint32_t *records,
                                           int64_t num_edges, void *stream)
 {
-    const uint8_t *hll1_in = hll1;
     using namespace ss;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr) return SS_ERR_INVALID_ARG;
-    if (p != 8 || P <= 0 || P % kWave || P > 256) return SS_ERR_UNSUPPORTED;  // caller uses ss_first_hop + ss_propagate
-    if (mh2_out && P != 128) return SS_ERR_UNSUPPORTED;                        // the hub pass of the table hop is P = 128 only
+    if (!graph_given(graph)) return SS_ERR_INVALID_ARG;
+    // written out: a shape without a kernel is answered before N is looked at (the caller uses ss_first_hop + ss_propagate)
+    if (p != 8 || P <= 0 || P % kWave || P > 256) return SS_ERR_UNSUPPORTED;
+    if (mh2_out && P != 128) return SS_ERR_UNSUPPORTED;  // the hub pass of the table hop is P = 128 only
     const int64_t N = graph->num_nodes;
     if (N == 0) return SS_OK;
-    if (!mh1_out || !a || !b || !hll1_in || !hll2_out || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    if ((graph->hub_rows == nullptr) != (graph->hub_count == nullptr)) return SS_ERR_INVALID_ARG;
-    ss_hll_params p0 = {};
-    if (cards2_out) {
-        const int rc = check_params(prm);
-        if (rc != SS_OK) return rc;
-        if (prm->p != p) return SS_ERR_INVALID_ARG;
-        p0 = *prm;
-    }
+    if (!mh1_out || !a || !b || !hll1 || !hll2_out || !graph_fits(*graph)) return SS_ERR_INVALID_ARG;
+    // the stage's second hop, a table hop from the hop-1 tables: the record the checks fill; hop 1 is a copy with its own tables
+    HopRequest hop2;
+    hop2.a = a;
+    hop2.b = b;
+    hop2.P = P;
+    hop2.p = p;
+    hop2.M = 256;
+    hop2.mh_in = mh2_out ? mh1_out : nullptr;
+    hop2.mh_out = mh2_out;
+    hop2.hll_in = hll1;
+    hop2.hll_out = hll2_out;
+    hop2.cards_out = cards2_out;
+    hop2.cards_stride = cards_stride;
+    hop2.stream = (hipStream_t)stream;
+    int rc = take_params(hop2, prm);
+    if (rc != SS_OK) return rc;
     if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;
-    GraphArgs g = to_args(*graph);
-    if (g.rows() == 0) return SS_OK;
+    hop2.g = to_args(*graph);
+    if (hop2.g.rows() == 0) return SS_OK;
     // both table hops of this stage read hop-1 tables of `graph`: the MinHash one this stage computes from node ids, the HLL one it
     // computes too unless it is the caller's (cards1_out == NULL) -- the promise of SS_GRAPH_HOP_TABLES, made here for the whole-graph,
     // single-device build (a row range or mirrors: the sharded builds, left alone)
-    const bool whole = graph->row_begin == 0 && graph->row_end == 0 && g.mir.n == 0;
-    const int32_t *const skip_word = self_skip_word(*graph, whole);
-    g.skip_self = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    const bool hubs = g.hub_rows && g.hub_count;
+    const bool whole = graph->row_begin == 0 && graph->row_end == 0 && hop2.g.mir.n == 0;
+    hop2.g.skip_self = self_skip_word(*graph, whole);
     // hub units: `lead` leading workgroups of the HLL first-hop launch serve both hop-1 tables, of the MinHash table hop both hop-2
     // tables (0: launches of their own, as in rounds 1-3)
-    const int lead = hub_lead_blocks(hubs);
+    schedule_hubs(hop2, true);
     const bool own_hop1 = cards1_out != nullptr;  // the hop-1 HLL table is computed here as well (build_hash_tables)
     // how the kernel posts its hop-1 HLL rows: through a buffer descriptor when the table and the row after it fit the descriptor's
     // 32-bit byte count, with flat addresses otherwise.  SS_FUSED_POSTS=flat, read at every launch, forces the flat form at any size
@@ -514,53 +519,56 @@ extern "C" int ss_fused_hop_stage_records(const ss_csr_graph *graph, const uint6
     // launch: 0 forces the dense form, 1 the records form wherever it is legal (tests and measurements).
     const char *rec_env = getenv("SS_FUSED_RECORDS");
     const bool rec_legal = records && own_hop1 && whole && buf_posts;
-    const bool rec_sparse = num_edges >= 0 && num_edges + N <= 24 * N && !hubs;
+    const bool rec_sparse = num_edges >= 0 && num_edges + N <= 24 * N && !hop2.hubs;
     const bool use_rec = rec_legal && (rec_env && !strcmp(rec_env, "1") ? true : rec_sparse && !(rec_env && !strcmp(rec_env, "0")));
+    // hop 1 from node ids: both tables where the stage owns the HLL one (ONE hub pass from node ids for both hop-1 sketches: the
+    // MinHash hub rows are not needed before the table hop below, but computing them here saves the hub launch after the fused
+    // kernel), the MinHash table alone otherwise
+    HopRequest hop1 = hop2;
+    hop1.g.skip_self = nullptr;  // (the first hop keeps its self loop)
+    hop1.mh_in = nullptr;
+    hop1.mh_out = mh1_out;
+    hop1.hll_in = nullptr;
+    hop1.hll_out = own_hop1 ? hll1 : nullptr;
+    hop1.cards_out = cards1_out;
+    if (!own_hop1) hop1.cards_stride = 0;
     if (own_hop1) {
         if (!cards2_out) return SS_ERR_INVALID_ARG;
-        int rc1 = launch_hll_first_hop_rows(g, p, hll1, cards1_out, cards_stride, p0, hubs, lead, a, b, lead > 0 ? mh1_out : nullptr, P, s,
-                                            use_rec ? records : nullptr);
-        if (rc1 != SS_OK) return rc1;
-        // ONE hub pass from node ids for both hop-1 sketches: the MinHash hub rows are not needed before the table hop below,
-        // but computing them here saves the hub launch after the fused kernel
-        if (lead == 0) rc1 = launch_first_hop_hub_only(g, a, b, P, mh1_out, p, hll1, cards1_out, cards_stride, p0, s);
-        if (rc1 != SS_OK) return rc1;
+        rc = launch_hll_first_hop_rows(hop1, use_rec ? records : nullptr);
+        if (rc == SS_OK && hop1.hub_launch_follows()) rc = launch_first_hop_hub_only(hop1);
+        if (rc != SS_OK) return rc;
     }
     constexpr int rows_per_block = 4 * kFusedRows;
-    const unsigned blocks = (unsigned)((g.rows() + rows_per_block - 1) / rows_per_block);
+    const unsigned blocks = (unsigned)((hop2.g.rows() + rows_per_block - 1) / rows_per_block);
     // 5 workgroups are resident per CU; several times that many balance the tail.  Bench graph (58 blocks per CU): 12 / 15 / 20 / 25 / 30 /
     // 40 per CU: 148.7 / 147.8 / 146.2-146.9 / 149.9 / 149.2 / 151.2 us.  ppa / citation2 size (140 / 715 blocks per CU): 15 / 20 / 30 /
     // 48 / 64 / 100 / 200 / all: 1 832 / 1 819 / 1 774 / 1 724 / 1 738 / 1 728 / 1 751 / 1 748 us and 3 540 / 3 499 / 3 448 / 3 418 / 3 408 /
     // 3 419 / 3 457 / 3 814 us
     const int wg_per_cu = blocks > 256u * 128u ? 64 : 20;
     const unsigned grid = blocks < (unsigned)(256 * wg_per_cu) ? blocks : (unsigned)(256 * wg_per_cu);
-    g.skip_self = own_hop1 ? skip_word : nullptr;
     {
-        ProfileSpan span(s, SS_PROF_FUSED, true);
+        // the fused kernel: hop-1 MinHash rows from node ids beside the hop-2 HLL rows (their self rows skipped only over a hop-1 HLL
+        // table this stage has just built)
+        GraphArgs g = hop2.g;
+        if (!own_hop1) g.skip_self = nullptr;
+        ProfileSpan span(hop2.stream, SS_PROF_FUSED, true);
         const uint32_t *const rec_in = use_rec ? records : nullptr;
-        auto launch = [&](auto buf, auto rec) {
-            constexpr bool B = decltype(buf)::value, RC = decltype(rec)::value;
-            switch (P / kWave) {
-                case 1: span.launch(fused_hop_persistent_kernel<1, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
-                case 2: span.launch(fused_hop_persistent_kernel<2, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
-                case 3: span.launch(fused_hop_persistent_kernel<3, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
-                default: span.launch(fused_hop_persistent_kernel<4, B, RC>, dim3(grid), dim3(256), g, a, b, mh1_out, p, hll1_in, hll2_out, cards2_out, cards_stride, p0, hubs, rec_in); break;
-            }
+        const auto launch = [&](auto buf, auto rec) {
+            for_ppl(P, [&](auto ppl) {
+                span.launch(fused_hop_persistent_kernel<decltype(ppl)::value, decltype(buf)::value, decltype(rec)::value>, dim3(grid), dim3(256), g, a,
+                            b, mh1_out, p, hop2.hll_in, hll2_out, cards2_out, cards_stride, hop2.prm, hop2.hubs, rec_in);
+            });
         };
         if (use_rec) launch(std::true_type{}, std::true_type{});
         else if (buf_posts) launch(std::true_type{}, std::false_type{});
         else launch(std::false_type{}, std::false_type{});
     }
     SS_LAUNCH_CHECK();
-    g.skip_self = skip_word;  // (the MinHash table hop below; the hub launches do not look at it)
     // hub rows of the hop-1 MinHash table (from node ids): they must be in place before anything reads that table
-    int rc = own_hop1 ? SS_OK : launch_first_hop_hub_only(g, a, b, P, mh1_out, p, nullptr, nullptr, 0, p0, s);
+    rc = own_hop1 ? SS_OK : launch_first_hop_hub_only(hop1);
     if (rc != SS_OK) return rc;
-    if (!mh2_out)  // hop-2 HLL hub rows alone
-        return launch_propagate_hub_only(g, nullptr, nullptr, hll1_in, hll2_out, cards2_out, cards_stride, p0, s);
+    if (!mh2_out) return launch_propagate_hub_only(hop2);  // hop-2 HLL hub rows alone
     // MinHash table hop of hop 2; its launch hosts the hub units of both hop-2 tables (or ONE hub pass for both follows)
-    if (lead > 0) return launch_minhash_hop(g, mh1_out, mh2_out, hubs, lead, hll1_in, hll2_out, cards2_out, cards_stride, p0, s);
-    rc = launch_minhash_hop(g, mh1_out, mh2_out, hubs, 0, nullptr, nullptr, nullptr, 0, p0, s);
-    if (rc != SS_OK) return rc;
-    return launch_propagate_hub_only(g, mh1_out, mh2_out, hll1_in, hll2_out, cards2_out, cards_stride, p0, s);
+    rc = launch_minhash_hop(hop2, hop2.lead > 0);
+    return rc != SS_OK || !hop2.hub_launch_follows() ? rc : launch_propagate_hub_only(hop2);
 }

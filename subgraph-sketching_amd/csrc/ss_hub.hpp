@@ -20,6 +20,7 @@
 // rows are served by different workgroups of ONE launch, at the same time.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "ss_walks.hpp"
 
@@ -40,6 +41,73 @@ inline int hub_lead_blocks(bool hubs)
     static_assert(kHubLeadBlocks >= 4, "every share of the leading workgroups holds one");
     return hubs && !launches ? kHubLeadBlocks : 0;
 }
+
+// ---- host side of the table build (ss_first_hop.hip, ss_propagate.hip, ss_fused_hop.hip, the tail of ss_update.hip) -----------------
+// What one call asks of its launches.  An extern "C" entry point fills one record after its checks; where its launches differ in a
+// few fields it copies the record and sets those by name.  A null table: that sketch is not part of the launch.
+struct HopRequest {
+    GraphArgs g;
+    const uint64_t *a = nullptr, *b = nullptr;  // MinHash permutations (the hops from node ids)
+    int P = 0, p = 0, M = 0;                    // permutations, hll_p, HLL registers
+    const uint32_t *mh_in = nullptr;            // input tables: the table hops only
+    uint32_t *mh_out = nullptr;
+    const uint8_t *hll_in = nullptr;
+    uint8_t *hll_out = nullptr;
+    float *cards_out = nullptr;
+    int64_t cards_stride = 0;
+    ss_hll_params prm = {};                     // (zeros unless cards_out, take_params)
+    hipStream_t stream = nullptr;
+    // the hub schedule (schedule_hubs): the row kernels leave the listed rows out, `lead` leading workgroups of a row launch serve them
+    bool hubs = false;
+    int lead = 0;
+    bool hub_launch_follows() const { return hubs && lead == 0; }  // no row launch hosted the units: the stand-alone hub kernel runs
+};
+
+// The hub schedule of one library call, asked once: are hub rows listed, does a row launch host their units, or does a hub launch
+// follow.  (hub_lead_blocks also counts the call for ss_debug_hub_calls.)  `served`: the call's kernels have hub units for its shape
+inline void schedule_hubs(HopRequest &r, bool served)
+{
+    r.hubs = served && r.g.hub_rows && r.g.hub_count;
+    r.lead = hub_lead_blocks(r.hubs);
+}
+
+// f(std::integral_constant<int, PPL>) for the PPL = P / 64 permutations a lane owns, 1 .. 4 (anything else: 4)
+template <class F>
+inline void for_ppl(int P, F &&f)
+{
+    switch (P / kWave) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
+// The entry preamble's shared checks, in the two places every entry point has them: before its N == 0 exit ...
+inline bool graph_given(const ss_csr_graph *graph) { return graph && graph->num_nodes >= 0 && graph->rowptr; }
+// ... and after it: node ids fit 31 bits and the hub list comes with its count
+inline bool graph_fits(const ss_csr_graph &graph)
+{
+    return graph.num_nodes < ((int64_t)1 << 31) && (graph.hub_rows == nullptr) == (graph.hub_count == nullptr);
+}
+// r.cards_out asks for cardinalities: of an HLL table this call writes, with usable parameters for rows of r.M registers
+inline int take_params(HopRequest &r, const ss_hll_params *prm)
+{
+    if (!r.cards_out) return SS_OK;
+    if (!r.hll_out) return SS_ERR_INVALID_ARG;
+    const int rc = check_params(prm);
+    if (rc != SS_OK) return rc;
+    if ((1 << prm->p) != r.M) return SS_ERR_INVALID_ARG;
+    r.prm = *prm;
+    return SS_OK;
+}
+
+// launches defined in ss_first_hop.hip / ss_propagate.hip that ss_fused_hop_stage strings together as well
+// (records: nullable; the regular-row groups also leave every row's code record there, hll_first_hop_row16)
+int launch_hll_first_hop_rows(const HopRequest &r, uint32_t *records);
+int launch_first_hop_hub_only(const HopRequest &r);
+int launch_minhash_hop(const HopRequest &r, bool host_hll);
+int launch_propagate_hub_only(const HopRequest &r);
 
 struct HubCounts {
     int hubs, mega, slices;

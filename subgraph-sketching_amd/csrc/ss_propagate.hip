@@ -159,63 +159,58 @@ __global__ __launch_bounds__(kHubThreads) void propagate_hub_kernel(GraphArgs g,
                                               want_cards, hub);
 }
 
+// ---- host: each kernel above has ONE launch expression --------------------------------------------------------------------------
+
+// propagate_kernel, four rows per workgroup behind r.lead leading workgroups: n_rows of the row range, or entries of the row list.
+// <128, 256> is only ever launched for the MinHash rows alone and hosts the hub units of the MinHash table -- with `hub_hll`, the
+// request whose HLL tables the stage computes beside it, the second half of the leading workgroups serves that table's units;
+// <0, 0> takes r.P / r.M at run time and has no hub units
 template <int TP, int TM>
-int launch_propagate(const GraphArgs &g, const uint32_t *mh_in, uint32_t *mh_out, int P, const uint8_t *hll_in, uint8_t *hll_out, int M,
-                     float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream)
+static void launch_propagate_kernel(ProfileSpan &span, const HopRequest &r, int64_t n_rows, const HopRequest *hub_hll)
 {
-    const int rows_per_block = 256 / kWave;
-    const int64_t blocks = (g.rows() + rows_per_block - 1) / rows_per_block;
-    const bool hubs = TP == 128 && TM == 256 && g.hub_rows && g.hub_count;
-    const int lead = hub_lead_blocks(hubs && !hll_out);  // (the <128, 256> row kernel hosts MinHash units only)
-    {
-        ProfileSpan span(stream, mh_out && !hll_out && TP == 128 ? SS_PROF_MINHASH_HOP : SS_PROF_TAGS);  // MinHash table hop
-        hipLaunchKernelGGL((propagate_kernel<TP, TM>), dim3((unsigned)(blocks + lead)), dim3(256), 0, stream, g, mh_in, mh_out, P, hll_in,
-                           hll_out, M, cards_out, cards_stride, prm, hubs, lead, (const uint8_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr);
-    }
-    SS_LAUNCH_CHECK();
-    if (hubs && lead == 0) return launch_propagate_hub_only(g, mh_in, mh_out, hll_in, hll_out, cards_out, cards_stride, prm, stream);
-    return SS_OK;
+    span.launch(propagate_kernel<TP, TM>, dim3((unsigned)((n_rows + 3) / 4 + r.lead)), dim3(256), r.g, r.mh_in, r.mh_out, TP ? TP : r.P, r.hll_in,
+                r.hll_out, TM ? TM : r.M, r.cards_out, r.cards_stride, r.prm, r.hubs, r.lead, hub_hll ? hub_hll->hll_in : nullptr,
+                hub_hll ? hub_hll->hll_out : nullptr, hub_hll ? hub_hll->cards_out : nullptr);
 }
 
-// the MinHash table hop alone (P = 128): the regular rows and -- `lead` leading workgroups -- the hub units of the MinHash table
-// and, with hub_hll_out, of the HLL table of the same hop (hub_cards_out / cards_stride / prm: its cardinalities)
-int launch_minhash_hop(const GraphArgs &g, const uint32_t *mh_in, uint32_t *mh_out, bool skip_hubs, int lead, const uint8_t *hub_hll_in,
-                       uint8_t *hub_hll_out, float *hub_cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream)
+// the MinHash table hop alone (P = 128) of a request that may name HLL tables too: the regular rows and -- r.lead leading workgroups --
+// the hub units of the MinHash table and, with host_hll, of the HLL table of the same hop (r.cards_out / cards_stride / prm: its
+// cardinalities)
+int launch_minhash_hop(const HopRequest &r, bool host_hll)
 {
-    ProfileSpan span(stream, SS_PROF_MINHASH_HOP, true);
-    span.launch(propagate_kernel<128, 256>, dim3((unsigned)((g.rows() + 3) / 4 + lead)), dim3(256), g, mh_in, mh_out, 128,
-                (const uint8_t *)nullptr, (uint8_t *)nullptr, 256, (float *)nullptr, cards_stride, prm, skip_hubs, lead, hub_hll_in, hub_hll_out,
-                hub_cards_out);
+    HopRequest rows = r;
+    rows.hll_in = nullptr;
+    rows.hll_out = nullptr;
+    rows.cards_out = nullptr;
+    if (!host_hll) rows.cards_stride = 0;
+    ProfileSpan span(r.stream, SS_PROF_MINHASH_HOP, true);
+    launch_propagate_kernel<128, 256>(span, rows, r.g.rows(), host_hll ? &r : nullptr);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
 // the hub units of a table hop as a launch of their own (16-wave workgroups): what the row launches above did not host
-int launch_propagate_hub_only(const GraphArgs &g, const uint32_t *mh_in, uint32_t *mh_out, const uint8_t *hll_in, uint8_t *hll_out,
-                              float *cards_out, int64_t cards_stride, const ss_hll_params &prm, hipStream_t stream)
+int launch_propagate_hub_only(const HopRequest &r)
 {
-    if (!g.hub_rows || !g.hub_count || (!mh_out && !hll_out)) return SS_OK;
-    ProfileSpan span(stream, SS_PROF_HUB);
-    if (mh_out && hll_out)
-        hipLaunchKernelGGL((propagate_hub_kernel<true, true>), dim3(kHubGrid), dim3(kHubThreads), 0, stream, g, mh_in, mh_out, hll_in, hll_out,
-                           cards_out, cards_stride, prm);
-    else if (mh_out)
-        hipLaunchKernelGGL((propagate_hub_kernel<true, false>), dim3(kHubGrid), dim3(kHubThreads), 0, stream, g, mh_in, mh_out, hll_in, hll_out,
-                           cards_out, cards_stride, prm);
-    else
-        hipLaunchKernelGGL((propagate_hub_kernel<false, true>), dim3(kHubGrid), dim3(kHubThreads), 0, stream, g, mh_in, mh_out, hll_in, hll_out,
-                           cards_out, cards_stride, prm);
+    if (!r.g.hub_rows || !r.g.hub_count || (!r.mh_out && !r.hll_out)) return SS_OK;
+    ProfileSpan span(r.stream, SS_PROF_HUB);
+    const auto launch = [&](auto mh, auto hll) {
+        hipLaunchKernelGGL((propagate_hub_kernel<decltype(mh)::value, decltype(hll)::value>), dim3(kHubGrid), dim3(kHubThreads), 0, r.stream, r.g,
+                           r.mh_in, r.mh_out, r.hll_in, r.hll_out, r.cards_out, r.cards_stride, r.prm);
+    };
+    if (r.mh_out && r.hll_out) launch(std::true_type{}, std::true_type{});
+    else if (r.mh_out) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::true_type{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
 // the HLL table hop alone (M = 256): 4 destinations per wavefront + the hub units of the HLL table
-static int launch_hll_hop(const GraphArgs &g, const uint8_t *hll_in, uint8_t *hll_out, float *cards_out, int64_t cards_stride,
-                          const ss_hll_params &prm, bool hubs, int lead, hipStream_t stream)
+static int launch_hll_hop(const HopRequest &r)
 {
-    ProfileSpan span(stream, SS_PROF_HLL_HOP);
-    hipLaunchKernelGGL(hll_propagate_row16_kernel, dim3((unsigned)((g.rows() + 15) / 16 + lead)), dim3(256), 0, stream, g, hll_in, hll_out,
-                       cards_out, cards_stride, prm, hubs, lead);
+    ProfileSpan span(r.stream, SS_PROF_HLL_HOP);
+    hipLaunchKernelGGL(hll_propagate_row16_kernel, dim3((unsigned)((r.g.rows() + 15) / 16 + r.lead)), dim3(256), 0, r.stream, r.g, r.hll_in,
+                       r.hll_out, r.cards_out, r.cards_stride, r.prm, r.hubs, r.lead);
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
@@ -227,35 +222,29 @@ extern "C" int ss_minhash_hop_rows(const ss_csr_graph *graph, const uint32_t *mh
                                    int64_t n_rows, void *stream)
 {
     using namespace ss;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr || !mh_in || !mh_out || n_rows < 0 || (n_rows > 0 && !rows)) return SS_ERR_INVALID_ARG;
+    if (!graph_given(graph) || !mh_in || !mh_out || n_rows < 0 || (n_rows > 0 && !rows)) return SS_ERR_INVALID_ARG;
     if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
-    const int64_t N = graph->num_nodes;
-    if (N == 0 || n_rows == 0) return SS_OK;
-    if (N >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 33)) return SS_ERR_INVALID_ARG;
-    if ((graph->hub_rows == nullptr) != (graph->hub_count == nullptr)) return SS_ERR_INVALID_ARG;
+    if (graph->num_nodes == 0 || n_rows == 0) return SS_OK;
+    if (!graph_fits(*graph) || n_rows >= ((int64_t)1 << 33)) return SS_ERR_INVALID_ARG;
     if (graph->row_begin != 0 || graph->row_end != 0) return SS_ERR_INVALID_ARG;  // a row list and a row range exclude each other
-    GraphArgs g = to_args(*graph);
-    g.row_list = rows;
-    g.n_list = n_rows;
-    hipStream_t s = (hipStream_t)stream;
-    const bool hubs = P == 128 && g.hub_rows && g.hub_count;  // (the hub units of the table hops are P = 128 only, as in ss_propagate)
-    const int lead = hub_lead_blocks(hubs);
-    const unsigned blocks = (unsigned)((n_rows + 3) / 4 + lead);
+    HopRequest r;
+    r.g = to_args(*graph);
+    r.mh_in = mh_in;
+    r.mh_out = mh_out;
+    r.P = P;
+    r.M = 256;
+    r.stream = (hipStream_t)stream;
+    schedule_hubs(r, P == 128);  // (the hub units of the table hops are P = 128 only, as in ss_propagate)
+    HopRequest listed = r;
+    listed.g.row_list = rows;
+    listed.g.n_list = n_rows;
     {
-        ProfileSpan span(s, SS_PROF_MINHASH_ROWS);
-        if (P == 128)
-            hipLaunchKernelGGL((propagate_kernel<128, 256>), dim3(blocks), dim3(256), 0, s, g, mh_in, mh_out, 128, (const uint8_t *)nullptr,
-                               (uint8_t *)nullptr, 256, (float *)nullptr, (int64_t)0, ss_hll_params{}, hubs, lead, (const uint8_t *)nullptr,
-                               (uint8_t *)nullptr, (float *)nullptr);
-        else
-            hipLaunchKernelGGL((propagate_kernel<0, 0>), dim3(blocks), dim3(256), 0, s, g, mh_in, mh_out, P, (const uint8_t *)nullptr,
-                               (uint8_t *)nullptr, 256, (float *)nullptr, (int64_t)0, ss_hll_params{}, false, 0, (const uint8_t *)nullptr,
-                               (uint8_t *)nullptr, (float *)nullptr);
+        ProfileSpan span(r.stream, SS_PROF_MINHASH_ROWS);
+        if (P == 128) launch_propagate_kernel<128, 256>(span, listed, n_rows, nullptr);
+        else launch_propagate_kernel<0, 0>(span, listed, n_rows, nullptr);
     }
     SS_LAUNCH_CHECK();
-    if (!hubs || lead > 0) return SS_OK;
-    GraphArgs all = to_args(*graph);
-    return launch_propagate_hub_only(all, mh_in, mh_out, nullptr, nullptr, nullptr, 0, ss_hll_params{}, s);
+    return r.hub_launch_follows() ? launch_propagate_hub_only(r) : SS_OK;
 }
 
 extern "C" int ss_propagate(const ss_csr_graph *graph, const uint32_t *mh_in, uint32_t *mh_out, int32_t P,
@@ -263,47 +252,53 @@ extern "C" int ss_propagate(const ss_csr_graph *graph, const uint32_t *mh_in, ui
                             float *cards_out, int64_t cards_stride, const ss_hll_params *prm, void *stream)
 {
     using namespace ss;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr) return SS_ERR_INVALID_ARG;
-    const int64_t N = graph->num_nodes;
-    if (N == 0) return SS_OK;
-    if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;
+    if (!graph_given(graph)) return SS_ERR_INVALID_ARG;
+    if (graph->num_nodes == 0) return SS_OK;
+    if (!row_range_ok(*graph)) return SS_ERR_INVALID_ARG;  // (here the row range is judged before the parameters)
     if ((mh_in == nullptr) != (mh_out == nullptr) || (hll_in == nullptr) != (hll_out == nullptr)) return SS_ERR_INVALID_ARG;
     if (!mh_out && !hll_out) return SS_ERR_INVALID_ARG;
     if (mh_out && (P <= 0 || (P & 3) || P > 2048)) return SS_ERR_INVALID_ARG;
     if (hll_out && (M < 16 || (M & (M - 1)) || M > 65536)) return SS_ERR_INVALID_ARG;
-    if (N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    if ((graph->hub_rows == nullptr) != (graph->hub_count == nullptr)) return SS_ERR_INVALID_ARG;
-    ss_hll_params p0 = {};
-    if (cards_out) {
-        if (!hll_out) return SS_ERR_INVALID_ARG;
-        const int rc = check_params(prm);
-        if (rc != SS_OK) return rc;
-        if ((1 << prm->p) != M) return SS_ERR_INVALID_ARG;
-        p0 = *prm;
+    if (!graph_fits(*graph)) return SS_ERR_INVALID_ARG;
+    HopRequest r;
+    r.mh_in = mh_in;
+    r.mh_out = mh_out;
+    r.P = P;
+    r.hll_in = hll_in;
+    r.hll_out = hll_out;
+    r.M = M;
+    r.cards_out = cards_out;
+    r.cards_stride = cards_stride;
+    r.stream = (hipStream_t)stream;
+    int rc = take_params(r, prm);
+    if (rc != SS_OK) return rc;
+    r.g = to_args(*graph);
+    if (r.g.rows() == 0) return SS_OK;
+    schedule_hubs(r, true);
+    if (hll_out && M == 256 && (!mh_out || P == 128)) {
+        // HLL alone: 4 destinations per wavefront.  Both sketches: one launch per sketch is faster than the two-sketch kernel
+        // (192 + 111 us vs 326 us on the bench graph): the HLL kernel keeps 4 destinations in flight per wavefront, the MinHash kernel
+        // one; each launch hosts the hub units of its own sketch
+        rc = launch_hll_hop(r);
+        if (rc == SS_OK && mh_out) rc = launch_minhash_hop(r, false);
+        return rc != SS_OK || !r.hub_launch_follows() ? rc : launch_propagate_hub_only(r);
     }
-    const GraphArgs g = to_args(*graph);
-    if (g.rows() == 0) return SS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool hubs = g.hub_rows && g.hub_count;
-    const int lead = hub_lead_blocks(hubs);
-    if (!mh_out && M == 256) {  // HLL alone: 4 destinations per wavefront
-        const int rc = launch_hll_hop(g, hll_in, hll_out, cards_out, cards_stride, p0, hubs, lead, s);
-        if (rc != SS_OK || lead > 0) return rc;
-        return launch_propagate_hub_only(g, nullptr, nullptr, hll_in, hll_out, cards_out, cards_stride, p0, s);
+    if (!hll_out && P == 128) {  // MinHash alone on the fast path: the row kernel that hosts its hub units
+        if (r.hubs) note_hub_call();  // (this path has always been counted twice; ss_debug_hub_calls is compared between builds)
+        {
+            ProfileSpan span(r.stream, SS_PROF_MINHASH_HOP);
+            launch_propagate_kernel<128, 256>(span, r, r.g.rows(), nullptr);
+        }
+        SS_LAUNCH_CHECK();
+        return r.hub_launch_follows() ? launch_propagate_hub_only(r) : SS_OK;
     }
-    if (mh_out && hll_out && P == 128 && M == 256) {
-        // both sketches: one launch per sketch is faster than the two-sketch kernel (192 + 111 us vs 326 us on the bench
-        // graph): the HLL kernel keeps 4 destinations in flight per wavefront, the MinHash kernel one; each launch hosts the hub
-        // units of its own sketch
-        int rc = launch_hll_hop(g, hll_in, hll_out, cards_out, cards_stride, p0, hubs, lead, s);
-        if (rc != SS_OK) return rc;
-        rc = launch_minhash_hop(g, mh_in, mh_out, hubs, lead, nullptr, nullptr, nullptr, 0, p0, s);
-        if (rc != SS_OK || lead > 0) return rc;
-        return launch_propagate_hub_only(g, mh_in, mh_out, hll_in, hll_out, cards_out, cards_stride, p0, s);
+    // any other shape: row sizes at run time, every row a wavefront's (no hub units, no span family)
+    r.hubs = false;
+    r.lead = 0;
+    {
+        ProfileSpan span(r.stream, SS_PROF_TAGS);
+        launch_propagate_kernel<0, 0>(span, r, r.g.rows(), nullptr);
     }
-    // the fast path needs both sketches (or the absent one's size irrelevant): P == 128 and M == 256
-    const bool fast = (!mh_out || P == 128) && (!hll_out || M == 256);
-    if (fast)
-        return launch_propagate<128, 256>(g, mh_in, mh_out, 128, hll_in, hll_out, 256, cards_out, cards_stride, p0, s);
-    return launch_propagate<0, 0>(g, mh_in, mh_out, P, hll_in, hll_out, M, cards_out, cards_stride, p0, s);
+    SS_LAUNCH_CHECK();
+    return SS_OK;
 }

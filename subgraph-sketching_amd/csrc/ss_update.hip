@@ -392,15 +392,6 @@ __global__ __launch_bounds__(kUpdHubThreads) void update_hub_first_kernel(GraphA
     }
 }
 
-template <int PPL>
-static void launch_update_first_minhash(const GraphArgs &g, const int32_t *list, const int32_t *n_rows, const int32_t *n_hubs, unsigned row_grid,
-                                        unsigned hub_grid, const uint64_t *a, const uint64_t *b, uint32_t *mh_out, int p, hipStream_t s)
-{
-    hipLaunchKernelGGL((update_first_minhash_rows_kernel<PPL>), dim3(row_grid), dim3(256), 0, s, g, list, n_rows, a, b, mh_out, p);
-    hipLaunchKernelGGL((update_hub_first_kernel<PPL, true, false>), dim3(hub_grid), dim3(kUpdHubThreads), 0, s, g, list, n_hubs, a, b, mh_out, p,
-                       (uint8_t *)nullptr, (float *)nullptr, (int64_t)0, ss_hll_params{});
-}
-
 }  // namespace ss
 
 extern "C" size_t ss_update_workspace_bytes(int64_t N, int32_t h)
@@ -415,10 +406,11 @@ extern "C" int ss_update_mark(const ss_csr_graph *graph, const int64_t *added_ds
 {
     using namespace ss;
     if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr || n_added < 0 || n_removed < 0) return SS_ERR_INVALID_ARG;
+    if (!graph_given(graph) || n_added < 0 || n_removed < 0) return SS_ERR_INVALID_ARG;
     if ((n_added > 0 && !added_dst) || (n_removed > 0 && !removed_dst)) return SS_ERR_INVALID_ARG;
     const int64_t N = graph->num_nodes;
     if (N == 0) return SS_OK;
+    // (written out, here and in ss_update_hop: the update lists its own hub rows and asks nothing of hub_rows / hub_count)
     if (N >= ((int64_t)1 << 31) || !cards_old || cards_stride < 1 || !workspace || !graph->col) return SS_ERR_INVALID_ARG;
     if (graph->row_begin != 0 || graph->row_end != 0) return SS_ERR_INVALID_ARG;
     if (workspace_bytes < ss_update_workspace_bytes(N, h)) return SS_ERR_WORKSPACE;
@@ -451,7 +443,7 @@ extern "C" int ss_update_hop(const ss_csr_graph *graph, int32_t hop, int32_t h, 
 {
     using namespace ss;
     if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
-    if (!graph || graph->num_nodes < 0 || !graph->rowptr || hop < 1 || hop > h) return SS_ERR_INVALID_ARG;
+    if (!graph_given(graph) || hop < 1 || hop > h) return SS_ERR_INVALID_ARG;
     if (P <= 0 || (P & 3) || P > 2048) return SS_ERR_INVALID_ARG;
     if (p < 4 || p > 16) return SS_ERR_UNSUPPORTED;
     if (!mh_in && (hop != 1 || P % kWave || P > 256)) return SS_ERR_UNSUPPORTED;  // MinHash from node ids: the first hop, 64 .. 256 permutations
@@ -461,51 +453,69 @@ extern "C" int ss_update_hop(const ss_csr_graph *graph, int32_t hop, int32_t h, 
     if (N >= ((int64_t)1 << 31) || !mh_out || !hll_out || !cards_out || !workspace || !graph->col) return SS_ERR_INVALID_ARG;
     if (!mh_in && (!a || !b)) return SS_ERR_INVALID_ARG;
     if (graph->row_begin != 0 || graph->row_end != 0) return SS_ERR_INVALID_ARG;
-    const int rc = check_params(prm);
+    HopRequest r;
+    r.a = a;
+    r.b = b;
+    r.P = P;
+    r.p = p;
+    r.M = 1 << p;
+    r.mh_in = mh_in;
+    r.mh_out = mh_out;
+    r.hll_in = hll_in;
+    r.hll_out = hll_out;
+    r.cards_out = cards_out;
+    r.cards_stride = cards_stride;
+    r.stream = (hipStream_t)stream;
+    const int rc = take_params(r, prm);
     if (rc != SS_OK) return rc;
-    if (prm->p != p) return SS_ERR_INVALID_ARG;
     if (workspace_bytes < ss_update_workspace_bytes(N, h)) return SS_ERR_WORKSPACE;
-    const GraphArgs g = to_args(*graph);
+    r.g = to_args(*graph);
     const UpdateWs w = carve_update_ws(const_cast<void *>(workspace), N, h);
     const int32_t *list = w.list[hop - 1];
     const int32_t *n_rows = w.counters + 4 * hop + 1, *n_hubs = w.counters + 4 * hop + 2;
-    hipStream_t s = (hipStream_t)stream;
-    const int M = 1 << p;
     // launches are sized by N, the bound the host knows; the workgroups stride over the device-side counts
     const unsigned grid4 = (unsigned)((N + 3) / 4 < kUpdRowGrid ? (N + 3) / 4 : kUpdRowGrid);
     const unsigned grid16 = (unsigned)((N + 15) / 16 < kUpdRowGrid ? (N + 15) / 16 : kUpdRowGrid);
     const unsigned hub_grid = (unsigned)(N < kUpdHubGrid ? N : kUpdHubGrid);
+    // the listed hub rows of a first hop, one sketch per launch; the other sketch's arguments are nulls and zeros
+    const auto hub_first = [&](auto ppl, auto mh, auto hll) {
+        constexpr bool MH = decltype(mh)::value, HLL = decltype(hll)::value;
+        hipLaunchKernelGGL((update_hub_first_kernel<decltype(ppl)::value, MH, HLL>), dim3(hub_grid), dim3(kUpdHubThreads), 0, r.stream, r.g, list, n_hubs,
+                           MH ? r.a : nullptr, MH ? r.b : nullptr, MH ? r.mh_out : nullptr, r.p, HLL ? r.hll_out : nullptr,
+                           HLL ? r.cards_out : nullptr, HLL ? r.cards_stride : (int64_t)0, HLL ? r.prm : ss_hll_params{});
+    };
 
     // ---- HLL rows + cardinalities
-    if (!hll_in) {
-        hipLaunchKernelGGL(update_first_hll_rows_kernel, dim3(grid16), dim3(256), 0, s, g, list, n_rows, p, hll_out, cards_out, cards_stride, *prm);
+    if (!r.hll_in) {
+        hipLaunchKernelGGL(update_first_hll_rows_kernel, dim3(grid16), dim3(256), 0, r.stream, r.g, list, n_rows, r.p, r.hll_out, r.cards_out,
+                           r.cards_stride, r.prm);
         SS_LAUNCH_CHECK();
-        hipLaunchKernelGGL((update_hub_first_kernel<1, false, true>), dim3(hub_grid), dim3(kUpdHubThreads), 0, s, g, list, n_hubs,
-                           (const uint64_t *)nullptr, (const uint64_t *)nullptr, (uint32_t *)nullptr, p, hll_out, cards_out, cards_stride, *prm);
-    } else if (M == 256) {
-        hipLaunchKernelGGL(update_hll256_rows_kernel, dim3(grid16), dim3(256), 0, s, g, list, n_rows, hll_in, hll_out, cards_out, cards_stride, *prm);
+        hub_first(std::integral_constant<int, 1>{}, std::false_type{}, std::true_type{});
+    } else if (r.M == 256) {
+        hipLaunchKernelGGL(update_hll256_rows_kernel, dim3(grid16), dim3(256), 0, r.stream, r.g, list, n_rows, r.hll_in, r.hll_out, r.cards_out,
+                           r.cards_stride, r.prm);
     } else {
-        hipLaunchKernelGGL(update_hll_rows_kernel, dim3(grid4), dim3(256), 0, s, g, list, n_rows, hll_in, hll_out, M, cards_out, cards_stride, *prm);
+        hipLaunchKernelGGL(update_hll_rows_kernel, dim3(grid4), dim3(256), 0, r.stream, r.g, list, n_rows, r.hll_in, r.hll_out, r.M, r.cards_out,
+                           r.cards_stride, r.prm);
     }
     SS_LAUNCH_CHECK();
     // ---- MinHash rows
-    if (!mh_in) {
-        switch (P / kWave) {
-            case 1: launch_update_first_minhash<1>(g, list, n_rows, n_hubs, grid4, hub_grid, a, b, mh_out, p, s); break;
-            case 2: launch_update_first_minhash<2>(g, list, n_rows, n_hubs, grid4, hub_grid, a, b, mh_out, p, s); break;
-            case 3: launch_update_first_minhash<3>(g, list, n_rows, n_hubs, grid4, hub_grid, a, b, mh_out, p, s); break;
-            default: launch_update_first_minhash<4>(g, list, n_rows, n_hubs, grid4, hub_grid, a, b, mh_out, p, s); break;
-        }
-    } else if (P == 128) {
-        hipLaunchKernelGGL((update_minhash_rows_kernel<128>), dim3(grid4), dim3(256), 0, s, g, list, n_rows, mh_in, mh_out, P);
+    if (!r.mh_in) {
+        for_ppl(r.P, [&](auto ppl) {
+            hipLaunchKernelGGL((update_first_minhash_rows_kernel<decltype(ppl)::value>), dim3(grid4), dim3(256), 0, r.stream, r.g, list, n_rows, r.a, r.b,
+                               r.mh_out, r.p);
+            hub_first(ppl, std::true_type{}, std::false_type{});
+        });
+    } else if (r.P == 128) {
+        hipLaunchKernelGGL((update_minhash_rows_kernel<128>), dim3(grid4), dim3(256), 0, r.stream, r.g, list, n_rows, r.mh_in, r.mh_out, r.P);
     } else {
-        hipLaunchKernelGGL((update_minhash_rows_kernel<0>), dim3(grid4), dim3(256), 0, s, g, list, n_rows, mh_in, mh_out, P);
+        hipLaunchKernelGGL((update_minhash_rows_kernel<0>), dim3(grid4), dim3(256), 0, r.stream, r.g, list, n_rows, r.mh_in, r.mh_out, r.P);
     }
     SS_LAUNCH_CHECK();
     // ---- listed hub rows of the sketches that read a table (one launch serves both when both do)
-    if (mh_in || hll_in) {
-        hipLaunchKernelGGL(update_hub_table_kernel, dim3(hub_grid), dim3(kUpdHubThreads), 0, s, g, list, n_hubs, mh_in, mh_in ? mh_out : nullptr, P,
-                           hll_in, hll_in ? hll_out : nullptr, M, cards_out, cards_stride, *prm);
+    if (r.mh_in || r.hll_in) {
+        hipLaunchKernelGGL(update_hub_table_kernel, dim3(hub_grid), dim3(kUpdHubThreads), 0, r.stream, r.g, list, n_hubs, r.mh_in,
+                           r.mh_in ? r.mh_out : nullptr, r.P, r.hll_in, r.hll_in ? r.hll_out : nullptr, r.M, r.cards_out, r.cards_stride, r.prm);
         SS_LAUNCH_CHECK();
     }
     return SS_OK;

@@ -93,6 +93,326 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.ss_propagate(byref(g), fake, fake, 128, None, None, 256, None, 0, None, None) == -1   # empty / reversed row range
 
 
+# ---- return codes of the table-hop entry points ---------------------------------------------------------------------------------
+# Every call below returns before a launch.  Each entry point has a base call that passes every check but the last one before its
+# first launch (an empty row range, a row range beside a row list, a workspace of 0 bytes) and a list of named edits to it: every
+# bad-argument class of its preamble and the early SS_OK exits.  _PINNED[entry][i][j] is the code with edits i and j applied together
+# (i == j: edit i alone), so a row shows which of two errors is reported: '0' SS_OK, 'I' SS_ERR_INVALID_ARG, 'W' SS_ERR_WORKSPACE,
+# 'U' SS_ERR_UNSUPPORTED.  The letters were produced by the library as it stood before the host side of these units was rewritten
+# around one request record, and that rewrite had to reproduce them.
+_FAKE = 8          # a non-null pointer that is never dereferenced
+_LETTER = {0: '0', -1: 'I', -3: 'W', -4: 'U'}
+
+
+def _edit(**fields):
+    """an edit: 'g.x' sets field x of the graph, 'prm.x' of the HLL parameters, anything else the argument of that name"""
+    def apply(s):
+        for key, value in fields.items():
+            where, _, name = key.rpartition('.')
+            if not where:
+                s[name] = value
+            elif s[where] is not None:   # (another edit may have taken the whole struct away)
+                s[where][name] = value
+    return apply
+
+
+def _graph_edits():
+    return [('no graph', _edit(g=None)), ('N < 0', _edit(**{'g.num_nodes': -1})), ('no rowptr', _edit(**{'g.rowptr': None})),
+            ('N = 0', _edit(**{'g.num_nodes': 0})), ('N = 2^31', _edit(**{'g.num_nodes': 1 << 31})),
+            ('hub_rows without hub_count', _edit(**{'g.hub_rows': _FAKE}))]
+
+
+def _prm_edits():
+    return [('no prm', _edit(prm=None)), ('prm.p = 3', _edit(**{'prm.p': 3})), ('prm.n_tbl = 5', _edit(**{'prm.n_tbl': 5})),
+            ('prm.bias missing', _edit(**{'prm.bias': None})), ('prm.p = 9', _edit(**{'prm.p': 9}))]
+
+
+def _state(**args):
+    g = dict(rowptr=_FAKE, col=_FAKE, num_nodes=4, n_self_loops=0, hub_threshold=512, row_begin=2, row_end=2)   # an empty row range
+    prm = dict(p=8, n_tbl=6, raw_est=_FAKE, bias=_FAKE, lc_table=_FAKE)
+    return dict(g=g, prm=prm, **args)
+
+
+def _table_hop_entries():
+    reversed_range = ('reversed row range', _edit(**{'g.row_begin': 3, 'g.row_end': 1}))
+    entries = {}
+    entries['ss_propagate'] = (
+        _state(mh_in=_FAKE, mh_out=_FAKE, P=128, hll_in=_FAKE, hll_out=_FAKE, M=256, cards_out=_FAKE, cards_stride=1),
+        ('g', 'mh_in', 'mh_out', 'P', 'hll_in', 'hll_out', 'M', 'cards_out', 'cards_stride', 'prm', None),
+        _graph_edits() + [reversed_range, ('mh_in alone', _edit(mh_out=None)), ('hll_out alone', _edit(hll_in=None)),
+                          ('no tables', _edit(mh_in=None, mh_out=None, hll_in=None, hll_out=None)), ('P = 130', _edit(P=130)),
+                          ('M = 100', _edit(M=100)), ('cards without HLL', _edit(hll_in=None, hll_out=None)),
+                          ('MinHash alone', _edit(hll_in=None, hll_out=None, cards_out=None)),
+                          ('HLL alone', _edit(mh_in=None, mh_out=None)), ('M = 512', _edit(M=512))] + _prm_edits())
+    entries['ss_first_hop'] = (
+        _state(a=_FAKE, b=_FAKE, P=128, mh_out=_FAKE, p=8, hll_out=_FAKE, cards_out=_FAKE, cards_stride=1),
+        ('g', 'a', 'b', 'P', 'mh_out', 'p', 'hll_out', 'cards_out', 'cards_stride', 'prm', None),
+        _graph_edits() + [reversed_range, ('p = 6', _edit(p=6)), ('P = 100', _edit(P=100)), ('P = 0', _edit(P=0)), ('P = 320', _edit(P=320)),
+                          ('no tables', _edit(mh_out=None, hll_out=None)), ('no a', _edit(a=None)), ('cards without HLL', _edit(hll_out=None)),
+                          ('MinHash alone', _edit(hll_out=None, cards_out=None)), ('HLL alone', _edit(mh_out=None, a=None, b=None))]
+        + _prm_edits())
+    fused = [reversed_range, ('p = 6', _edit(p=6)), ('P = 100', _edit(P=100)), ('P = 192', _edit(P=192)),
+             ('P = 192, no mh2_out', _edit(P=192, mh2_out=None)), ('no mh1_out', _edit(mh1_out=None)), ('no b', _edit(b=None)),
+             ('no hll1', _edit(hll1=None)), ('no hll2_out', _edit(hll2_out=None)),
+             # (the only check behind the empty-range exit: with cards1_out the stage computes hop 1 too and wants cards2_out)
+             ('cards1_out without cards2_out, whole graph', _edit(cards2_out=None, **{'g.row_begin': 0, 'g.row_end': 0}))]
+    entries['ss_fused_hop_stage'] = (
+        _state(a=_FAKE, b=_FAKE, P=128, mh1_out=_FAKE, mh2_out=_FAKE, p=8, hll1=_FAKE, cards1_out=_FAKE, hll2_out=_FAKE, cards2_out=_FAKE,
+               cards_stride=1),
+        ('g', 'a', 'b', 'P', 'mh1_out', 'mh2_out', 'p', 'hll1', 'cards1_out', 'hll2_out', 'cards2_out', 'cards_stride', 'prm', None),
+        _graph_edits() + fused + _prm_edits())
+    entries['ss_fused_hop_stage_records'] = (
+        dict(entries['ss_fused_hop_stage'][0], records=_FAKE, num_edges=8),
+        entries['ss_fused_hop_stage'][1][:-1] + ('records', 'num_edges', None),
+        _graph_edits() + fused + [('no records', _edit(records=None)), ('num_edges = -1', _edit(num_edges=-1))] + _prm_edits())
+    entries['ss_minhash_hop_rows'] = (
+        dict(_state(mh_in=_FAKE, mh_out=_FAKE, P=128, rows=_FAKE, n_rows=4), g=dict(_state()['g'], row_begin=1, row_end=3)),
+        ('g', 'mh_in', 'mh_out', 'P', 'rows', 'n_rows', None),
+        _graph_edits() + [('no mh_in', _edit(mh_in=None)), ('no mh_out', _edit(mh_out=None)), ('n_rows < 0', _edit(n_rows=-1)),
+                          ('no rows', _edit(rows=None)), ('P = 130', _edit(P=130)), ('P = 0', _edit(P=0)), ('P = 2052', _edit(P=2052)),
+                          ('P = 100', _edit(P=100)), ('empty list', _edit(rows=None, n_rows=0)), ('n_rows = 2^33', _edit(n_rows=1 << 33))])
+    whole = dict(_state()['g'], row_begin=0, row_end=0)
+    update_graph = [e for e in _graph_edits() if e[0] != 'hub_rows without hub_count'] + [
+        ('no col', _edit(**{'g.col': None})), ('a row range', _edit(**{'g.row_begin': 1, 'g.row_end': 3})), ('no workspace', _edit(workspace=None)),
+        ('h = 0', _edit(h=0)), ('h = 4', _edit(h=4))]
+    entries['ss_update_mark'] = (
+        dict(_state(added_dst=_FAKE, n_added=2, removed_dst=_FAKE, n_removed=2, cards_old=_FAKE, cards_stride=1, h=2, err_flag=_FAKE,
+                    workspace=_FAKE, workspace_bytes=0), g=whole),
+        ('g', 'added_dst', 'n_added', 'removed_dst', 'n_removed', 'cards_old', 'cards_stride', 'h', 'err_flag', 'workspace', 'workspace_bytes',
+         None),
+        update_graph + [('n_added < 0', _edit(n_added=-1)), ('no added_dst', _edit(added_dst=None)), ('no removed_dst', _edit(removed_dst=None)),
+                        ('no edits', _edit(added_dst=None, n_added=0, removed_dst=None, n_removed=0)), ('no cards_old', _edit(cards_old=None)),
+                        ('cards_stride = 0', _edit(cards_stride=0))])
+    entries['ss_update_hop'] = (
+        dict(_state(hop=1, h=2, a=_FAKE, b=_FAKE, mh_in=_FAKE, mh_out=_FAKE, P=128, hll_in=_FAKE, hll_out=_FAKE, p=8, cards_out=_FAKE,
+                    cards_stride=1, workspace=_FAKE, workspace_bytes=0), g=whole),
+        ('g', 'hop', 'h', 'a', 'b', 'mh_in', 'mh_out', 'P', 'hll_in', 'hll_out', 'p', 'cards_out', 'cards_stride', 'prm', 'workspace',
+         'workspace_bytes', None),
+        update_graph + [('hop = 0', _edit(hop=0)), ('hop = 3', _edit(hop=3)), ('hop = 2', _edit(hop=2)), ('P = 130', _edit(P=130)),
+                        ('P = 100', _edit(P=100)), ('p = 3', _edit(p=3)), ('p = 6', _edit(p=6)), ('no mh_in', _edit(mh_in=None)),
+                        ('no hll_in', _edit(hll_in=None)), ('no mh_out', _edit(mh_out=None)), ('no hll_out', _edit(hll_out=None)),
+                        ('no cards_out', _edit(cards_out=None)), ('no a', _edit(a=None))] + _prm_edits())
+    return entries
+
+
+def _return_code(lib, nat, entry, state, order, edits):
+    import copy
+    from ctypes import byref
+    s = copy.deepcopy(state)
+    for apply in edits:
+        apply(s)
+    keep = []   # the structs outlive the call
+    def arg(name):
+        if name is None:
+            return None     # the stream
+        value = s[name]
+        if name == 'g' and value is not None:
+            keep.append(nat.CsrGraphStruct(**value))
+            return byref(keep[-1])
+        if name == 'prm' and value is not None:
+            keep.append(nat.HllParams(**value))
+            return byref(keep[-1])
+        return value
+    return getattr(lib, entry)(*[arg(name) for name in order])
+
+
+def _return_code_rows(entry):
+    import subgraph_sketching_amd as ssa
+    nat = ssa._native
+    state, order, edits = _table_hop_entries()[entry]
+    rows = []
+    for name_i, edit_i in edits:
+        codes = [_return_code(nat.lib(), nat, entry, state, order, [edit_i] if edit_i is edit_j else [edit_i, edit_j]) for _, edit_j in edits]
+        rows.append((name_i, ''.join(_LETTER.get(c, '?') for c in codes)))
+    return rows
+
+
+_PINNED = {
+    'ss_propagate': {
+        'base call': '0',
+        'no graph': 'IIIIIIIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIIIIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'III0I0000000000000000',
+        'N = 2^31': 'III0IIIIIIIIIIIIIIIII',
+        'hub_rows without hub_count': 'III0IIIIIIIIIIIIIIIII',
+        'reversed row range': 'III0IIIIIIIIIIIIIIIII',
+        'mh_in alone': 'III0IIIIIIIIII0IIIIII',
+        'hll_out alone': 'III0IIIIIIIII0IIIIIII',
+        'no tables': 'III0IIIIIIIIIIIIIIIII',
+        'P = 130': 'III0IIIIIIIIII0IIIIII',
+        'M = 100': 'III0IIIIIIIII0IIIIIII',
+        'cards without HLL': 'III0IIIIIIIII0IIIIIII',
+        'MinHash alone': 'III0IIII0II000I000000',
+        'HLL alone': 'III0III0II0III0IIUIII',
+        'M = 512': 'III0IIIIIIIII0IIIUII0',
+        'no prm': 'III0IIIIIIIII0IIIIIII',
+        'prm.p = 3': 'III0IIIIIIIII0UUIUUUI',
+        'prm.n_tbl = 5': 'III0IIIIIIIII0IIIUIII',
+        'prm.bias missing': 'III0IIIIIIIII0IIIUIII',
+        'prm.p = 9': 'III0IIIIIIIII0I0IUIII',
+    },
+    'ss_first_hop': {
+        'base call': '0',
+        'no graph': 'IIIIIIIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIIIIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'III0I00UUUU0000000000',
+        'N = 2^31': 'III0IIIUUUUIIIIIIIIII',
+        'hub_rows without hub_count': 'III0IIIUUUUIIIIIIIIII',
+        'reversed row range': 'III0IIIUUUUIIIIIIUIII',
+        'p = 6': 'IIIUUUUUUUUIUI0UUUUUU',
+        'P = 100': 'IIIUUUUUUUUUUUUUUUUUU',
+        'P = 0': 'IIIUUUUUUUUUUUUUUUUUU',
+        'P = 320': 'IIIUUUUUUUUUUUUUUUUUU',
+        'no tables': 'III0IIIIUUUIIIIIIIIII',
+        'no a': 'III0IIIUUUUIIII0IIIII',
+        'cards without HLL': 'III0IIIIUUUIII0IIIIII',
+        'MinHash alone': 'III0III0UUUII00I00000',
+        'HLL alone': 'III0IIIUUUUI0II0IUIII',
+        'no prm': 'III0IIIUUUUIII0IIIIII',
+        'prm.p = 3': 'III0IIUUUUUIII0UIUUUI',
+        'prm.n_tbl = 5': 'III0IIIUUUUIII0IIUIII',
+        'prm.bias missing': 'III0IIIUUUUIII0IIUIII',
+        'prm.p = 9': 'III0IIIUUUUIII0IIUIII',
+    },
+    'ss_fused_hop_stage': {
+        'base call': '0',
+        'no graph': 'IIIIIIIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIIIIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'III0I00UUU00000000000',
+        'N = 2^31': 'III0IIIUUUIIIIIIIIIII',
+        'hub_rows without hub_count': 'III0IIIUUUIIIIIIIIIII',
+        'reversed row range': 'III0IIIUUUIIIIIIIUIII',
+        'p = 6': 'IIIUUUUUUUUUUUUUUUUUU',
+        'P = 100': 'IIIUUUUUUU0UUUUUUUUUU',
+        'P = 192': 'IIIUUUUUUU0UUUUUUUUUU',
+        'P = 192, no mh2_out': 'III0IIIUU00IIIIIIUIII',
+        'no mh1_out': 'III0IIIUUUIIIIIIIIIII',
+        'no b': 'III0IIIUUUIIIIIIIIIII',
+        'no hll1': 'III0IIIUUUIIIIIIIIIII',
+        'no hll2_out': 'III0IIIUUUIIIIIIIIIII',
+        'cards1_out without cards2_out, whole graph': 'III0IIIUUUIIIIIIIIIII',
+        'no prm': 'III0IIIUUUIIIIIIIIIII',
+        'prm.p = 3': 'III0IIUUUUUIIIIIIUUUI',
+        'prm.n_tbl = 5': 'III0IIIUUUIIIIIIIUIII',
+        'prm.bias missing': 'III0IIIUUUIIIIIIIUIII',
+        'prm.p = 9': 'III0IIIUUUIIIIIIIUIII',
+    },
+    'ss_fused_hop_stage_records': {
+        'base call': '0',
+        'no graph': 'IIIIIIIIIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIIIIIIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'III0I00UUU0000000000000',
+        'N = 2^31': 'III0IIIUUUIIIIIIIIIIIII',
+        'hub_rows without hub_count': 'III0IIIUUUIIIIIIIIIIIII',
+        'reversed row range': 'III0IIIUUUIIIIIIIIIUIII',
+        'p = 6': 'IIIUUUUUUUUUUUUUUUUUUUU',
+        'P = 100': 'IIIUUUUUUU0UUUUUUUUUUUU',
+        'P = 192': 'IIIUUUUUUU0UUUUUUUUUUUU',
+        'P = 192, no mh2_out': 'III0IIIUU00IIIII00IUIII',
+        'no mh1_out': 'III0IIIUUUIIIIIIIIIIIII',
+        'no b': 'III0IIIUUUIIIIIIIIIIIII',
+        'no hll1': 'III0IIIUUUIIIIIIIIIIIII',
+        'no hll2_out': 'III0IIIUUUIIIIIIIIIIIII',
+        'cards1_out without cards2_out, whole graph': 'III0IIIUUUIIIIIIIIIIIII',
+        'no records': 'III0IIIUUU0IIIII00IUIII',
+        'num_edges = -1': 'III0IIIUUU0IIIII00IUIII',
+        'no prm': 'III0IIIUUUIIIIIIIIIIIII',
+        'prm.p = 3': 'III0IIUUUUUIIIIIUUIUUUI',
+        'prm.n_tbl = 5': 'III0IIIUUUIIIIIIIIIUIII',
+        'prm.bias missing': 'III0IIIUUUIIIIIIIIIUIII',
+        'prm.p = 9': 'III0IIIUUUIIIIIIIIIUIII',
+    },
+    'ss_minhash_hop_rows': {
+        'base call': 'I',
+        'no graph': 'IIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIIIIIIIII',
+        'N = 0': 'III0I0IIIIIII000',
+        'N = 2^31': 'III0IIIIIIIIII0I',
+        'hub_rows without hub_count': 'III0IIIIIIIIII0I',
+        'no mh_in': 'IIIIIIIIIIIIIIII',
+        'no mh_out': 'IIIIIIIIIIIIIIII',
+        'n_rows < 0': 'IIIIIIIIIIIIII0I',
+        'no rows': 'IIIIIIIIIIIIII0I',
+        'P = 130': 'IIIIIIIIIIIIIIII',
+        'P = 0': 'IIIIIIIIIIIIIIII',
+        'P = 2052': 'IIIIIIIIIIIIIIII',
+        'P = 100': 'III0IIIIIIIIII0I',
+        'empty list': 'III000III0III00I',
+        'n_rows = 2^33': 'III0IIIIIIIIII0I',
+    },
+    'ss_update_mark': {
+        'base call': 'W',
+        'no graph': 'IIIIIIIIUUIIIIII',
+        'N < 0': 'III0IIIIUUIIIIII',
+        'no rowptr': 'IIIIIIIIUUIIIIII',
+        'N = 0': 'III0I000UUIII000',
+        'N = 2^31': 'III0IIIIUUIIIIII',
+        'no col': 'III0IIIIUUIIIIII',
+        'a row range': 'III0IIIIUUIIIIII',
+        'no workspace': 'III0IIIIUUIIIIII',
+        'h = 0': 'UUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUU',
+        'n_added < 0': 'IIIIIIIIUUIIIWII',
+        'no added_dst': 'IIIIIIIIUUIIIWII',
+        'no removed_dst': 'IIIIIIIIUUIIIWII',
+        'no edits': 'III0IIIIUUIWWWII',
+        'no cards_old': 'III0IIIIUUIIIIII',
+        'cards_stride = 0': 'III0IIIIUUIIIIII',
+    },
+    'ss_update_hop': {
+        'base call': 'W',
+        'no graph': 'IIIIIIIIUUIIIIIIIIIIIIIIIIII',
+        'N < 0': 'III0IIIIUUIIIIIIIIIIIIIIIIII',
+        'no rowptr': 'IIIIIIIIUUIIIIIIIIIIIIIIIIII',
+        'N = 0': 'III0I000UUII0I0U000000000000',
+        'N = 2^31': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'no col': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'a row range': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'no workspace': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'hop = 0': 'IIIIIIIIUUIIWIIIIIIIIIIIIIII',
+        'hop = 3': 'IIIIIIIIUUIIWIIIIIIIIIIIIIII',
+        'hop = 2': 'III0IIIIUUIIWIWUIUUIIIWIUIII',
+        'P = 130': 'IIIIIIIIUUIIIIWIIIIIIIIIIIII',
+        'P = 100': 'III0IIIIUUIIWIWUIUWIIIWIUIII',
+        'p = 3': 'IIIUUUUUUUIIUIUUIUUUUUUUUUUU',
+        'p = 6': 'III0IIIIUUIIIIIUIIUIIIIIUIII',
+        'no mh_in': 'III0IIIIUUIIUIUUIWWIIIIIUIII',
+        'no hll_in': 'III0IIIIUUIIUIWUUWWIIIWIUIII',
+        'no mh_out': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'no hll_out': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'no cards_out': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'no a': 'III0IIIIUUIIWIWUIIWIIIWIUIII',
+        'no prm': 'III0IIIIUUIIIIIUIIIIIIIIIIII',
+        'prm.p = 3': 'III0IIIIUUIIUIUUUUUIIIUIUUUI',
+        'prm.n_tbl = 5': 'III0IIIIUUIIIIIUIIIIIIIIUIII',
+        'prm.bias missing': 'III0IIIIUUIIIIIUIIIIIIIIUIII',
+        'prm.p = 9': 'III0IIIIUUIIIIIUIIIIIIIIUIII',
+    },
+}
+
+
+@pytest.mark.parametrize('entry', sorted(_table_hop_entries()))
+def test_table_hop_return_codes_are_pinned(entry):
+    """every bad-argument class of the table-hop entry points, alone and in pairs, and their early SS_OK exits: the codes of the
+    library before its host side was refactored (a '?' would be a code outside the four: a launch was reached)"""
+    import subgraph_sketching_amd as ssa
+    nat = ssa._native
+    state, order, _ = _table_hop_entries()[entry]
+    base = _return_code(nat.lib(), nat, entry, state, order, [])
+    assert _LETTER.get(base) == _PINNED[entry]['base call'], base
+    got = _return_code_rows(entry)
+    assert [name for name, _ in got] == [name for name in _PINNED[entry] if name != 'base call']
+    for name, row in got:
+        assert row == _PINNED[entry][name], (entry, name, row, _PINNED[entry][name])
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     import subgraph_sketching_amd as ssa
     monkeypatch.setattr(ssa._native, '_lib', None)

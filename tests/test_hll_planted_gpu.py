@@ -449,3 +449,64 @@ def test_update_moves_a_target_across_the_linear_counting_limit(ssa, dev, monkey
     _check_build(table, cards, n_tbl, True, f'n_tbl={n_tbl} threshold={threshold}: edge added')
     table, cards = eh.update_hash_tables(table, cards, nb.n, base, removed=extra, copy=True)
     _check_build(table, cards, n_tbl, False, f'n_tbl={n_tbl} threshold={threshold}: edge removed')
+
+
+# ---- single-sketch table hops on hub rows, under both hub schedules ------------------------------------------------------------------------
+_SINGLE_SKETCH_HOPS = r"""
+import sys
+from argparse import Namespace
+from ctypes import byref
+import numpy as np, torch
+sys.path[:0] = [%r, %r]
+import subgraph_sketching_amd as ssa
+import hll_planted as hp
+from subgraph_sketching_amd._runtime import _ptr, _stream
+dev = torch.device('cuda:0')
+d = np.load(sys.argv[1])
+n = int(d['n'])
+csr = ssa.hashing.build_csr(torch.from_numpy(d['edge_index']).to(dev), n, dev, check=True, hub_threshold=8)
+csr.use_inferred_self_loops = True
+eh = ssa.ElphHashes(Namespace(max_hash_hops=2, hll_p=8, minhash_num_perm=128, floor_sf=False, use_zero_one=True))
+eh.hll_tables = hp.tables(8, None)
+prm = eh._params(dev)
+mh1, hll1 = torch.from_numpy(d['mh1'].view(np.int32)).to(dev), torch.from_numpy(d['hll1']).to(dev)
+mh2, hll2 = torch.full_like(mh1, 0x5A5A5A5A), torch.full_like(hll1, 255)
+cards = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
+lib, graph, s = ssa._native.lib(), csr.struct(), _stream(dev)
+lib.ss_debug_hub_calls(1)
+rc_mh = lib.ss_propagate(byref(graph), _ptr(mh1), _ptr(mh2), 128, None, None, 0, None, 0, None, s)
+calls_mh = lib.ss_debug_hub_calls(1)
+rc_hll = lib.ss_propagate(byref(graph), None, None, 0, _ptr(hll1), _ptr(hll2), 256, _ptr(cards), 1, byref(prm.struct), s)
+calls_hll = lib.ss_debug_hub_calls(1)
+torch.cuda.synchronize()
+np.savez(sys.argv[2], rc=[rc_mh, rc_hll], calls=[calls_mh, calls_hll], hubs=int(csr.hub_count[0]), mega=int(csr.mega_count[0]),
+         mh2=mh2.cpu().numpy().view(np.uint32), hll2=hll2.cpu().numpy(), cards=cards.cpu().numpy())
+"""
+
+
+@pytest.mark.parametrize('launches', ['0', '1'])
+def test_single_sketch_table_hops_on_hub_rows_under_both_hub_schedules(tmp_path, launches):
+    """ss_propagate with the MinHash table alone and with the HLL table alone on the planted neighbourhoods at a hub threshold of 8 (the
+    targets are hub rows, `big` a mega row), from the oracle's hop-1 tables: the hop-2 tables equal the oracle's, the cardinalities pass
+    _check_counts.  Once with the hub units hosted by the row launches and once as launches of their own -- SS_HUB_LAUNCHES is read once
+    per process, hence a child process per schedule.  The MinHash-alone call is counted twice by ss_debug_hub_calls, the HLL-alone call
+    once, as they always were."""
+    import os
+    import subprocess
+    import sys
+    from conftest import REPO
+    nb = _hood()
+    t, prm, _ = _setup(8, None)
+    _, otab, _ = _oracle_build(None, False)
+    src, out = str(tmp_path / 'in.npz'), str(tmp_path / 'out.npz')
+    np.savez(src, n=nb.n, edge_index=nb.edge_index, mh1=otab[1]['minhash'].astype(np.uint32), hll1=otab[1]['hll'].astype(np.uint8))
+    env = dict(os.environ, SS_HUB_LAUNCHES=launches)
+    done = subprocess.run([sys.executable, '-c', _SINGLE_SKETCH_HOPS % (REPO, os.path.dirname(os.path.abspath(__file__))), src, out], env=env,
+                          capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0, done.stderr[-2000:]
+    got = np.load(out)
+    assert got['rc'].tolist() == [0, 0] and int(got['hubs']) >= len(nb.targets) and int(got['mega']) >= 1
+    assert got['calls'].tolist() == [2, 1]
+    assert np.array_equal(got['mh2'], otab[2]['minhash']), 'MinHash alone'
+    assert np.array_equal(got['hll2'], otab[2]['hll']), 'HLL alone'
+    _check_counts(got['cards'], got['hll2'], t, prm, f'HLL alone, SS_HUB_LAUNCHES={launches}')
