@@ -9,6 +9,8 @@ edge_index that is the symmetrised graph).  Per link this file adds
   the BFS depths        from a root over those adjacency rows, optionally with one node removed (a plain queue)
   the labels            'de', 'de+', 'drnl' of the reference's labelling_tricks.py from those depths; 'hop' / 'zo' from the ball distances
 u == v (outside the reference's domain): one root, nothing removed, both depths equal.
+adjacency_of_rows() is the adjacency and the roots of node rows made by anyone (restate() calls it; tests/subgraph_planted.py hands it
+hand-made rows); link_labels() takes one link's raw arrays.
 """
 from collections import deque
 
@@ -43,6 +45,16 @@ def restate(num_nodes, edge_index, links, h, mask_target=True, max_nodes=None):
         rowptr = np.concatenate([[0], np.cumsum([len(r[0]) for r in rows])]).astype(np.int64)
         ids = np.concatenate([r[0] for r in rows] + [np.zeros((0,), dtype=np.int64)])
         dist = np.concatenate([r[1].reshape(-1, 2) for r in rows] + [np.zeros((0, 2), dtype=np.uint8)])
+    roots, adj_ptr, nbr, weight = adjacency_of_rows(n, ei, links, rowptr, ids, mask_target)
+    return Restated(rowptr=rowptr, ids=ids, dist=dist, roots=roots, adj_ptr=adj_ptr, nbr=nbr, weight=weight, links=links)
+
+
+def adjacency_of_rows(num_nodes, edge_index, links, rowptr, ids, mask_target):
+    """(roots int32 [L, 2], adj_ptr int64 [T + 1], nbr int32 [A], weight int32 [A]) of given node rows: row q = ids[rowptr[q] :
+    rowptr[q + 1]], ascending, distinct, with both ends of links[q] (ids in [0, num_nodes)) unless it is empty; whoever made the rows"""
+    n = int(num_nodes)
+    links = np.asarray(links, dtype=np.int64).reshape(-1, 2)
+    ei = np.asarray(edge_index, dtype=np.int64).reshape(2, -1)
     # in-arcs grouped by target: sources of the arcs j -> x at src[ptr[x] : ptr[x + 1]]
     order = np.argsort(ei[1], kind='stable')
     src = ei[0][order]
@@ -67,7 +79,7 @@ def restate(num_nodes, edge_index, links, h, mask_target=True, max_nodes=None):
             weight.append(w[ok])
     adj_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     cat = lambda parts: np.concatenate(parts + [np.zeros((0,), dtype=np.int64)]).astype(np.int32)
-    return Restated(rowptr=rowptr, ids=ids, dist=dist, roots=roots, adj_ptr=adj_ptr, nbr=cat(nbr), weight=cat(weight), links=links)
+    return roots, adj_ptr, cat(nbr), cat(weight)
 
 
 def bfs(ptr, nbr, root, removed=-1):

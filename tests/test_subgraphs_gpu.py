@@ -2,7 +2,8 @@
 (tests/subgraph_restatement.py), rowptr / ids / dist must equal exact_subgraph_nodes on the same arguments, and on BA-40 the labels must
 equal what the reference's own labelling functions gave (tests/golden/g17_seal_labels.npz) -- under batching and shuffling, through
 either tier of the node list and of the label kernel, through either direction of the adjacency intersection, on multigraphs, self
-loops, masked links, u == v, unreachable roots, max_nodes and the edge cases (no links, no edges, CPU inputs, a directed edge_index)."""
+loops, masked links, u == v, unreachable roots, max_nodes and the edge cases (no links, no edges, CPU inputs, a directed edge_index).
+The two kernels on hand-made rows, where their branches are planted: tests/subgraph_planted.py, tests/test_subgraph_planted_{host,gpu}.py."""
 from argparse import Namespace
 
 import numpy as np
