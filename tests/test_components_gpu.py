@@ -3,7 +3,13 @@ restatement (components_restatement.py) and, for the fixture graphs, against the
 (tests/golden/g19_lcc.npz).  "Equal" is exact integer equality of whole arrays: labels, roots, sizes, largest(), and the nodes, mapper,
 edge_index and edge_ids of largest_component_subgraph.  The shapes are the smallest at which the kernels can still go wrong: deep chains
 (a path of 4 096 nodes in four listings), one contended root (a star), all-distinct and all-equal labels inside a wavefront (matchings, a
-giant component), several workgroups of the count / fill passes (N = 50 000 against chunks of 2 048), ties for the largest size."""
+giant component), several workgroups of the count / fill passes (N = 50 000 against chunks of 2 048), ties for the largest size.
+Six graphs come from components_planted.py (tests/test_components_planted_host.py pins what they reach): `late giant`, whose largest
+root lies behind 3 chunks + 191 isolated nodes at lane 63; `tie across workgroups` and `tie in one wavefront`, two paths of 777 nodes
+whose roots sit in chunks 5 and 17, or at lanes 62 and 63 of one wavefront, the path with the larger ids listed first; `stride random`,
+`stride random shuffled` and `stride path`, 1 100 000 nodes with 1 400 000 and 1 099 999 arcs: more than the 4 096 x 256 items one trip
+of the grid-stride launches (init, hook, flatten) covers -- the shuffled arcs past the cap carry edges the first trip has not seen, the
+path is a deep chain that crosses every stride boundary."""
 import functools
 import importlib.util
 import os
@@ -14,6 +20,7 @@ import pytest
 import torch
 
 from conftest import REPO, load_golden
+import components_planted as planted
 import components_restatement as restated
 
 pytestmark = pytest.mark.gpu
@@ -73,6 +80,7 @@ GRAPHS = {
     'three cliques': lambda: _cliques(3),
 }
 GRAPHS.update({f'fixture {k}': (lambda k=k: FIXTURE[k][:2]) for k in range(len(FIXTURE))})
+GRAPHS.update(planted.API_GRAPHS)
 
 
 @functools.lru_cache(maxsize=None)
