@@ -12,7 +12,7 @@ mkdir -p build
 for f in $UNITS; do
   stale=0
   [ -f build/$f.o ] || stale=1
-  for dep in $f.hip ss_common.hpp ss_pair_math.hpp ss_topk_key.hpp ss_head.hpp ss_head_scan.hpp ss_feature_algebra.hpp ss_walks.hpp ss_feature_rows.hpp ss_hub.hpp ss_negatives.hpp ss_wedge.hpp ss_exact_bfs.hpp ss_sampled.hpp ../../include/subgraph_sketch.h ../../include/subgraph_sketch_debug.h build.sh; do
+  for dep in $f.hip ss_common.hpp ss_pair_math.hpp ss_pair_rows.hpp ss_topk_key.hpp ss_head.hpp ss_head_scan.hpp ss_feature_algebra.hpp ss_walks.hpp ss_feature_rows.hpp ss_hub.hpp ss_negatives.hpp ss_wedge.hpp ss_exact_bfs.hpp ss_sampled.hpp ../../include/subgraph_sketch.h ../../include/subgraph_sketch_debug.h build.sh; do
     [ -e $dep ] && [ $dep -nt build/$f.o ] && stale=1
   done
   if [ $stale = 1 ]; then

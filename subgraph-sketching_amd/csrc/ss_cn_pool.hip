@@ -1,13 +1,13 @@
 // ss_cn_pool.hip -- the common neighbours of node pairs as lists, and the node features of those neighbours pooled per pair:
 //     members(u, v) = the columns stored in both row u and row v of A (structural: a stored zero is a member)
-//     c(u, v, w)    = float32( A[u, w] * (A[v, w] * mult[w]) )      fp64 with this association, ONE rounding -- the term of
-//                     common_neighbour_kernel (csrc/ss_heuristics.hip), for every matrix dtype
+//     c(u, v, w)    = float32( A[u, w] * (A[v, w] * mult[w]) )      fp64 with this association, ONE rounding -- coefficient()
+//                     of csrc/ss_pair_rows.hpp, the term the fp64 scores add up, for every matrix dtype
 //     pool(u, v)    = sum over the members w, ASCENDING, of c(u, v, w) * x[w, :]      fp32, from +0.0, product and sum rounded
 //                     separately (-ffp-contract=off), every output element accumulated by ONE lane
 // A is a CSR with sorted, duplicate-free column ids.  One unit of lanes per pair: the lanes stride over the SHORTER row in chunks
 // of one entry per lane and binary-search the longer one; a ballot over the chunk puts the hits in ascending column order (the
 // shorter row is sorted), so neither the list nor the sum needs a sort, and a member's rank inside the pair is the running
-// popcount plus the prefix inside the ballot.  Three kernels on that step:
+// popcount plus the prefix inside the ballot.  Three kernels on that step (pair_rows, member, unit_ballot: csrc/ss_pair_rows.hpp):
 //   count  16 lanes per pair, the membership step alone
 //   fill   16 lanes per pair, ids[offsets[q] + rank] = w and, when asked for, coef[...] = c
 //   pool   U = 16 | 32 | 64 lanes per pair, chosen from F as ss_spmm chooses lanes_per_row (F = 128 -> 32 lanes, two pairs per
@@ -17,69 +17,12 @@
 //          4 F-byte rows, no MFMA, no LDS, no atomics.  A pair whose shorter row is long is walked chunk after chunk by its one
 //          unit: slow, never wrong.
 // A pair's row has ONE value: it does not depend on the grid, the unit size, the batch or which row was the shorter one.
-#include "ss_common.hpp"
+#include "ss_pair_rows.hpp"
 #include "ss_walks.hpp"
 
 namespace ss {
 
-constexpr int kListLanes = 16;  // lanes per pair of the count and fill kernels
-
 __host__ __device__ constexpr int pieces_of(int F) { return (F >> 2) + ((F & 3) ? 1 : 0); }  // four-column pieces of a feature row
-
-// the two rows of a pair, the shorter one first; `swapped`: the shorter row is v's
-struct PairRows {
-    int64_t sb, lb;
-    int ds, dl;
-    bool swapped;
-};
-
-__device__ __forceinline__ PairRows pair_rows(const int64_t *__restrict__ rowptr, int64_t u, int64_t v)
-{
-    const int64_t ub = rowptr[u], vb = rowptr[v];
-    const int du = (int)(rowptr[u + 1] - ub), dv = (int)(rowptr[v + 1] - vb);
-    PairRows r;
-    r.swapped = du > dv;
-    r.sb = r.swapped ? vb : ub;
-    r.lb = r.swapped ? ub : vb;
-    r.ds = r.swapped ? dv : du;
-    r.dl = r.swapped ? du : dv;
-    return r;
-}
-
-// entry i of the shorter row: is its column in the longer row?  w = the column, pos = where it sits in the longer row
-__device__ __forceinline__ bool member(const int32_t *__restrict__ col, const PairRows &r, int i, int32_t &w, int &pos)
-{
-    w = col[r.sb + i];
-    int lo = 0, hi = r.dl;  // first position in the long row with col >= w
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[r.lb + mid] < w) lo = mid + 1;
-        else hi = mid;
-    }
-    pos = lo;
-    return lo < r.dl && col[r.lb + lo] == w;
-}
-
-// c(u, v, w) of a member: the roles of src and dst stay the reference's whichever row was walked
-__device__ __forceinline__ float coefficient(const double *__restrict__ val, const double *__restrict__ mult, const PairRows &r, int i,
-                                             int pos, int32_t w)
-{
-    const double a_short = val ? val[r.sb + i] : 1.0, a_long = val ? val[r.lb + pos] : 1.0;
-    const double a_src = r.swapped ? a_long : a_short, a_dst = r.swapped ? a_short : a_long;
-    return (float)(a_src * (mult ? a_dst * mult[w] : a_dst));
-}
-
-// this unit's bits of the wavefront ballot (U lanes starting at lane `base`); control flow is uniform inside a unit
-__device__ __forceinline__ uint64_t unit_ballot(bool pred, int base, int U)
-{
-    const uint64_t all = __ballot(pred) >> base;
-    return U == kWave ? all : all & (((uint64_t)1 << U) - 1);
-}
-
-__device__ __forceinline__ bool ids_in_range(int64_t u, int64_t v, int64_t N)
-{
-    return (uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N;
-}
 
 // FILL: the fill pass (ids and, when coef is non-null, the coefficients); otherwise the count pass
 template <bool FILL>
@@ -89,10 +32,10 @@ __global__ __launch_bounds__(256) void cn_list_kernel(const int64_t *__restrict_
                                                       const int64_t *__restrict__ offsets, int64_t *__restrict__ ids,
                                                       float *__restrict__ coef, int32_t *__restrict__ err_flag)
 {
-    const int l = threadIdx.x & (kListLanes - 1);
+    int l;
+    int64_t q;
+    if (!group_pair(B, l, q)) return;
     const int base = (threadIdx.x & (kWave - 1)) - l;
-    const int64_t q = (int64_t)blockIdx.x * (blockDim.x / kListLanes) + threadIdx.x / kListLanes;
-    if (q >= B) return;
     const int64_t u = links[2 * q], v = links[2 * q + 1];
     if (!ids_in_range(u, v, N)) {
         if (l == 0) {
@@ -104,16 +47,15 @@ __global__ __launch_bounds__(256) void cn_list_kernel(const int64_t *__restrict_
     const PairRows r = pair_rows(rowptr, u, v);
     const int64_t first = FILL ? offsets[q] : 0;
     int rank = 0;
-    for (int i0 = 0; i0 < r.ds; i0 += kListLanes) {
+    for (int i0 = 0; i0 < r.ds; i0 += kPairLanes) {
         const int i = i0 + l;
-        int32_t w = 0;
-        int pos = 0;
-        const bool hit = i < r.ds && member(col, r, i, w, pos);
-        const uint32_t mask = (uint32_t)unit_ballot(hit, base, kListLanes);
+        Member m = {};
+        const bool hit = i < r.ds && member(col, r, i, m);
+        const uint32_t mask = (uint32_t)unit_ballot(hit, base, kPairLanes);
         if (FILL && hit) {
             const int64_t at = first + rank + __popc(mask & ((1u << l) - 1u));
-            ids[at] = w;
-            if (coef) coef[at] = coefficient(val, mult, r, i, pos, w);
+            ids[at] = m.w;
+            if (coef) coef[at] = coefficient(val, mult, r, m);
         }
         rank += __popc(mask);
     }
@@ -175,10 +117,9 @@ __global__ __launch_bounds__(256) void cn_pool_kernel(const int64_t *__restrict_
         float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         for (int i0 = 0; i0 < r.ds; i0 += U) {
             const int i = i0 + cl;
-            int32_t w = 0;
-            int pos = 0;
-            const bool hit = i < r.ds && member(col, r, i, w, pos);
-            const float cf = hit ? coefficient(val, mult, r, i, pos, w) : 0.0f;
+            Member m = {};
+            const bool hit = i < r.ds && member(col, r, i, m);
+            const float cf = hit ? coefficient(val, mult, r, m) : 0.0f;
             uint64_t mask = unit_ballot(hit, base, U);
             while (mask) {  // (uniform inside the unit) four hits at a time: their rows are requested before the first is used
                 float4 rw[4];
@@ -189,7 +130,7 @@ __global__ __launch_bounds__(256) void cn_pool_kernel(const int64_t *__restrict_
                     const bool take = mask != 0;
                     const int src = base + (take ? __ffsll((unsigned long long)mask) - 1 : 0);
                     mask &= mask - 1;  // (0 stays 0)
-                    const int32_t wk = __shfl(w, src);
+                    const int32_t wk = __shfl(m.w, src);
                     ck[k] = __shfl(cf, src);
                     n += take ? 1 : 0;
                     rw[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -209,42 +150,22 @@ __global__ __launch_bounds__(256) void cn_pool_kernel(const int64_t *__restrict_
     }
 }
 
-inline bool cn_sizes_ok(int64_t N, int64_t B) { return N >= 0 && B >= 0 && N < ((int64_t)1 << 31); }
-
 }  // namespace ss
 
 extern "C" int ss_common_neighbour_count(const int64_t *rowptr, const int32_t *col, int64_t N, const int64_t *links, int64_t B,
                                          int64_t *counts, int32_t *err_flag, void *stream)
 {
-    using namespace ss;
-    if (!cn_sizes_ok(N, B)) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    if (!rowptr || !col || !links || !counts) return SS_ERR_INVALID_ARG;
-    const int per_block = 256 / kListLanes;
-    const int64_t blocks = (B + per_block - 1) / per_block;
-    if (blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(cn_list_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col,
-                       (const double *)nullptr, (const double *)nullptr, N, links, B, counts, (const int64_t *)nullptr,
-                       (int64_t *)nullptr, (float *)nullptr, err_flag);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
+    return ss::launch_pairs(ss::cn_list_kernel<false>, ss::kPairLanes, N, B, rowptr && col && links && counts, stream, rowptr, col,
+                            (const double *)nullptr, (const double *)nullptr, N, links, B, counts, (const int64_t *)nullptr,
+                            (int64_t *)nullptr, (float *)nullptr, err_flag);
 }
 
 extern "C" int ss_common_neighbour_fill(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult, int64_t N,
                                         const int64_t *links, int64_t B, const int64_t *offsets, int64_t *ids, float *coef,
                                         int32_t *err_flag, void *stream)
 {
-    using namespace ss;
-    if (!cn_sizes_ok(N, B)) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    if (!rowptr || !col || !links || !offsets || !ids) return SS_ERR_INVALID_ARG;
-    const int per_block = 256 / kListLanes;
-    const int64_t blocks = (B + per_block - 1) / per_block;
-    if (blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(cn_list_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, mult, N, links,
-                       B, (int64_t *)nullptr, offsets, ids, coef, err_flag);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
+    return ss::launch_pairs(ss::cn_list_kernel<true>, ss::kPairLanes, N, B, rowptr && col && links && offsets && ids, stream, rowptr, col,
+                            val, mult, N, links, B, (int64_t *)nullptr, offsets, ids, coef, err_flag);
 }
 
 extern "C" int ss_common_neighbour_pool(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult, int64_t N,
@@ -252,21 +173,10 @@ extern "C" int ss_common_neighbour_pool(const int64_t *rowptr, const int32_t *co
                                         void *stream)
 {
     using namespace ss;
-    if (!cn_sizes_ok(N, B) || F < 0) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    if (!rowptr || !col || !links || (F > 0 && (!x || !out))) return SS_ERR_INVALID_ARG;
-    int U = pow2_ceil(pieces_of(F));
-    U = U < kListLanes ? kListLanes : (U > kWave ? kWave : U);
-    const int per_block = (256 / kWave) * (kWave / U);
-    const int64_t blocks = (B + per_block - 1) / per_block;
-    if (blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
+    if (F < 0) return SS_ERR_INVALID_ARG;
+    int U = pow2_ceil(pieces_of(F));  // the unit: lanes per pair, so 256 / U pairs per block
+    U = U < kPairLanes ? kPairLanes : (U > kWave ? kWave : U);
     const bool vec = (F & 3) == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(cn_pool_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, mult, N,
-                           links, B, x, (int)F, out, err_flag, U);
-    else
-        hipLaunchKernelGGL(cn_pool_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, mult, N,
-                           links, B, x, (int)F, out, err_flag, U);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
+    return launch_pairs(vec ? cn_pool_kernel<true> : cn_pool_kernel<false>, U, N, B, rowptr && col && links && (F == 0 || (x && out)),
+                        stream, rowptr, col, val, mult, N, links, B, x, (int)F, out, err_flag, U);
 }

@@ -61,6 +61,19 @@ __device__ __forceinline__ bool link_ids(const int64_t *links, int64_t q, int64_
     return (uint64_t)u < (uint64_t)N && (uint64_t)v < (uint64_t)N;
 }
 
+// the first index in [lo, hi) of the ascending a[] whose entry is not below `key` (UPPER: above it); hi if there is none.  I is the
+// index type: a site keeps its width (32-bit positions inside a row, 64-bit positions in a table)
+template <bool UPPER, typename I, typename T, typename K>
+__device__ __forceinline__ I bound(const T *__restrict__ a, I lo, I hi, K key)
+{
+    while (lo < hi) {
+        const I mid = (lo + hi) >> 1;
+        if (UPPER ? a[mid] <= key : a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // ---- byte-parallel helpers on HLL registers (4 registers per dword) --------------------------------
 // even/odd byte split: both halves are valid packed-u16 operands (odd bytes stay in the high byte of
 // each u16 lane, so unsigned 16-bit max orders them like the bytes).

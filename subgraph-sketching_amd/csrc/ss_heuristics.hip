@@ -16,11 +16,10 @@
 //     rounded down to a multiple of 8 and both halves summed so.  The kernel reproduces that order bit for bit: a ballot
 //     over the 16 lanes puts the matches of each 16-column chunk in rank order, and the group replays numpy's recursion as
 //     a stream (the leaves are contiguous runs of at most 128 terms, met left to right).
-#include "ss_common.hpp"
+// The row pair, the membership search and the term itself are csrc/ss_pair_rows.hpp's, shared with the lists of ss_cn_pool.hip.
+#include "ss_pair_rows.hpp"
 
 namespace ss {
-
-constexpr int kPairLanes = 16;
 
 __device__ inline double row16_sum_d(double x)
 {
@@ -28,43 +27,37 @@ __device__ inline double row16_sum_d(double x)
     return x;
 }
 
+// the pair of this 16-lane group (lane l of it) and its two rows; false: no pair is left, or one with an id outside [0, N), which
+// scores 0 and raises the error flag
+__device__ __forceinline__ bool scored_pair(const int64_t *__restrict__ rowptr, int64_t N, const int64_t *__restrict__ links, int64_t B,
+                                            float *__restrict__ out, int32_t *__restrict__ err_flag, int &l, int64_t &q, PairRows &r)
+{
+    if (!group_pair(B, l, q)) return false;
+    const int64_t u = links[2 * q], v = links[2 * q + 1];
+    if (!ids_in_range(u, v, N)) {
+        if (l == 0) {
+            out[q] = 0.0f;
+            if (err_flag) *err_flag = 1;
+        }
+        return false;
+    }
+    r = pair_rows(rowptr, u, v);
+    return true;
+}
+
 __global__ __launch_bounds__(256) void common_neighbour_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                                const double *__restrict__ val, const double *__restrict__ mult,
                                                                int64_t N, const int64_t *__restrict__ links, int64_t B,
                                                                float *__restrict__ out, int32_t *__restrict__ err_flag)
 {
-    const int l = threadIdx.x & (kPairLanes - 1);
-    const int64_t q = (int64_t)blockIdx.x * (blockDim.x / kPairLanes) + threadIdx.x / kPairLanes;
-    if (q >= B) return;
-    const int64_t u = links[2 * q], v = links[2 * q + 1];
-    if (u < 0 || u >= N || v < 0 || v >= N) {
-        if (l == 0) {
-            out[q] = 0.0f;
-            if (err_flag) *err_flag = 1;
-        }
-        return;
-    }
-    const int64_t ub = rowptr[u], vb = rowptr[v];
-    const int du = (int)(rowptr[u + 1] - ub), dv = (int)(rowptr[v + 1] - vb);
-    // walk the shorter row, search the longer one; `swapped` keeps the roles of the reference's product:
-    // term = A[src, w] * (A[dst, w] * mult[w])
-    const bool swapped = du > dv;
-    const int64_t sb = swapped ? vb : ub, lb = swapped ? ub : vb;
-    const int ds = swapped ? dv : du, dl = swapped ? du : dv;
+    int l;
+    int64_t q;
+    PairRows r;
+    if (!scored_pair(rowptr, N, links, B, out, err_flag, l, q, r)) return;
     double acc = 0.0;
-    for (int i = l; i < ds; i += kPairLanes) {
-        const int32_t w = col[sb + i];
-        int lo = 0, hi = dl;  // first position in the long row with col >= w
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (col[lb + mid] < w) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < dl && col[lb + lo] == w) {
-            const double a_short = val ? val[sb + i] : 1.0, a_long = val ? val[lb + lo] : 1.0;
-            const double a_src = swapped ? a_long : a_short, a_dst = swapped ? a_short : a_long;
-            acc += a_src * (mult ? a_dst * mult[w] : a_dst);
-        }
+    for (int i = l; i < r.ds; i += kPairLanes) {
+        Member m;
+        if (member(col, r, i, m)) acc += term_f64(val, mult, r, m);
     }
     acc = row16_sum_d(acc);
     if (l == 0) out[q] = (float)acc;
@@ -74,11 +67,6 @@ __global__ __launch_bounds__(256) void common_neighbour_kernel(const int64_t *__
 // ---- fp32 mode ---------------------------------------------------------------------------------------------------------------
 // Control flow is uniform inside a 16-lane group (every value below except `r` and the stack slots is the same in all 16
 // lanes), so ballots and width-16 shuffles see the whole group.
-
-__device__ inline uint32_t group_ballot(bool pred)  // this group's 16 bits of the wavefront ballot
-{
-    return (uint32_t)(__ballot(pred) >> (threadIdx.x & 48)) & 0xFFFFu;
-}
 
 // numpy's float32 pairwise sum of s[0..n) fed one term at a time, in order.  A node of more than 128 terms splits at
 // n2 = n/2 - (n/2) % 8; the leaves (<= 128 terms) are met left to right, so only the pending left halves need keeping: a
@@ -159,22 +147,13 @@ struct PairwiseF32 {
     }
 };
 
-// the term of short-row entry i, 0.0f when its column is not in the long row (or the product is 0: scipy drops it too)
+// the term of short-row entry i, 0.0f past the row's end and when its column is not in the long row (or the product is 0: scipy
+// drops it too)
 __device__ inline float f32_term(const int32_t *__restrict__ col, const double *__restrict__ val, const double *__restrict__ mult,
-                                 int64_t sb, int64_t lb, int i, int dl, bool swapped)
+                                 const PairRows &r, int i)
 {
-    const int32_t w = col[sb + i];
-    int lo = 0, hi = dl;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[lb + mid] < w) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= dl || col[lb + lo] != w) return 0.0f;
-    // the values are float32 numbers held in fp64: these casts are exact
-    const float a_short = val ? (float)val[sb + i] : 1.0f, a_long = val ? (float)val[lb + lo] : 1.0f;
-    const float a_src = swapped ? a_long : a_short, a_dst = swapped ? a_short : a_long;
-    return a_src * (mult ? a_dst * (float)mult[w] : a_dst);  // A_ = A.multiply(mult) is stored rounded, then the product
+    Member m;
+    return i < r.ds && member(col, r, i, m) ? term_f32(val, mult, r, m) : 0.0f;
 }
 
 __global__ __launch_bounds__(256) void common_neighbour_f32_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -182,37 +161,24 @@ __global__ __launch_bounds__(256) void common_neighbour_f32_kernel(const int64_t
                                                                    int64_t N, const int64_t *__restrict__ links, int64_t B,
                                                                    float *__restrict__ out, int32_t *__restrict__ err_flag)
 {
-    const int l = threadIdx.x & (kPairLanes - 1);
-    const int64_t q = (int64_t)blockIdx.x * (blockDim.x / kPairLanes) + threadIdx.x / kPairLanes;
-    if (q >= B) return;
-    const int64_t u = links[2 * q], v = links[2 * q + 1];
-    if (u < 0 || u >= N || v < 0 || v >= N) {
-        if (l == 0) {
-            out[q] = 0.0f;
-            if (err_flag) *err_flag = 1;
-        }
-        return;
-    }
-    const int64_t ub = rowptr[u], vb = rowptr[v];
-    const int du = (int)(rowptr[u + 1] - ub), dv = (int)(rowptr[v + 1] - vb);
-    const bool swapped = du > dv;
-    const int64_t sb = swapped ? vb : ub, lb = swapped ? ub : vb;
-    const int ds = swapped ? dv : du, dl = swapped ? du : dv;
+    int l;
+    int64_t q;
+    PairRows r;
+    if (!scored_pair(rowptr, N, links, B, out, err_flag, l, q, r)) return;
+    const int base = (threadIdx.x & (kWave - 1)) - l;
     // pass 1: m, the number of non-zero terms (numpy's split points depend on it); the first chunk's terms are kept
-    const float first = l < ds ? f32_term(col, val, mult, sb, lb, l, dl, swapped) : 0.0f;
-    int m = __popc(group_ballot(first != 0.0f));
-    for (int c = kPairLanes; c < ds; c += kPairLanes) {
-        const float t = c + l < ds ? f32_term(col, val, mult, sb, lb, c + l, dl, swapped) : 0.0f;
-        m += __popc(group_ballot(t != 0.0f));
-    }
+    const float first = f32_term(col, val, mult, r, l);
+    int m = __popc((uint32_t)unit_ballot(first != 0.0f, base, kPairLanes));
+    for (int c = kPairLanes; c < r.ds; c += kPairLanes)
+        m += __popc((uint32_t)unit_ballot(f32_term(col, val, mult, r, c + l) != 0.0f, base, kPairLanes));
     // pass 2: the terms in column order -> t[0] + pairwise(t[1:])
     PairwiseF32 pw;
     pw.init(m > 1 ? m - 1 : 0, l);
     float head = 0.0f;
     int rank = 0;
-    for (int c = 0; c < ds && rank < m; c += kPairLanes) {
-        const float t = c == 0 ? first : (c + l < ds ? f32_term(col, val, mult, sb, lb, c + l, dl, swapped) : 0.0f);
-        uint32_t mask = group_ballot(t != 0.0f);
+    for (int c = 0; c < r.ds && rank < m; c += kPairLanes) {
+        const float t = c == 0 ? first : f32_term(col, val, mult, r, c + l);
+        uint32_t mask = (uint32_t)unit_ballot(t != 0.0f, base, kPairLanes);
         while (mask) {
             const int src = __ffs(mask) - 1;
             mask &= mask - 1;
@@ -230,31 +196,13 @@ __global__ __launch_bounds__(256) void common_neighbour_f32_kernel(const int64_t
 extern "C" int ss_common_neighbour_scores(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
                                           int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream)
 {
-    using namespace ss;
-    if (N < 0 || B < 0 || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    if (!rowptr || !col || !links || !out) return SS_ERR_INVALID_ARG;
-    const int pairs_per_block = 256 / kPairLanes;
-    const int64_t blocks = (B + pairs_per_block - 1) / pairs_per_block;
-    if (blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(common_neighbour_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, mult, N,
-                       links, B, out, err_flag);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
+    return ss::launch_pairs(ss::common_neighbour_kernel, ss::kPairLanes, N, B, rowptr && col && links && out, stream, rowptr, col, val,
+                            mult, N, links, B, out, err_flag);
 }
 
 extern "C" int ss_common_neighbour_scores_f32(const int64_t *rowptr, const int32_t *col, const double *val, const double *mult,
                                               int64_t N, const int64_t *links, int64_t B, float *out, int32_t *err_flag, void *stream)
 {
-    using namespace ss;
-    if (N < 0 || B < 0 || N >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    if (B == 0) return SS_OK;
-    if (!rowptr || !col || !links || !out) return SS_ERR_INVALID_ARG;
-    const int pairs_per_block = 256 / kPairLanes;
-    const int64_t blocks = (B + pairs_per_block - 1) / pairs_per_block;
-    if (blocks >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(common_neighbour_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rowptr, col, val, mult,
-                       N, links, B, out, err_flag);
-    SS_LAUNCH_CHECK();
-    return SS_OK;
+    return ss::launch_pairs(ss::common_neighbour_f32_kernel, ss::kPairLanes, N, B, rowptr && col && links && out, stream, rowptr, col,
+                            val, mult, N, links, B, out, err_flag);
 }

@@ -24,11 +24,7 @@ typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
 // is x in the sorted col[b .. e) ?
 __device__ __forceinline__ bool row_has(const int32_t *__restrict__ col, int64_t b, int64_t e, int32_t x)
 {
-    int64_t lo = b, hi = e;  // first position whose entry is not below x
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (col[mid] < x) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = bound<false>(col, b, e, x);
     return lo < e && col[lo] == x;
 }
 

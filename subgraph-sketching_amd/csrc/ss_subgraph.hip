@@ -62,22 +62,6 @@ __device__ __forceinline__ int64_t owner_link(const int64_t *__restrict__ rowptr
     return lo;
 }
 
-// first index in [0, n) whose value is >= key (UPPER: > key); n if none
-template <bool UPPER, typename T>
-__device__ __forceinline__ int64_t bound(const T *__restrict__ a, int64_t n, int64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int64_t y = (int64_t)a[mid];
-        if (UPPER ? y <= key : y < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(kSubThreads) void subgraph_adj_kernel(AdjArgs a)
 {
@@ -110,14 +94,14 @@ __global__ __launch_bounds__(kSubThreads) void subgraph_adj_kernel(AdjArgs a)
                 if (by_ids) {
                     const int64_t j = idr[i];
                     if (j != x && j != skip) {
-                        const int64_t lb = bound<false>(col, deg, j);
-                        if (lb < deg && col[lb] == j) w = (int32_t)(bound<true>(col, deg, j) - lb);
+                        const int64_t lb = bound<false>(col, (int64_t)0, deg, j);
+                        if (lb < deg && col[lb] == j) w = (int32_t)(bound<true>(col, (int64_t)0, deg, j) - lb);
                     }
                     loc = i;
                 } else {
                     const int64_t j = col[i];
                     if ((i == 0 || col[i - 1] != j) && j != x && j != skip) {  // the first arc of a run of equal sources
-                        loc = bound<false>(idr, n, j);
+                        loc = bound<false>(idr, (int64_t)0, n, j);
                         if (loc < n && idr[loc] == j) {
                             int64_t e = i + 1;
                             while (e < deg && col[e] == j) ++e;
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(kSubThreads) void subgraph_adj_kernel(AdjArgs a)
         }
         if (!FILL && lane == 0) a.counts[t] = total;
         if (FILL && t == row && lane < 2) {  // once per link: where its roots are listed (they always are)
-            const int64_t r = bound<false>(idr, n, lane ? v : u);
+            const int64_t r = bound<false>(idr, (int64_t)0, n, lane ? v : u);
             a.roots[2 * q + lane] = r < n ? (int32_t)r : -1;
         }
     }

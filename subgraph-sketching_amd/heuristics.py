@@ -180,28 +180,46 @@ def _adjacency(A, device):
     return adj
 
 
+class _PairCall(object):
+    """The walk the three pair calls share after their own argument checks: the links' home and the compute device (`x` may name it,
+    `out` must be on it), the device adjacency, the links there as contiguous int64, the library, the error flag and the stream."""
+
+    def __init__(self, A, links, x=None, out=None):
+        self.home = links.device
+        self.device = _compute_device(links, x)
+        if out is not None and out.device != self.device:
+            raise ValueError(f'out must be on the compute device {self.device}, it is on {out.device}')
+        self.adj = _adjacency(A, self.device)
+        self.lk = links.to(device=self.device, dtype=torch.int64).contiguous()
+        self.lib, self.err, self.stream = _native.lib(), _ptr(_error_flag(self.device)), _stream(self.device)
+
+    def csr(self, mult):  # the head of every ss_common_neighbour_* call that takes values
+        return _ptr(self.adj.rowptr), _ptr(self.adj.col), _ptr(self.adj.val), _ptr(mult), self.adj.num_nodes
+
+    def launch(self, fn, *args, name=None):  # ... and its tail; `name`: what an error names
+        _native.check(getattr(self.lib, fn)(*args, self.err, self.stream), name or fn)
+
+    def batches(self, batch_size):  # the reference's DataLoader chunks (heuristics.py:18,41,62); results do not depend on them
+        L, step = self.lk.size(0), max(int(batch_size), 1)
+        return [(lo, min(lo + step, L)) for lo in range(0, L, step)]
+
+    def finish(self, *results, stay=False):  # one synchronising read after the launches, then the results on the links' device
+        if _take_error(self.device):
+            raise IndexError(f'edge_index refers to nodes outside [0, {self.adj.num_nodes})')
+        return [t if t is None or stay else t.to(self.home) for t in results]
+
+
 def _scores(kind, A, edge_index, batch_size):
     links = torch.as_tensor(edge_index)
     if links.dim() != 2 or links.size(1) != 2:
         raise ValueError('edge_index must be a tensor of links with shape [num_links, 2]')
-    home = links.device
-    device = _compute_device(links)
-    adj = _adjacency(A, device)
-    mult = adj.multiplier(kind)
-    lk = links.to(device=device, dtype=torch.int64).contiguous()
-    L = lk.size(0)
-    out = torch.empty(L, dtype=torch.float32, device=device)
-    err = _error_flag(device)
-    lib = _native.lib()
-    fn = lib.ss_common_neighbour_scores_f32 if adj.dtype == np.float32 else lib.ss_common_neighbour_scores
-    step = max(int(batch_size), 1)
-    for lo in range(0, L, step):  # the reference's DataLoader chunks (heuristics.py:18,41,62); results do not depend on it
-        hi = min(lo + step, L)
-        _native.check(fn(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes, _ptr(lk[lo:hi]), hi - lo,
-                         _ptr(out[lo:hi]), _ptr(err), _stream(device)), 'ss_common_neighbour_scores')
-    if _take_error(device):
-        raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
-    return out.to(home), edge_index
+    call = _PairCall(A, links)
+    mult = call.adj.multiplier(kind)
+    out = torch.empty(call.lk.size(0), dtype=torch.float32, device=call.device)
+    fn = 'ss_common_neighbour_scores_f32' if call.adj.dtype == np.float32 else 'ss_common_neighbour_scores'
+    for lo, hi in call.batches(batch_size):
+        call.launch(fn, *call.csr(mult), _ptr(call.lk[lo:hi]), hi - lo, _ptr(out[lo:hi]), name='ss_common_neighbour_scores')
+    return call.finish(out)[0], edge_index
 
 
 def CN(A, edge_index, batch_size=100000):
@@ -276,29 +294,22 @@ def common_neighbours(A, edge_index, weighting=None):
     (ss_common_neighbour_count / _fill: csrc/ss_cn_pool.hip).  A link id outside [0, N) raises IndexError after the launches."""
     links = _check_links(edge_index)
     weighting = _check_weighting(A, weighting, allow_none=True)
-    home = links.device
-    device = _compute_device(links)
-    adj = _adjacency(A, device)
+    call = _PairCall(A, links)
+    adj, lk, device = call.adj, call.lk, call.device
     mult, with_coef = _multiplier(adj, weighting)
-    lk = links.to(device=device, dtype=torch.int64).contiguous()
     L = lk.size(0)
     rowptr = torch.zeros(L + 1, dtype=torch.int64, device=device)
-    lib, err, stream = _native.lib(), _error_flag(device), _stream(device)
     T = 0
     if L:
         counts = torch.empty(L, dtype=torch.int64, device=device)
-        _native.check(lib.ss_common_neighbour_count(_ptr(adj.rowptr), _ptr(adj.col), adj.num_nodes, _ptr(lk), L, _ptr(counts), _ptr(err),
-                                                    stream), 'ss_common_neighbour_count')
+        call.launch('ss_common_neighbour_count', _ptr(adj.rowptr), _ptr(adj.col), adj.num_nodes, _ptr(lk), L, _ptr(counts))
         torch.cumsum(counts, 0, out=rowptr[1:])
         T = int(rowptr[-1].item())
     ids = torch.empty(max(T, 1), dtype=torch.int64, device=device)  # (never an empty device buffer behind the C ABI)
     coef = torch.empty(max(T, 1), dtype=torch.float32, device=device) if with_coef else None
     if T:
-        _native.check(lib.ss_common_neighbour_fill(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes, _ptr(lk), L,
-                                                   _ptr(rowptr), _ptr(ids), _ptr(coef), _ptr(err), stream), 'ss_common_neighbour_fill')
-    if _take_error(device):
-        raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
-    return CommonNeighbours(rowptr.to(home), ids[:T].to(home), coef[:T].to(home) if with_coef else None)
+        call.launch('ss_common_neighbour_fill', *call.csr(mult), _ptr(lk), L, _ptr(rowptr), _ptr(ids), _ptr(coef))
+    return CommonNeighbours(*call.finish(rowptr, ids[:T], coef[:T] if with_coef else None))
 
 
 def common_neighbour_features(A, edge_index, x, weighting='CN', batch_size=100000, out=None):
@@ -327,25 +338,13 @@ def common_neighbour_features(A, edge_index, x, weighting='CN', batch_size=10000
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (L, F)
                             or not out.is_contiguous()):
         raise ValueError(f'out must be a contiguous float32 tensor of shape [{L}, {F}]')
-    home = links.device
-    device = _compute_device(links, x)
-    if out is not None and out.device != device:
-        raise ValueError(f'out must be on the compute device {device}, it is on {out.device}')
-    adj = _adjacency(A, device)
-    mult, _ = _multiplier(adj, weighting)
-    lk = links.to(device=device, dtype=torch.int64).contiguous()
-    xd = x.detach().to(device).contiguous()
-    res = out if out is not None else torch.empty((L, F), dtype=torch.float32, device=device)
-    lib, err, stream = _native.lib(), _error_flag(device), _stream(device)
-    step = max(int(batch_size), 1)
-    for lo in range(0, L, step):
-        hi = min(lo + step, L)
-        _native.check(lib.ss_common_neighbour_pool(_ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(mult), adj.num_nodes,
-                                                   _ptr(lk[lo:hi]), hi - lo, _ptr(xd), F, _ptr(res[lo:hi]), _ptr(err), stream),
-                      'ss_common_neighbour_pool')
-    if _take_error(device):
-        raise IndexError(f'edge_index refers to nodes outside [0, {adj.num_nodes})')
-    return res if out is not None else res.to(home)
+    call = _PairCall(A, links, x, out)
+    mult, _ = _multiplier(call.adj, weighting)
+    xd = x.detach().to(call.device).contiguous()
+    res = out if out is not None else torch.empty((L, F), dtype=torch.float32, device=call.device)
+    for lo, hi in call.batches(batch_size):
+        call.launch('ss_common_neighbour_pool', *call.csr(mult), _ptr(call.lk[lo:hi]), hi - lo, _ptr(xd), F, _ptr(res[lo:hi]))
+    return call.finish(res, stay=out is not None)[0]  # (a caller's `out` stays on the compute device)
 
 
 PprPlan = collections.namedtuple('PprPlan', 'edge_reindex sources link_col batches')

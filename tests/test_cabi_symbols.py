@@ -216,10 +216,10 @@ def _return_code(lib, nat, entry, state, order, edits):
     return getattr(lib, entry)(*[arg(name) for name in order])
 
 
-def _return_code_rows(entry):
+def _return_code_rows(entry, entries=None):
     import subgraph_sketching_amd as ssa
     nat = ssa._native
-    state, order, edits = _table_hop_entries()[entry]
+    state, order, edits = (entries or _table_hop_entries())[entry]
     rows = []
     for name_i, edit_i in edits:
         codes = [_return_code(nat.lib(), nat, entry, state, order, [edit_i] if edit_i is edit_j else [edit_i, edit_j]) for _, edit_j in edits]
@@ -411,6 +411,134 @@ def test_table_hop_return_codes_are_pinned(entry):
     assert [name for name, _ in got] == [name for name in _PINNED[entry] if name != 'base call']
     for name, row in got:
         assert row == _PINNED[entry][name], (entry, name, row, _PINNED[entry][name])
+
+
+# ---- return codes of the common-neighbour entry points ---------------------------------------------------------------------------
+# The same scheme for ss_common_neighbour_scores, _scores_f32, _count, _fill and _pool.  The last check before their launch is the grid's
+# 2^31 cap, so the base call asks for 2^36 pairs (2^32 blocks at 16 pairs a block, 2^34 at 4) with every pointer given and comes back
+# SS_ERR_INVALID_ARG; the edits are the bad-argument classes in front of it and the early SS_OK exit of an empty batch.  The letters were
+# produced by the library as it stood before the five host preambles became one launcher (csrc/ss_pair_rows.hpp).
+def _pair_entries():
+    def sizes(*pointers):
+        return [('N < 0', _edit(N=-1)), ('B < 0', _edit(B=-1)), ('N = 2^31', _edit(N=1 << 31)),
+                ('B = 0, no pointers', _edit(B=0, **{name: None for name in pointers}))]
+
+    def missing(*names):
+        return [('no ' + name, _edit(**{name: None})) for name in names]
+
+    entries = {}
+    csr = dict(rowptr=_FAKE, col=_FAKE, val=_FAKE, mult=_FAKE, N=4, links=_FAKE, B=1 << 36, err_flag=_FAKE)
+    scores = (dict(csr, out=_FAKE), ('rowptr', 'col', 'val', 'mult', 'N', 'links', 'B', 'out', 'err_flag', None),
+              sizes('rowptr', 'col', 'val', 'mult', 'links', 'out', 'err_flag') + missing('rowptr', 'col', 'links', 'out')
+              + [('no val, mult, err_flag', _edit(val=None, mult=None, err_flag=None)), ('B = 2^35', _edit(B=1 << 35))])
+    entries['ss_common_neighbour_scores'] = entries['ss_common_neighbour_scores_f32'] = scores
+    entries['ss_common_neighbour_count'] = (
+        dict(csr, counts=_FAKE), ('rowptr', 'col', 'N', 'links', 'B', 'counts', 'err_flag', None),
+        sizes('rowptr', 'col', 'links', 'counts', 'err_flag') + missing('rowptr', 'col', 'links', 'counts', 'err_flag')
+        + [('B = 2^35', _edit(B=1 << 35))])
+    entries['ss_common_neighbour_fill'] = (
+        dict(csr, offsets=_FAKE, ids=_FAKE, coef=_FAKE),
+        ('rowptr', 'col', 'val', 'mult', 'N', 'links', 'B', 'offsets', 'ids', 'coef', 'err_flag', None),
+        sizes('rowptr', 'col', 'val', 'mult', 'links', 'offsets', 'ids', 'coef', 'err_flag')
+        + missing('rowptr', 'col', 'links', 'offsets', 'ids') + [('no val, mult, coef, err_flag', _edit(val=None, mult=None, coef=None, err_flag=None)),
+                                                                 ('B = 2^35', _edit(B=1 << 35))])
+    entries['ss_common_neighbour_pool'] = (
+        dict(csr, x=_FAKE, F=128, out=_FAKE), ('rowptr', 'col', 'val', 'mult', 'N', 'links', 'B', 'x', 'F', 'out', 'err_flag', None),
+        sizes('rowptr', 'col', 'val', 'mult', 'links', 'x', 'out', 'err_flag') + missing('rowptr', 'col', 'links')
+        + [('no val, mult, err_flag', _edit(val=None, mult=None, err_flag=None)), ('F < 0', _edit(F=-1)),
+           ('F = 0, no x, no out', _edit(F=0, x=None, out=None)), ('F = 0', _edit(F=0)), ('F > 0, no x', _edit(x=None)),
+           ('F > 0, no out', _edit(out=None)), ('F = 1024 (64 lanes)', _edit(F=1024)), ('B = 2^35', _edit(B=1 << 35))])
+    return entries
+
+
+_PAIR_PINNED = {
+    'ss_common_neighbour_scores': {
+        'base call': 'I',
+        'N < 0': 'IIIIIIIIII',
+        'B < 0': 'III0IIIIII',
+        'N = 2^31': 'IIIIIIIIII',
+        'B = 0, no pointers': 'III000000I',
+        'no rowptr': 'III0IIIIII',
+        'no col': 'III0IIIIII',
+        'no links': 'III0IIIIII',
+        'no out': 'III0IIIIII',
+        'no val, mult, err_flag': 'III0IIIIII',
+        'B = 2^35': 'III0IIIIII',
+    },
+    'ss_common_neighbour_scores_f32': {
+        'base call': 'I',
+        'N < 0': 'IIIIIIIIII',
+        'B < 0': 'III0IIIIII',
+        'N = 2^31': 'IIIIIIIIII',
+        'B = 0, no pointers': 'III000000I',
+        'no rowptr': 'III0IIIIII',
+        'no col': 'III0IIIIII',
+        'no links': 'III0IIIIII',
+        'no out': 'III0IIIIII',
+        'no val, mult, err_flag': 'III0IIIIII',
+        'B = 2^35': 'III0IIIIII',
+    },
+    'ss_common_neighbour_count': {
+        'base call': 'I',
+        'N < 0': 'IIIIIIIIII',
+        'B < 0': 'III0IIIIII',
+        'N = 2^31': 'IIIIIIIIII',
+        'B = 0, no pointers': 'III000000I',
+        'no rowptr': 'III0IIIIII',
+        'no col': 'III0IIIIII',
+        'no links': 'III0IIIIII',
+        'no counts': 'III0IIIIII',
+        'no err_flag': 'III0IIIIII',
+        'B = 2^35': 'III0IIIIII',
+    },
+    'ss_common_neighbour_fill': {
+        'base call': 'I',
+        'N < 0': 'IIIIIIIIIII',
+        'B < 0': 'III0IIIIIII',
+        'N = 2^31': 'IIIIIIIIIII',
+        'B = 0, no pointers': 'III0000000I',
+        'no rowptr': 'III0IIIIIII',
+        'no col': 'III0IIIIIII',
+        'no links': 'III0IIIIIII',
+        'no offsets': 'III0IIIIIII',
+        'no ids': 'III0IIIIIII',
+        'no val, mult, coef, err_flag': 'III0IIIIIII',
+        'B = 2^35': 'III0IIIIIII',
+    },
+    'ss_common_neighbour_pool': {
+        'base call': 'I',
+        'N < 0': 'IIIIIIIIIIIIIII',
+        'B < 0': 'III0IIIIIIIIIII',
+        'N = 2^31': 'IIIIIIIIIIIIIII',
+        'B = 0, no pointers': 'III00000I00000I',
+        'no rowptr': 'III0IIIIIIIIIII',
+        'no col': 'III0IIIIIIIIIII',
+        'no links': 'III0IIIIIIIIIII',
+        'no val, mult, err_flag': 'III0IIIIIIIIIII',
+        'F < 0': 'IIIIIIIIIIIIIII',
+        'F = 0, no x, no out': 'III0IIIIIIIIIII',
+        'F = 0': 'III0IIIIIIIIIII',
+        'F > 0, no x': 'III0IIIIIIIIIII',
+        'F > 0, no out': 'III0IIIIIIIIIII',
+        'F = 1024 (64 lanes)': 'III0IIIIIIIIIII',
+        'B = 2^35': 'III0IIIIIIIIIII',
+    },
+}
+
+
+@pytest.mark.parametrize('entry', sorted(_pair_entries()))
+def test_common_neighbour_return_codes_are_pinned(entry):
+    """every bad-argument class of the five common-neighbour entry points, alone and in pairs, and the empty batch's SS_OK: the codes
+    of the library before their preambles were merged (a '?' would be a code outside the four: a launch was reached)"""
+    import subgraph_sketching_amd as ssa
+    nat = ssa._native
+    state, order, _ = _pair_entries()[entry]
+    base = _return_code(nat.lib(), nat, entry, state, order, [])
+    assert _LETTER.get(base) == _PAIR_PINNED[entry]['base call'], base
+    got = _return_code_rows(entry, _pair_entries())
+    assert [name for name, _ in got] == [name for name in _PAIR_PINNED[entry] if name != 'base call']
+    for name, row in got:
+        assert row == _PAIR_PINNED[entry][name], (entry, name, row, _PAIR_PINNED[entry][name])
 
 
 def test_missing_library_fails_loudly(monkeypatch):
