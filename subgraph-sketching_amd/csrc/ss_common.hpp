@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "subgraph_sketch.h"
 #include "subgraph_sketch_debug.h"
 
@@ -535,6 +536,18 @@ inline int check_params(const ss_hll_params *prm)
     if (prm->n_tbl < 6 || prm->n_tbl > SS_MAX_TABLE) return SS_ERR_INVALID_ARG;
     if (!prm->raw_est || !prm->bias || !prm->lc_table) return SS_ERR_INVALID_ARG;
     return SS_OK;
+}
+
+// f(std::integral_constant<int, h>) for the kernels templated on the hop count alone (h checked: 1 .. 3): the exact-subgraph
+// kernels and masked_pairs_kernel
+template <class F>
+inline void dispatch_h(int32_t h, F f)
+{
+    switch (h) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
+    }
 }
 
 }  // namespace ss

@@ -6,11 +6,9 @@
 //   large tier    the slot of device memory with its leaf helpers (byte, clear, the union walk), the two-sided BFS into it, the
 //                 claim of the next overflow entry and the ordered scan of a slot's bytes
 //   both          a fill pass's row fetch
-//   host          the argument checks (tier_check), what an entry point hands its launch (Tier, tier_lds, tier_large), dispatch_h
+//   host          the argument checks (tier_check), what an entry point hands its launch (Tier, tier_lds, tier_large); dispatch_h: ss_common.hpp
 // The sampled walk is its own (one joint walk, its own level byte: ss_sampled_nodes.hip); it uses the tables, the slots and the leaves.
 #pragma once
-#include <type_traits>
-
 #include "ss_common.hpp"
 
 namespace ss {
@@ -424,17 +422,6 @@ inline int tier_large(int64_t N, int32_t slots, const void *arena, size_t arena_
     if (slots <= 0 || !arena) return SS_ERR_INVALID_ARG;
     if (arena_bytes / ss_exact_slot_bytes(N) < (size_t)slots) return SS_ERR_WORKSPACE;
     return tier_lds(0, workspace, stream, t);
-}
-
-// f(std::integral_constant<int, h>) for the kernels templated on the hop count (h checked: 1 .. 3)
-template <class F>
-inline void dispatch_h(int32_t h, F f)
-{
-    switch (h) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        default: f(std::integral_constant<int, 3>{}); break;
-    }
 }
 
 }  // namespace ss

@@ -1,10 +1,10 @@
 // ss_head_scan.hpp -- the host half of the two one-vs-all scans by the structure head, topk_score_scan_kernel (ss_topk_head.hip) and
-// rank_score_scan_kernel (ss_rank.hip): the LDS budget of a staged entry (a source / a link), the launch geometry, the (h, CMPL)
-// dispatch and the checks both entry points make.  The DEVICE body -- staging, candidate rows, the score of (u, v) -- stays written
+// rank_score_scan_kernel (ss_rank.hip): the LDS budget of a staged entry (a source / a link) and the checks both entry points make.
+// Their launch geometry (scan_grid, ss_topk_key.hpp) and their (h, CMPL) dispatch (dispatch_pair_shape, ss_pair_math.hpp) are the ones
+// topk_scan_kernel and the pair query use.  The DEVICE body -- staging, candidate rows, the score of (u, v) -- stays written
 // out in each kernel: as one source it kept scratch and LDS in all 30 instantiations and lowered the VGPRs of 29, but at <1, 0> that
 // moved both kernels from 7 to 8 waves per SIMD, and the rule was "equal" (DESIGN_EXPERIMENTS 3.13).
 #pragma once
-#include <utility>
 #include "ss_head.hpp"
 #include "ss_pair_math.hpp"
 #include "ss_topk_key.hpp"
@@ -29,32 +29,13 @@ constexpr int head_scan_entries(int H, int CMPL, int extra)
     return 8;  // (8 .. 32 either way: threads 0 .. 2 * entries - 1 of a workgroup stage the entries and hand their sums over)
 }
 
-// grid.y blocks of `per_block` entries, grid.x workgroups of candidates so that a launch aims at kTopkGrid workgroups
-inline dim3 head_scan_grid(int64_t n, int per_block, int64_t N)
-{
-    const int64_t blocks_y = (n + per_block - 1) / per_block;
-    int64_t blocks_x = (kTopkGrid + blocks_y - 1) / blocks_y;
-    const int64_t need_x = (N + kTopkRows - 1) / kTopkRows;
-    if (blocks_x > need_x) blocks_x = need_x;
-    return dim3((unsigned)blocks_x, (unsigned)blocks_y);
-}
-
-// launch(H, CMPL), both std::integral_constant<int, .>, for a checked hop count and sketch shape: instantiation I = 5 (H - 1) + CMPL
-// of std::make_integer_sequence<int, 5 * SS_MAX_HOPS>.  CMPL > 0: fast shape (p = 8, P = 64 * CMPL); 0: any other supported shape
-template <class Launch, int... I>
-void dispatch_head_scan(int h, int P, int M, Launch &&launch, std::integer_sequence<int, I...>)
-{
-    const int i = 5 * (h - 1) + (is_fast_pair_shape(P, M) ? P / 64 : 0);
-    ((i == I ? launch(std::integral_constant<int, I / 5 + 1>{}, std::integral_constant<int, I % 5>{}) : void()), ...);
-}
-
 // The checks both entry points make, in their order, up to the head.  n == 0 answers SS_OK before the pointers are looked at: the
 // caller returns when rc != SS_OK || n == 0.  N_end: the first N the kernel cannot take; own: the entry point's own pointers are there.
 inline int check_head_scan_args(int32_t n, int64_t N, int64_t N_end, bool own, int32_t h, const uint32_t *const *mh, const uint8_t *const *hll,
                                 int32_t P, const float *cards, int64_t cards_stride, const ss_hll_params *prm, const float *degrees,
                                 const ss_structure_head *head, HeadArgs &args)
 {
-    const int rc = check_pair_query_args(h, true, prm, P);
+    const int rc = check_pair_query_args(h, true, prm, P, false);
     if (rc != SS_OK) return rc;
     if (n < 0 || N <= 0 || N >= N_end) return SS_ERR_INVALID_ARG;
     if (n == 0) return SS_OK;

@@ -324,16 +324,6 @@ __global__ __launch_bounds__(kMaskedThreads) void masked_pairs_kernel(GraphArgs 
     }
 }
 
-template <int H>
-static void launch_masked(const GraphArgs &g, const int64_t *links, int64_t B, int64_t N, const int32_t *counter, const int32_t *list,
-                          const uint64_t *a, const uint64_t *b, const HopTables &tabs, int P, const ss_hll_params &prm, uint32_t flags,
-                          float *out, int32_t *dbg_match, int32_t *dbg_zero, int32_t *dbg_row_zeros, size_t dyn_bytes, hipStream_t s)
-{
-    const unsigned grid = (unsigned)(B < kMaskedGrid ? B : kMaskedGrid);
-    hipLaunchKernelGGL(masked_pairs_kernel<H>, dim3(grid), dim3(kMaskedThreads), dyn_bytes, s, g, links, N, counter, list, a, b, tabs, P, prm,
-                       flags, out, dbg_match, dbg_zero, dbg_row_zeros);
-}
-
 }  // namespace ss
 
 extern "C" size_t ss_masked_workspace_bytes(int64_t B)
@@ -378,11 +368,11 @@ extern "C" int ss_masked_pair_features(const ss_csr_graph *graph, const int64_t 
     }
     const GraphArgs g = to_args(*graph);
     const size_t dyn = ((size_t)2 * h * W4 + kMaskedThreads) * 16 + (size_t)M * 4;
-    switch (h) {
-        case 1: launch_masked<1>(g, links, B, N, counter, list, a, b, tabs, P, *prm, flags, out, dbg_match, dbg_zero, dbg_row_zeros, dyn, s); break;
-        case 2: launch_masked<2>(g, links, B, N, counter, list, a, b, tabs, P, *prm, flags, out, dbg_match, dbg_zero, dbg_row_zeros, dyn, s); break;
-        default: launch_masked<3>(g, links, B, N, counter, list, a, b, tabs, P, *prm, flags, out, dbg_match, dbg_zero, dbg_row_zeros, dyn, s); break;
-    }
+    const unsigned grid = (unsigned)(B < kMaskedGrid ? B : kMaskedGrid);
+    dispatch_h(h, [&](auto H) {
+        hipLaunchKernelGGL(masked_pairs_kernel<H()>, dim3(grid), dim3(kMaskedThreads), dyn, s, g, links, N, counter, list, a, b, tabs, (int)P, *prm,
+                           flags, out, dbg_match, dbg_zero, dbg_row_zeros);
+    });
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

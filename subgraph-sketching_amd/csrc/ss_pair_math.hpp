@@ -6,13 +6,18 @@
 // have ONE source here for pair_features_kernel, pair_features_runs_kernel, topk_score_scan_kernel and masked_pairs_kernel.  The finish
 // of a pair between them -- lane c < h^2: intersection_estimate, __shfl of I to the row, assemble_features -- stays written out in each
 // of the four: as one function it changed their registers (DESIGN_EXPERIMENTS "One source for the pair finish").  The host half at the
-// end is what their entry points share: the table pointers and the argument checks.  rank_score_scan_kernel (ss_rank.hip) repeats the
+// end is what their entry points share: the table pointers, the pair query's request record, the (h, P, M) -> template arguments
+// dispatch of the five scan / query kernels and the argument checks.  rank_score_scan_kernel (ss_rank.hip) repeats the
 // body of topk_score_scan_kernel: one source for the two was built and measured -- two instantiations changed occupancy and the scan
 // was 1 - 2 % slower -- so both stay written out and share their host half only (ss_head_scan.hpp, DESIGN_EXPERIMENTS 3.13).
 #pragma once
+#include <type_traits>
+#include <utility>
 #include "ss_feature_algebra.hpp"
 
 namespace ss {
+
+struct HeadArgs;  // (ss_head.hpp: PairQuery below names it by pointer only)
 
 // (measured and rejected in round 3: counting equal dwords as 4 - sum(min(a ^ b, 1)) instead of v_cmp_eq_u32 + v_addc_co_u32 -- hipcc
 // puts an `s_nop 1` behind each of the 72 compares of a pair at h = 3, gfx950 wanting two wait states between a VALU write of VCC
@@ -130,12 +135,46 @@ inline bool fill_hop_tables(const uint32_t *const *mh, const uint8_t *const *hll
     return true;
 }
 
+// What one launch of the pair kernels takes (ss_pairs.hip): every entry point there fills it by name, the launchers read it.
+struct PairQuery {
+    const int64_t *links;
+    const int32_t *order;  // nullable: position t of the walk is pair order[t]
+    int64_t B, N;
+    int h;
+    HopTables tabs;
+    int P, M;
+    const float *cards;
+    int64_t cards_stride;
+    ss_hll_params prm;
+    uint32_t flags;
+    const float *degrees;  // nullable: the degree-normalised copy is appended / fed to the head
+    float *out;
+    int32_t *dbg_match, *dbg_zero;  // the three dbg_*: ss_pair_features alone
+    float *dbg_inter;
+    int32_t *err;
+    hipStream_t stream;
+    bool grouped;            // the walk has locality: the capped register budget whatever the batch size
+    const HeadArgs *head;    // nullable: ss_pair_scores (ss_head.hpp)
+};
+
 // the shapes with compile-time kernels: p = 8 and the permutation counts the first hop is specialised for (ss_first_hop: P / 64 = 1 .. 4)
 inline bool is_fast_pair_shape(int P, int M) { return M == 256 && (P == 64 || P == 128 || P == 192 || P == 256); }
 
+// launch(H, CMPL), both std::integral_constant<int, .>, for a checked hop count and sketch shape: instantiation I = 5 (H - 1) + CMPL
+// of PairShapes.  CMPL > 0: fast shape (p = 8, P = 64 * CMPL: TP = 64 * CMPL, TM = 256 in the pair kernels); 0: any other supported
+// shape (TP = TM = 0).  The one place where h, P and M become template arguments for the pair query, the run-aware query and the three
+// one-vs-all scans; a kernel without a hop count (topk_scan_kernel) passes h = 1 and ignores H.
+using PairShapes = std::make_integer_sequence<int, 5 * SS_MAX_HOPS>;
+template <class Launch, int... I>
+void dispatch_pair_shape(int h, int P, int M, Launch &&launch, std::integer_sequence<int, I...>)
+{
+    const int i = 5 * (h - 1) + (is_fast_pair_shape(P, M) ? P / 64 : 0);
+    ((i == I ? launch(std::integral_constant<int, I / 5 + 1>{}, std::integral_constant<int, I % 5>{}) : void()), ...);
+}
+
 // Hop count, the caller's own size checks, HLL parameters, sketch width -- in the one order that decides which code comes back.
 // `empty`: the entry points that answer an empty query with SS_OK before they look at P pass B == 0 (and return right after).
-inline int check_pair_query_args(int h, bool sizes_ok, const ss_hll_params *prm, int P, bool empty = false)
+inline int check_pair_query_args(int h, bool sizes_ok, const ss_hll_params *prm, int P, bool empty)
 {
     if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;  // hashing.py:54, 308-309
     if (!sizes_ok) return SS_ERR_INVALID_ARG;

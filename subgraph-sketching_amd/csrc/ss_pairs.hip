@@ -13,9 +13,6 @@
 // inside the row with DPP (quad_perm / row_half_mirror / row_mirror -- no LDS traffic), then lane c < h^2
 // runs the HLL++ estimator for combination c and the h(h+2) features are assembled in fp32 in the
 // reference's own operation order.
-#include <cstdlib>
-#include <cstring>
-
 #include <type_traits>
 
 #include "ss_feature_algebra.hpp"
@@ -387,12 +384,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(H == 3 ? 3 
     }
 }
 
-// HEAD: the kernel with *head behind its arguments (ss_pair_scores) -- the same grid and the same choice of register budget
-template <int H, int TP, int TM, bool HEAD = false>
-int launch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                 int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
-                 int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
-                 bool grouped = false, const HeadArgs *head = nullptr)
+// ---- host side: a PairQuery (ss_pair_math.hpp) is checked once, then planned and launched by one of two functions ---------------
+// The checks the five entry points share, in the one order that decides which code comes back; they complete the record (tables,
+// HLL parameters, M).  N_end: the first N the entry point cannot take, 0 for none (the grouped entry points: 2^31).  The caller returns
+// when rc != SS_OK || q.B == 0.
+static int finish_pair_query(PairQuery &q, const uint32_t *const *mh, const uint8_t *const *hll, const ss_hll_params *prm, int64_t N_end)
+{
+    const int rc = check_pair_query_args(q.h, q.B >= 0 && q.N >= 0, prm, q.P, /*empty=*/q.B == 0);
+    if (rc != SS_OK || q.B == 0) return rc;
+    if (q.N == 0 || (N_end && q.N >= N_end) || !q.links || !mh || !hll || !q.cards || !q.out || q.cards_stride < q.h) return SS_ERR_INVALID_ARG;
+    if (q.order && q.B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices)
+    if (!fill_hop_tables(mh, hll, q.h, q.tabs)) return SS_ERR_INVALID_ARG;
+    q.prm = *prm;
+    q.M = 1 << prm->p;
+    return SS_OK;
+}
+
+// pair_features_kernel for a finished record; with q.head the kernel with *head behind its arguments (ss_pair_scores) -- the same
+// grid and the same choice of register budget
+static int launch_pair_query(const PairQuery &q)
 {
     const int pairs_per_block = 256 / kRow;
     // pairs per 16-lane group the grid is sized for: ONE while that still fits the chip in a single round of workgroups (ELPH
@@ -401,8 +411,8 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &ta
     // 8 192, 2.18 with 2 048, 2.06 with 1 280).  Measured and rejected: 64- / 128-thread workgroups, persistent
     // grids of 512 - 1 024 workgroups, and a software-pipelined variant that requests the next pair's rows in the middle of the
     // current pair's arithmetic (165 VGPRs: +1.5 % on batches of millions, -7 % at B = 65 536).
-    const int per_group = B <= 1024 * pairs_per_block ? 1 : 2;
-    int64_t blocks = (B + per_group * pairs_per_block - 1) / (per_group * pairs_per_block);
+    const int per_group = q.B <= 1024 * pairs_per_block ? 1 : 2;
+    int64_t blocks = (q.B + per_group * pairs_per_block - 1) / (per_group * pairs_per_block);
     if (blocks > kPairGrid) blocks = kPairGrid;
     if (blocks < 1) blocks = 1;
     // Which register budget (TP = 128 only: one more instantiation per hop count).  Walks with locality: the capped build (OCC, see the
@@ -410,97 +420,52 @@ int launch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &ta
     // GB, cold and after 2 000 launches): at H = 3 the fourth wavefront per SIMD wins at every table size while the launch is small --
     // B = 65 536: -4 .. -9 %, B = 261 424 (ogbl-citation2's batch): -1 .. -5 % -- and is level (+-0.6 %) at 4 M pairs; at H = 2 the fifth
     // wins 1 - 4 % at B = 65 536 (the bench step's query, ELPH batches) and LOSES 2 - 9 % at 261 424 on tables above ~1.5 GB.
-    const bool small_launch = H == 3 ? B <= ((int64_t)1 << 21) : B <= 65536;
-    const bool occ = grouped || small_launch;
+    const bool small_launch = q.h == 3 ? q.B <= ((int64_t)1 << 21) : q.B <= 65536;
+    const bool occ = q.grouped || small_launch;
     {
-        ProfileSpan span(stream, SS_PROF_PAIRS, true);
-        constexpr bool HAS_OCC = TP == 128 && H >= 2;  // (elsewhere both names below are the one default-budget kernel)
-        const auto launch = [&](auto kernel, auto... head_args) {
-            span.launch(kernel, dim3((unsigned)blocks), dim3(256), links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match,
-                        dbg_zero, dbg_inter, err, degrees, order, head_args...);
-        };
-        if constexpr (HEAD) launch(occ ? pair_features_kernel<H, TP, TM, HAS_OCC, HeadArgs> : pair_features_kernel<H, TP, TM, false, HeadArgs>, *head);
-        else launch(occ ? pair_features_kernel<H, TP, TM, HAS_OCC> : pair_features_kernel<H, TP, TM>);
+        ProfileSpan span(q.stream, SS_PROF_PAIRS, true);
+        dispatch_pair_shape(q.h, q.P, q.M, [&](auto H, auto CMPL) {
+            constexpr int TP = 64 * CMPL(), TM = CMPL() ? 256 : 0;
+            constexpr bool HAS_OCC = TP == 128 && H() >= 2;  // (elsewhere both names below are the one default-budget kernel)
+            const auto launch = [&](auto kernel, auto... head_args) {
+                span.launch(kernel, dim3((unsigned)blocks), dim3(256), q.links, q.B, q.N, q.tabs, q.P, q.M, q.cards, q.cards_stride, q.prm, q.flags,
+                            q.out, q.dbg_match, q.dbg_zero, q.dbg_inter, q.err, q.degrees, q.order, head_args...);
+            };
+            if (q.head) launch(occ ? pair_features_kernel<H(), TP, TM, HAS_OCC, HeadArgs> : pair_features_kernel<H(), TP, TM, false, HeadArgs>, *q.head);
+            else launch(occ ? pair_features_kernel<H(), TP, TM, HAS_OCC> : pair_features_kernel<H(), TP, TM>);
+        }, PairShapes{});
     }
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
-template <int H, bool HEAD = false>
-int dispatch_pairs(const int64_t *links, int64_t B, int64_t N, const HopTables &tabs, int P, int M, const float *cards,
-                   int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *dbg_match,
-                   int32_t *dbg_zero, float *dbg_inter, int32_t *err, const float *degrees, hipStream_t stream, const int32_t *order = nullptr,
-                   bool grouped = false, const HeadArgs *head = nullptr)
-{
-    const bool fast = is_fast_pair_shape(P, M);
-#define SS_PAIRS_FAST(TP)                                                                                                      \
-    if (P == TP && fast)                                                                                                        \
-        return launch_pairs<H, TP, 256, HEAD>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, \
-                                              dbg_inter, err, degrees, stream, order, grouped, head);
-    SS_PAIRS_FAST(128)  // the reference's default shape
-    SS_PAIRS_FAST(64)
-    SS_PAIRS_FAST(192)
-    SS_PAIRS_FAST(256)
-#undef SS_PAIRS_FAST
-    return launch_pairs<H, 0, 0, HEAD>(links, B, N, tabs, P, M, cards, cards_stride, prm, flags, out, dbg_match, dbg_zero, dbg_inter,
-                                       err, degrees, stream, order, grouped, head);
-}
-
-template <int H, int TP>
-int launch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const HopTables &tabs, const float *cards,
-                     int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *err, const float *degrees,
-                     hipStream_t stream)
+// pair_features_runs_kernel for a finished record of a fast shape (the kernel has no run-time-shape form)
+static int launch_pair_runs(const PairQuery &q)
 {
     // pairs per chunk: 16 once that still leaves >= 32 768 chunks (eight rounds of 16-group workgroups over 256 CUs); fewer for
     // smaller batches so that the chip stays full
-    int64_t K = B / 32768;
+    int64_t K = q.B / 32768;
     K = K < 1 ? 1 : (K > kRow ? kRow : K);
-    const int64_t chunks = (B + K - 1) / K;
+    const int64_t chunks = (q.B + K - 1) / K;
     int64_t blocks = (chunks + 256 / kRow - 1) / (256 / kRow);
     if (blocks > kPairGrid) blocks = kPairGrid;
+    bool launched = false;
     {
-        ProfileSpan span(stream, SS_PROF_PAIRS);
-        hipLaunchKernelGGL((pair_features_runs_kernel<H, TP, 256>), dim3((unsigned)blocks), dim3(256), 0, stream, links, order, B, N, (int)K,
-                           tabs, cards, cards_stride, prm, flags, out, err, degrees);
+        ProfileSpan span(q.stream, SS_PROF_PAIRS);
+        dispatch_pair_shape(q.h, q.P, q.M, [&](auto H, auto CMPL) {
+            if constexpr (CMPL() > 0) {
+                hipLaunchKernelGGL((pair_features_runs_kernel<H(), 64 * CMPL(), 256>), dim3((unsigned)blocks), dim3(256), 0, q.stream, q.links, q.order,
+                                   q.B, q.N, (int)K, q.tabs, q.cards, q.cards_stride, q.prm, q.flags, q.out, q.err, q.degrees);
+                launched = true;
+            }
+        }, PairShapes{});
     }
+    if (!launched) return SS_ERR_UNSUPPORTED;  // (a run-time shape: grouped_pair_query sends those to the ordinary kernel)
     SS_LAUNCH_CHECK();
     return SS_OK;
 }
 
-template <int H>
-int dispatch_pair_runs(const int64_t *links, const int32_t *order, int64_t B, int64_t N, const HopTables &tabs, int P, const float *cards,
-                       int64_t cards_stride, const ss_hll_params &prm, uint32_t flags, float *out, int32_t *err, const float *degrees,
-                       hipStream_t stream)
-{
-    switch (P) {
-        case 64: return launch_pair_runs<H, 64>(links, order, B, N, tabs, cards, cards_stride, prm, flags, out, err, degrees, stream);
-        case 128: return launch_pair_runs<H, 128>(links, order, B, N, tabs, cards, cards_stride, prm, flags, out, err, degrees, stream);
-        case 192: return launch_pair_runs<H, 192>(links, order, B, N, tabs, cards, cards_stride, prm, flags, out, err, degrees, stream);
-        default: return launch_pair_runs<H, 256>(links, order, B, N, tabs, cards, cards_stride, prm, flags, out, err, degrees, stream);
-    }
-}
-
 }  // namespace ss
-
-static int pair_features_impl(const int64_t *links, int64_t B, int64_t N, int32_t h, const uint32_t *const *mh, int32_t P,
-                              const uint8_t *const *hll, const float *cards, int64_t cards_stride, const ss_hll_params *prm,
-                              uint32_t flags, const float *degrees, float *out, int32_t *dbg_match, int32_t *dbg_zero,
-                              float *dbg_inter, int32_t *err_flag, void *stream, const int32_t *order = nullptr, bool grouped = false)
-{
-    using namespace ss;
-    const int rc = check_pair_query_args(h, B >= 0 && N >= 0, prm, P, B == 0);
-    if (rc != SS_OK || B == 0) return rc;
-    if (N == 0 || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    HopTables tabs;
-    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
-    const int M = 1 << prm->p;
-    hipStream_t s = (hipStream_t)stream;
-    switch (h) {
-        case 1: return dispatch_pairs<1>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
-        case 2: return dispatch_pairs<2>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
-        default: return dispatch_pairs<3>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, dbg_match, dbg_zero, dbg_inter, err_flag, degrees, s, order, grouped);
-    }
-}
 
 // One score per pair: the structure-feature head of both reference models (models/elph.py:73-86 LinkPredictor.forward, :324-352
 // BUDDY.forward -- label_lin_layer, bn_labels in eval mode, ReLU, the label branch's columns of lin) behind the ordinary walk, so
@@ -514,21 +479,27 @@ extern "C" int ss_pair_scores(const int64_t *links, const int32_t *order, int64_
     if (h < 1 || h > SS_MAX_HOPS) return SS_ERR_UNSUPPORTED;
     if (B < 0 || N < 0) return SS_ERR_INVALID_ARG;
     if (B == 0) return SS_OK;  // (before prm is looked at, unlike the feature queries: so the two checks above are written out here)
-    const int rc = check_pair_query_args(h, true, prm, P);
+    PairQuery q = {};
+    q.links = links;
+    q.order = order;
+    q.B = B;
+    q.N = N;
+    q.h = h;
+    q.P = P;
+    q.cards = cards;
+    q.cards_stride = cards_stride;
+    q.flags = flags;
+    q.degrees = degrees;
+    q.out = out;
+    q.err = err_flag;
+    q.stream = (hipStream_t)stream;
+    q.grouped = order != nullptr;  // a walk with locality: the capped register budget, as ss_pair_features_grouped
+    const int rc = finish_pair_query(q, mh, hll, prm, /*N_end=*/0);
     if (rc != SS_OK) return rc;
-    if (N == 0 || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices)
     HeadArgs args;
-    HopTables tabs;
-    if (!make_head_args(head, h, degrees, args) || !fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
-    const int M = 1 << prm->p;
-    hipStream_t s = (hipStream_t)stream;
-    const bool grouped = order != nullptr;  // a walk with locality: the capped register budget, as ss_pair_features_grouped
-    switch (h) {
-        case 1: return dispatch_pairs<1, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
-        case 2: return dispatch_pairs<2, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
-        default: return dispatch_pairs<3, true>(links, B, N, tabs, P, M, cards, cards_stride, *prm, flags, out, nullptr, nullptr, nullptr, err_flag, degrees, s, order, grouped, &args);
-    }
+    if (!make_head_args(head, h, degrees, args)) return SS_ERR_INVALID_ARG;
+    q.head = &args;
+    return launch_pair_query(q);
 }
 
 extern "C" int ss_pair_features(const int64_t *links, int64_t B, int64_t N, int32_t h,
@@ -537,8 +508,25 @@ extern "C" int ss_pair_features(const int64_t *links, int64_t B, int64_t N, int3
                                 float *out, int32_t *dbg_match, int32_t *dbg_zero, float *dbg_inter, int32_t *err_flag,
                                 void *stream)
 {
-    return pair_features_impl(links, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, nullptr, out, dbg_match, dbg_zero,
-                              dbg_inter, err_flag, stream);
+    using namespace ss;
+    PairQuery q = {};
+    q.links = links;
+    q.B = B;
+    q.N = N;
+    q.h = h;
+    q.P = P;
+    q.cards = cards;
+    q.cards_stride = cards_stride;
+    q.flags = flags;
+    q.out = out;
+    q.dbg_match = dbg_match;
+    q.dbg_zero = dbg_zero;
+    q.dbg_inter = dbg_inter;
+    q.err = err_flag;
+    q.stream = (hipStream_t)stream;
+    const int rc = finish_pair_query(q, mh, hll, prm, /*N_end=*/0);
+    if (rc != SS_OK || B == 0) return rc;
+    return launch_pair_query(q);
 }
 
 extern "C" int ss_pair_features_normalised(const int64_t *links, int64_t B, int64_t N, int32_t h,
@@ -546,17 +534,26 @@ extern "C" int ss_pair_features_normalised(const int64_t *links, int64_t B, int6
                                            const float *cards, int64_t cards_stride, const ss_hll_params *prm, uint32_t flags,
                                            const float *degrees, float *out, int32_t *err_flag, void *stream)
 {
+    using namespace ss;
     if (!degrees) return SS_ERR_INVALID_ARG;
-    return pair_features_impl(links, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, nullptr, nullptr, nullptr,
-                              err_flag, stream);
+    PairQuery q = {};
+    q.links = links;
+    q.B = B;
+    q.N = N;
+    q.h = h;
+    q.P = P;
+    q.cards = cards;
+    q.cards_stride = cards_stride;
+    q.flags = flags;
+    q.degrees = degrees;
+    q.out = out;
+    q.err = err_flag;
+    q.stream = (hipStream_t)stream;
+    const int rc = finish_pair_query(q, mh, hll, prm, /*N_end=*/0);
+    if (rc != SS_OK || B == 0) return rc;
+    return launch_pair_query(q);
 }
 
-// The query over a link list whose pairs are walked in runs of equal first nodes (see pair_features_runs_kernel): `order`
-// (nullable) = a permutation of the pair indices, e.g. from ss_group_links_by_source; without it the pairs are walked as they
-// are listed (a coalesced edge list, or an evaluation set that lists all negatives of a source together, already has the
-// runs).  Row q of `out` is pair q whatever the order; rows are bit-identical to ss_pair_features[_normalised]'s.  degrees
-// nullable (non-null: the degree-normalised copy is appended, as ss_pair_features_normalised does).  Shapes without a
-// specialised kernel (P not in {64, 128, 192, 256} or p != 8) take the ordinary path -- same rows, no reuse.
 // ---- the two permutations around a grouped query over a link set too large for its caches -------------------------------------
 // Walking `order` directly makes every position read links[order[t]] (16 B) and write out[order[t]] (<= 120 B) at random places
 // of arrays of gigabytes (ogbl-citation2: 5.7 GB of links, 21 GB of features): gfx9 counts loads and stores in ONE in-order
@@ -611,16 +608,32 @@ extern "C" int ss_scatter_feature_rows(const float *rows, const int32_t *order, 
     return SS_OK;
 }
 
-static int pair_features_grouped_impl(int which /* -1: chosen per hop count, 0: ordinary kernel, 1: run-aware kernel */, const int64_t *links,
-                                      const int32_t *order, int64_t B, int64_t N, int32_t h, const uint32_t *const *mh, int32_t P,
-                                      const uint8_t *const *hll, const float *cards, int64_t cards_stride, const ss_hll_params *prm,
-                                      uint32_t flags, const float *degrees, float *out, int32_t *err_flag, void *stream)
+namespace ss {
+
+// The two grouped entry points differ in `which` alone (-1 chosen per hop count, 0 ordinary kernel, 1 run-aware kernel): the record
+// they fill, its checks (N < 2^31: the run-aware kernel keeps node ids in 32-bit lanes, and the entry point promises one limit for both)
+// and the kernel.
+static int grouped_pair_query(int which, const int64_t *links, const int32_t *order, int64_t B, int64_t N, int32_t h, const uint32_t *const *mh,
+                              int32_t P, const uint8_t *const *hll, const float *cards, int64_t cards_stride, const ss_hll_params *prm,
+                              uint32_t flags, const float *degrees, float *out, int32_t *err_flag, void *stream)
 {
-    using namespace ss;
-    const int rc = check_pair_query_args(h, B >= 0 && N >= 0, prm, P, B == 0);
+    PairQuery q = {};
+    q.links = links;
+    q.order = order;
+    q.B = B;
+    q.N = N;
+    q.h = h;
+    q.P = P;
+    q.cards = cards;
+    q.cards_stride = cards_stride;
+    q.flags = flags;
+    q.degrees = degrees;
+    q.out = out;
+    q.err = err_flag;
+    q.stream = (hipStream_t)stream;
+    q.grouped = true;
+    const int rc = finish_pair_query(q, mh, hll, prm, /*N_end=*/(int64_t)1 << 31);
     if (rc != SS_OK || B == 0) return rc;
-    if (N == 0 || N >= ((int64_t)1 << 31) || !links || !mh || !hll || !cards || !out || cards_stride < h) return SS_ERR_INVALID_ARG;
-    const bool fast = is_fast_pair_shape(P, 1 << prm->p);
     // Which kernel (measured, tools/probe_pair_runs.py -> profiles/round3_pair_runs_*.json, 4 M links): WITH an order the ordinary
     // kernel -- neighbouring lane groups take neighbouring positions, so the rows of a shared first node meet in the CU's L1 / the
     // L2 -- is ahead or level at every hop count (ppa-size tables, h = 2, random links grouped: 2.69 against 2.63 G pairs/s;
@@ -633,31 +646,25 @@ static int pair_features_grouped_impl(int which /* -1: chosen per hop count, 0: 
     // run-aware kernel keeps h = 1 (6.84 against 6.57 on evaluation lists).  A run-aware kernel with u's rows in LDS instead of registers
     // (global_load_lds landings, ds_read_b128 per comparison) was built and measured: 128 VGPRs + 124 bytes of scratch at four
     // wavefronts per SIMD (1.34 G pairs/s at h = 3), 170 VGPRs at three (1.93): level with the ordinary kernel's default budget, behind
-    // its capped one -- not shipped.  SS_PAIR_GROUPED_KERNEL = runs | plain forces one.
-    static const char *forced = getenv("SS_PAIR_GROUPED_KERNEL");
-    const bool runs = fast && (which >= 0 ? which == 1 : (forced ? !strcmp(forced, "runs") : (order == nullptr && h <= 1)));
-    if (!runs) {
-        if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;
-        return pair_features_impl(links, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, nullptr, nullptr, nullptr,
-                                  err_flag, stream, order, /*grouped=*/true);
-    }
-    if (order && B >= ((int64_t)1 << 31)) return SS_ERR_INVALID_ARG;  // (order entries are int32 pair indices, as on the other path)
-    HopTables tabs;
-    if (!fill_hop_tables(mh, hll, h, tabs)) return SS_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    switch (h) {
-        case 1: return dispatch_pair_runs<1>(links, order, B, N, tabs, P, cards, cards_stride, *prm, flags, out, err_flag, degrees, s);
-        case 2: return dispatch_pair_runs<2>(links, order, B, N, tabs, P, cards, cards_stride, *prm, flags, out, err_flag, degrees, s);
-        default: return dispatch_pair_runs<3>(links, order, B, N, tabs, P, cards, cards_stride, *prm, flags, out, err_flag, degrees, s);
-    }
+    // its capped one -- not shipped.  ss_pair_features_grouped_kernel forces one.
+    const bool runs = is_fast_pair_shape(q.P, q.M) && (which >= 0 ? which == 1 : (order == nullptr && h <= 1));
+    return runs ? launch_pair_runs(q) : launch_pair_query(q);
 }
 
+}  // namespace ss
+
+// The query over a link list whose pairs are walked in runs of equal first nodes (see pair_features_runs_kernel): `order`
+// (nullable) = a permutation of the pair indices, e.g. from ss_group_links_by_source; without it the pairs are walked as they
+// are listed (a coalesced edge list, or an evaluation set that lists all negatives of a source together, already has the
+// runs).  Row q of `out` is pair q whatever the order; rows are bit-identical to ss_pair_features[_normalised]'s.  degrees
+// nullable (non-null: the degree-normalised copy is appended, as ss_pair_features_normalised does).  Shapes without a
+// specialised kernel (P not in {64, 128, 192, 256} or p != 8) take the ordinary path -- same rows, no reuse.
 extern "C" int ss_pair_features_grouped(const int64_t *links, const int32_t *order, int64_t B, int64_t N, int32_t h,
                                         const uint32_t *const *mh, int32_t P, const uint8_t *const *hll, const float *cards,
                                         int64_t cards_stride, const ss_hll_params *prm, uint32_t flags, const float *degrees, float *out,
                                         int32_t *err_flag, void *stream)
 {
-    return pair_features_grouped_impl(-1, links, order, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, err_flag, stream);
+    return ss::grouped_pair_query(-1, links, order, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, err_flag, stream);
 }
 
 // measurement / test hook (subgraph_sketch_debug.h): the same call with the kernel forced -- 0 ordinary, 1 run-aware
@@ -667,5 +674,5 @@ extern "C" int ss_pair_features_grouped_kernel(int32_t which, const int64_t *lin
                                                float *out, int32_t *err_flag, void *stream)
 {
     if (which != 0 && which != 1) return SS_ERR_INVALID_ARG;
-    return pair_features_grouped_impl(which, links, order, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, err_flag, stream);
+    return ss::grouped_pair_query(which, links, order, B, N, h, mh, P, hll, cards, cards_stride, prm, flags, degrees, out, err_flag, stream);
 }

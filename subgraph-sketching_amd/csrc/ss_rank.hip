@@ -19,7 +19,8 @@
 //
 // Links per workgroup (rank_queries()): as many of {32, 16, 8} as leave TWO workgroups per CU (2 x 80 KiB of the 160 KiB LDS) next
 // to the estimator and head tables -- a link costs 256 * CMPL + 576 bytes per hop plus 32 + 4 h bytes of ids, sizes, threshold and sums.
-// The budget behind it, the launch geometry, the (h, CMPL) dispatch and the shared entry checks: ss_head_scan.hpp.  The kernel body is
+// The budget behind it and the shared entry checks: ss_head_scan.hpp; the launch geometry: scan_grid (ss_topk_key.hpp); the (h, CMPL)
+// dispatch: dispatch_pair_shape (ss_pair_math.hpp).  The kernel body is
 // written out here and in ss_topk_head.hip: one source for both was measured and dropped (DESIGN_EXPERIMENTS 3.13).
 #include "ss_feature_algebra.hpp"
 #include "ss_head_scan.hpp"
@@ -223,11 +224,11 @@ extern "C" int ss_rank_score_scan(const int64_t *links, const float *thr, int32_
     HopTables tabs;
     if (!fill_head_scan_tables(mh, hll, h, L, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
-    dispatch_head_scan(h, P, M, [&](auto H, auto CMPL) {
-        hipLaunchKernelGGL((rank_score_scan_kernel<H(), CMPL()>), head_scan_grid(L, rank_queries(H(), CMPL()), N), dim3(256), 0,
+    dispatch_pair_shape(h, P, M, [&](auto H, auto CMPL) {
+        hipLaunchKernelGGL((rank_score_scan_kernel<H(), CMPL()>), scan_grid(L, rank_queries(H(), CMPL()), N), dim3(256), 0,
                            (hipStream_t)stream, links, thr, (int)L, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args,
                            reinterpret_cast<unsigned long long *>(counts), err_flag);
-    }, std::make_integer_sequence<int, 5 * SS_MAX_HOPS>{});
+    }, PairShapes{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

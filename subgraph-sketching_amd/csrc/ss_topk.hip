@@ -159,7 +159,7 @@ extern "C" int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const 
                             size_t keys_bytes, int32_t *err_flag, void *stream)
 {
     using namespace ss;
-    const int rc = check_pair_query_args(/*h=*/1, true, prm, P);  // (one hop pair: no hop count of its own)
+    const int rc = check_pair_query_args(/*h=*/1, true, prm, P, false);  // (one hop pair: no hop count of its own)
     if (rc != SS_OK) return rc;
     if (S < 0 || N <= 0 || N >= ((int64_t)1 << 32) - 1) return SS_ERR_INVALID_ARG;  // (the key's low word holds 0xFFFFFFFF - v)
     if (S == 0) return SS_OK;
@@ -167,18 +167,11 @@ extern "C" int ss_topk_scan(const int64_t *sources, int32_t S, int64_t N, const 
     if (keys_bytes < ss_topk_workspace_bytes(N, S)) return SS_ERR_WORKSPACE;
     const int M = 1 << prm->p;
     const TopkTables tabs = {mh_src, hll_src, mh_cand, hll_cand};
-    const int64_t blocks_y = (S + kTopkSources - 1) / kTopkSources;
-    if (blocks_y > 65535) return SS_ERR_INVALID_ARG;
-    int64_t blocks_x = (kTopkGrid + blocks_y - 1) / blocks_y;
-    const int64_t need_x = (N + kTopkRows - 1) / kTopkRows;
-    if (blocks_x > need_x) blocks_x = need_x;
-    const dim3 grid((unsigned)blocks_x, (unsigned)blocks_y);
-    hipStream_t s = (hipStream_t)stream;
-    if (!is_fast_pair_shape(P, M)) hipLaunchKernelGGL(topk_scan_kernel<0>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
-    else if (P == 64) hipLaunchKernelGGL(topk_scan_kernel<1>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
-    else if (P == 128) hipLaunchKernelGGL(topk_scan_kernel<2>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
-    else if (P == 192) hipLaunchKernelGGL(topk_scan_kernel<3>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
-    else hipLaunchKernelGGL(topk_scan_kernel<4>, grid, dim3(256), 0, s, sources, (int)S, N, tabs, (int)P, M, *prm, keys, err_flag);
+    if (((int64_t)S + kTopkSources - 1) / kTopkSources > 65535) return SS_ERR_INVALID_ARG;  // grid.y
+    dispatch_pair_shape(/*h=*/1, P, M, [&](auto, auto CMPL) {
+        hipLaunchKernelGGL(topk_scan_kernel<CMPL()>, scan_grid(S, kTopkSources, N), dim3(256), 0, (hipStream_t)stream, sources, (int)S, N, tabs,
+                           (int)P, M, *prm, keys, err_flag);
+    }, PairShapes{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

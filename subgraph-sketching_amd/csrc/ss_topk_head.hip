@@ -18,7 +18,8 @@
 //
 // Sources per workgroup (kernel parameter SB, topk_head_sources()): as many of {32, 16, 8} as leave TWO workgroups per CU
 // (2 x 80 KiB of the 160 KiB LDS) next to the estimator and head tables -- a source costs 256 * CMPL + 576 bytes per hop.
-// The budget behind it, the launch geometry, the (h, CMPL) dispatch and the shared entry checks: ss_head_scan.hpp.  The kernel body is
+// The budget behind it and the shared entry checks: ss_head_scan.hpp; the launch geometry: scan_grid (ss_topk_key.hpp); the (h, CMPL)
+// dispatch: dispatch_pair_shape (ss_pair_math.hpp).  The kernel body is
 // written out here and in ss_rank.hip: one source for both was measured and dropped (DESIGN_EXPERIMENTS 3.13).
 #include "ss_feature_algebra.hpp"
 #include "ss_head_scan.hpp"
@@ -190,10 +191,10 @@ extern "C" int ss_topk_score_scan(const int64_t *sources, int32_t S, int64_t N, 
     HopTables tabs;
     if (!fill_head_scan_tables(mh, hll, h, S, tabs)) return SS_ERR_INVALID_ARG;
     const int M = 1 << prm->p;
-    dispatch_head_scan(h, P, M, [&](auto H, auto CMPL) {
-        hipLaunchKernelGGL((topk_score_scan_kernel<H(), CMPL()>), head_scan_grid(S, topk_head_sources(H(), CMPL()), N), dim3(256), 0,
+    dispatch_pair_shape(h, P, M, [&](auto H, auto CMPL) {
+        hipLaunchKernelGGL((topk_score_scan_kernel<H(), CMPL()>), scan_grid(S, topk_head_sources(H(), CMPL()), N), dim3(256), 0,
                            (hipStream_t)stream, sources, (int)S, N, tabs, (int)P, M, cards, cards_stride, *prm, flags, degrees, args, keys, err_flag);
-    }, std::make_integer_sequence<int, 5 * SS_MAX_HOPS>{});
+    }, PairShapes{});
     SS_LAUNCH_CHECK();
     return SS_OK;
 }

@@ -212,6 +212,12 @@ def _return_code(lib, nat, entry, state, order, edits):
         if name == 'prm' and value is not None:
             keep.append(nat.HllParams(**value))
             return byref(keep[-1])
+        if name == 'head' and value is not None:
+            keep.append(nat.StructureHeadStruct(**value))
+            return byref(keep[-1])
+        if isinstance(value, list):   # the per-hop table pointers: a ctypes array, None entries null
+            keep.append((ctypes.c_void_p * len(value))(*value))
+            return keep[-1]
         return value
     return getattr(lib, entry)(*[arg(name) for name in order])
 
@@ -539,6 +545,463 @@ def test_common_neighbour_return_codes_are_pinned(entry):
     assert [name for name, _ in got] == [name for name in _PAIR_PINNED[entry] if name != 'base call']
     for name, row in got:
         assert row == _PAIR_PINNED[entry][name], (entry, name, row, _PAIR_PINNED[entry][name])
+
+
+# ---- return codes of the link-query entry points ---------------------------------------------------------------------------------
+# The same scheme for the pair queries (ss_pairs.hip), the one-vs-all scans (ss_topk.hip, ss_topk_head.hip, ss_rank.hip), the masked
+# query and the two permutation passes.  Base calls, none of which an edit can turn into a launch: the pair queries get a table-pointer
+# array whose last entry is null; ss_topk_scan 32 * 65 535 + 1 sources and the head scans 8 * 65 535 + 1 entries with every byte of keys
+# "given" (grid.y is the failing check); ss_topk_exclude keys one byte short and ss_masked_pair_features a workspace of 0 bytes;
+# ss_gather_links a links pointer that is not 16-byte aligned; ss_scatter_feature_rows, which has no check that fails without a launch
+# behind it, n = 0 (its edits give n > 0 only together with a missing pointer).  The orders the code marks as deliberate show in the
+# rows: ss_pair_scores answers B = 0 before it looks at prm, the feature queries after it but before P.  The letters were produced by
+# the library as it stood before the host side of these units was rewritten around one request record and one shape dispatcher.
+def _link_query_entries():
+    F = _FAKE
+    head = dict(dim=8, normalised=0, w1=F, shift=F, w2=F, bias=0.5)   # a plain head of h = 2
+    hops = [('h = 0', _edit(h=0)), ('h = 4', _edit(h=4))]
+    width = [('P = 0', _edit(P=0)), ('P = 130', _edit(P=130)), ('P = 2052', _edit(P=2052)), ('P = 100', _edit(P=100))]
+    tables = [('no mh', _edit(mh=None)), ('no hll', _edit(hll=None)), ('mh[0] null', _edit(mh=[None, F])), ('hll whole, no mh', _edit(hll=[F, F], mh=None)),
+              ('no cards', _edit(cards=None)), ('cards_stride < h', _edit(cards_stride=1))]
+    heads = [('no head', _edit(head=None)), ('head.dim = 15', _edit(**{'head.dim': 15})), ('head.w2 null', _edit(**{'head.w2': None})),
+             ('degrees with a plain head', _edit(degrees=F)),
+             ('normalised head without degrees', _edit(degrees=None, **{'head.dim': 16, 'head.normalised': 1})),
+             ('normalised head with degrees', _edit(degrees=F, **{'head.dim': 16, 'head.normalised': 1}))]
+
+    def sizes(n, ceilings):
+        return ([(f'{n} < 0', _edit(**{n: -1})), (f'{n} = 0', _edit(**{n: 0})), ('N < 0', _edit(N=-1)), ('N = 0', _edit(N=0))]
+                + [(f'N = {name}', _edit(N=value)) for name, value in ceilings])
+
+    pair_n = [('2^31', 1 << 31)]
+    scan_n = [('2^32 - 2', (1 << 32) - 2), ('2^32 - 1', (1 << 32) - 1), ('2^32', 1 << 32)]
+    ordered = [('no order', _edit(order=None)), ('B = 2^31', _edit(B=1 << 31)), ('B = 2^31, no order', _edit(B=1 << 31, order=None))]
+    entries = {}
+    pq = dict(_state(links=F, B=4, N=4, h=2, mh=[F, F], P=128, hll=[F, None], cards=F, cards_stride=2, flags=0, out=F, err_flag=F), g=None)
+    entries['ss_pair_features'] = (
+        dict(pq, dbg_match=F, dbg_zero=F, dbg_inter=F),
+        ('links', 'B', 'N', 'h', 'mh', 'P', 'hll', 'cards', 'cards_stride', 'prm', 'flags', 'out', 'dbg_match', 'dbg_zero', 'dbg_inter',
+         'err_flag', None),
+        hops + sizes('B', pair_n) + [('no links', _edit(links=None)), ('no out', _edit(out=None)),
+                                     ('no dbg, no err_flag', _edit(dbg_match=None, dbg_zero=None, dbg_inter=None, err_flag=None))]
+        + tables + width + _prm_edits())
+    entries['ss_pair_features_normalised'] = (
+        dict(pq, degrees=F),
+        ('links', 'B', 'N', 'h', 'mh', 'P', 'hll', 'cards', 'cards_stride', 'prm', 'flags', 'degrees', 'out', 'err_flag', None),
+        hops + sizes('B', pair_n) + [('no links', _edit(links=None)), ('no out', _edit(out=None)), ('no degrees', _edit(degrees=None)),
+                                     ('no err_flag', _edit(err_flag=None))] + tables + width + _prm_edits())
+    grouped_order = ('links', 'order', 'B', 'N', 'h', 'mh', 'P', 'hll', 'cards', 'cards_stride', 'prm', 'flags', 'degrees', 'out', 'err_flag', None)
+    grouped = (hops + sizes('B', pair_n) + ordered + [('no links', _edit(links=None)), ('no out', _edit(out=None)),
+                                                      ('no degrees, no err_flag', _edit(degrees=None, err_flag=None)), ('h = 1', _edit(h=1, hll=[None, F]))]
+               + tables + width + _prm_edits())
+    entries['ss_pair_features_grouped'] = (dict(pq, order=F, degrees=F), grouped_order, grouped)
+    entries['ss_pair_features_grouped_kernel'] = (
+        dict(pq, order=F, degrees=F, which=1), ('which',) + grouped_order,
+        [('which = -1', _edit(which=-1)), ('which = 2', _edit(which=2)), ('which = 0', _edit(which=0))] + grouped)
+    entries['ss_pair_scores'] = (
+        dict(pq, order=F, degrees=None, head=head),
+        ('links', 'order', 'B', 'N', 'h', 'mh', 'P', 'hll', 'cards', 'cards_stride', 'prm', 'flags', 'degrees', 'head', 'out', 'err_flag', None),
+        hops + sizes('B', pair_n) + ordered + [('no links', _edit(links=None)), ('no out', _edit(out=None)), ('no err_flag', _edit(err_flag=None))]
+        + tables + heads + width + _prm_edits())
+    S_y = 32 * 65535 + 1
+    entries['ss_topk_scan'] = (
+        dict(_state(sources=F, S=S_y, N=4, mh_src=F, hll_src=F, mh_cand=F, hll_cand=F, P=128, keys=F, keys_bytes=(1 << 64) - 1, err_flag=F), g=None),
+        ('sources', 'S', 'N', 'mh_src', 'hll_src', 'mh_cand', 'hll_cand', 'P', 'prm', 'keys', 'keys_bytes', 'err_flag', None),
+        sizes('S', scan_n) + [('no ' + name, _edit(**{name: None})) for name in ('sources', 'mh_src', 'hll_src', 'mh_cand', 'hll_cand', 'keys', 'err_flag')]
+        + [('keys_bytes one short', _edit(keys_bytes=8 * 4 * S_y - 1)), ('keys_bytes exact', _edit(keys_bytes=8 * 4 * S_y))] + width + _prm_edits())
+    entries['ss_topk_exclude'] = (
+        dict(sources=F, S=4, N=4, rowptr=F, col=F, keys=F, keys_bytes=8 * 4 * 4 - 1),
+        ('sources', 'S', 'N', 'rowptr', 'col', 'keys', 'keys_bytes', None),
+        sizes('S', scan_n) + [('no ' + name, _edit(**{name: None})) for name in ('sources', 'rowptr', 'col', 'keys')]
+        + [('keys_bytes = 0', _edit(keys_bytes=0))])
+    n_y = 8 * 65535 + 1
+    hs = dict(_state(N=4, h=2, mh=[F, F], hll=[F, F], P=128, cards=F, cards_stride=2, flags=0, degrees=None, head=head, err_flag=F), g=None)
+    scan_tables = [e for e in tables if e[0] != 'hll whole, no mh'] + [('hll[1] null', _edit(hll=[F, None]))]
+    entries['ss_topk_score_scan'] = (
+        dict(hs, sources=F, S=n_y, keys=F, keys_bytes=(1 << 64) - 1),
+        ('sources', 'S', 'N', 'h', 'mh', 'hll', 'P', 'cards', 'cards_stride', 'prm', 'flags', 'degrees', 'head', 'keys', 'keys_bytes', 'err_flag', None),
+        hops + sizes('S', scan_n) + [('no sources', _edit(sources=None)), ('no keys', _edit(keys=None)), ('no err_flag', _edit(err_flag=None)),
+                                     ('keys_bytes one short', _edit(keys_bytes=8 * 4 * n_y - 1))] + scan_tables + heads + width + _prm_edits())
+    entries['ss_rank_score_scan'] = (
+        dict(hs, links=F, thr=F, L=n_y, counts=F),
+        ('links', 'thr', 'L', 'N', 'h', 'mh', 'hll', 'P', 'cards', 'cards_stride', 'prm', 'flags', 'degrees', 'head', 'counts', 'err_flag', None),
+        hops + sizes('L', scan_n) + [('no links', _edit(links=None)), ('no thr', _edit(thr=None)), ('no counts', _edit(counts=None)),
+                                     ('no err_flag', _edit(err_flag=None))] + scan_tables + heads + width + _prm_edits())
+    entries['ss_masked_pair_features'] = (
+        dict(_state(links=F, B=4, N=4, h=2, a=F, b=F, mh=[F, F], P=128, hll=[F, F], cards=F, cards_stride=2, flags=0, out=F, dbg_match=F, dbg_zero=F,
+                    dbg_row_zeros=F, dbg_masked=F, err_flag=F, workspace=F, workspace_bytes=0), g=dict(_state()['g'], row_begin=0, row_end=0)),
+        ('g', 'links', 'B', 'N', 'h', 'a', 'b', 'mh', 'P', 'hll', 'cards', 'cards_stride', 'prm', 'flags', 'out', 'dbg_match', 'dbg_zero',
+         'dbg_row_zeros', 'dbg_masked', 'err_flag', 'workspace', 'workspace_bytes', None),
+        hops + sizes('B', pair_n) + [('B = 2^31', _edit(B=1 << 31)), ('N = 2^31 in the graph too', _edit(N=1 << 31, **{'g.num_nodes': 1 << 31})),
+                                     ('no graph', _edit(g=None)), ('no rowptr', _edit(**{'g.rowptr': None})), ('no col', _edit(**{'g.col': None})),
+                                     ('a row range', _edit(**{'g.row_begin': 1, 'g.row_end': 3})), ('no a', _edit(a=None)), ('no b', _edit(b=None)),
+                                     ('no workspace', _edit(workspace=None)), ('no links', _edit(links=None)), ('no out', _edit(out=None)),
+                                     ('no dbg, no err_flag', _edit(dbg_match=None, dbg_zero=None, dbg_row_zeros=None, dbg_masked=None, err_flag=None)),
+                                     ('P = 1024 (272 chunks)', _edit(P=1024))]
+        + [e for e in tables if e[0] != 'hll whole, no mh'] + width + _prm_edits())
+    entries['ss_gather_links'] = (
+        dict(links=F, order=F, n=4, out_links=16), ('links', 'order', 'n', 'out_links', None),
+        [('n < 0', _edit(n=-1)), ('n = 0', _edit(n=0)), ('n = 0, no pointers', _edit(n=0, links=None, order=None, out_links=None)),
+         ('no links', _edit(links=None)), ('no order', _edit(order=None)), ('no out_links', _edit(out_links=None)),
+         ('out_links unaligned too', _edit(out_links=F))])
+    entries['ss_scatter_feature_rows'] = (
+        dict(rows=F, order=F, n=0, width=8, out=F), ('rows', 'order', 'n', 'width', 'out', None),
+        [('n < 0', _edit(n=-1)), ('width = 0', _edit(width=0)), ('width < 0', _edit(width=-1)), ('n = 0, no pointers', _edit(rows=None, order=None, out=None)),
+         ('n = 4, no rows', _edit(n=4, rows=None)), ('n = 4, no order', _edit(n=4, order=None)), ('n = 4, no out', _edit(n=4, out=None))])
+    return entries
+
+
+_LINK_PINNED = {
+    'ss_pair_features': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUU',
+        'B < 0': 'UUI0IIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'UUI0I000000000000000IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no out': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no dbg, no err_flag': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'hll whole, no mh': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUIUIUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_pair_features_normalised': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUIUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUIUUUUUUUUUUUUUUUU',
+        'B < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'UUI0I0000I00000000000IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no out': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no degrees': 'IIIIIIIIIIIIIIIIIIIIIIIIII',
+        'no err_flag': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'hll whole, no mh': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUIUIUUUUIUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_pair_features_grouped': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUUUUUIUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUIUUUUUUUUUUUUUUU',
+        'B < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'UUI0I000II00000000000000IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no order': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31, no order': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no out': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no degrees, no err_flag': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'h = 1': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'hll whole, no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUIUIUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_pair_features_grouped_kernel': {
+        'base call': 'I',
+        'which = -1': 'IIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'which = 2': 'IIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'which = 0': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'h = 0': 'IIUUUUUUUUUUUUUUIUUUUUUUUUUUUUUU',
+        'h = 4': 'IIUUUUUUUUUUUUUUIUUUUUUUUUUUUUUU',
+        'B < 0': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'II0UUI0I000II00000000000000IUII0',
+        'N < 0': 'IIIUUIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no order': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31, no order': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no out': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no degrees, no err_flag': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'h = 1': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'hll whole, no mh': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'IIIUUIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'IIUUUIUIUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'IIIUUIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'IIIUUIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'IIIUUI0IIIIIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_pair_scores': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'B < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'UUI0I000II000000000000000000000000',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no order': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'B = 2^31, no order': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no out': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no err_flag': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'hll whole, no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.dim = 15': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.w2 null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'degrees with a plain head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head without degrees': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head with degrees': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUI0IUUUUUUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_topk_scan': {
+        'base call': 'I',
+        'S < 0': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'S = 0': 'I0II0II000000000III0IUII0',
+        'N < 0': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 0': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32 - 2': 'I0IIIIIIIIIIIIWWIIIIIUIII',
+        'N = 2^32 - 1': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'no sources': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no mh_src': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no hll_src': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no mh_cand': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no hll_cand': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no keys': 'I0IIIIIIIIIIIIIIIIIIIUIII',
+        'no err_flag': 'I0IIIIIIIIIIIIWIIIIIIUIII',
+        'keys_bytes one short': 'I0IIWIIIIIIIIWWIIIIWIUIIW',
+        'keys_bytes exact': 'I0IIWIIIIIIIIIWIIIIIIUIII',
+        'P = 0': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'I0IIIIIIIIIIIIWIIIIIIUIII',
+        'no prm': 'IIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'IIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'I0IIIIIIIIIIIIWIIIIIIUIII',
+    },
+    'ss_topk_exclude': {
+        'base call': 'W',
+        'S < 0': 'I0IIIIIIIIII',
+        'S = 0': 'I0II0II00000',
+        'N < 0': 'IIIIWIIIIIII',
+        'N = 0': 'IIIIWIIIIIII',
+        'N = 2^32 - 2': 'I0IIWIIIIIIW',
+        'N = 2^32 - 1': 'IIIIWIIIIIII',
+        'N = 2^32': 'IIIIWIIIIIII',
+        'no sources': 'I0IIIIIIIIII',
+        'no rowptr': 'I0IIIIIIIIII',
+        'no col': 'I0IIIIIIIIII',
+        'no keys': 'I0IIIIIIIIII',
+        'keys_bytes = 0': 'I0IIWIIIIIIW',
+    },
+    'ss_topk_score_scan': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'S < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'S = 0': 'UUI0II0II0000000000000000III0IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32 - 2': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32 - 1': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no sources': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no keys': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no err_flag': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'keys_bytes one short': 'UUI0IIWIIIIWWIIWIIWIIIIIWIIIWIUIIW',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'hll[1] null': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'no head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.dim = 15': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.w2 null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'degrees with a plain head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head without degrees': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head with degrees': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIWIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_rank_score_scan': {
+        'base call': 'I',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'L < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'L = 0': 'UUI0II00I0000000000000000III0IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32 - 2': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32 - 1': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^32': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no thr': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no counts': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no err_flag': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no cards': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'hll[1] null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.dim = 15': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'head.w2 null': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'degrees with a plain head': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head without degrees': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'normalised head with degrees': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 130': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 2052': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUIUUUI',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+    },
+    'ss_masked_pair_features': {
+        'base call': 'W',
+        'h = 0': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'h = 4': 'UUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUUU',
+        'B < 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'B = 0': 'UUI0I0III00000000000000000000IUII0',
+        'N < 0': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 0': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'N = 2^31': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'B = 2^31': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'N = 2^31 in the graph too': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'no graph': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no rowptr': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no col': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'a row range': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no a': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no b': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no workspace': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'no links': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'no out': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'no dbg, no err_flag': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'P = 1024 (272 chunks)': 'UUI0IIIIIIIIIIIIUUUUIIUUUIIIWIUIIU',
+        'no mh': 'UUI0IIIIIIIIIIIIIIIIIIWIIIIIIIUIII',
+        'no hll': 'UUI0IIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'mh[0] null': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'no cards': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'cards_stride < h': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'P = 0': 'UUI0IIIIIIIIIIIIIIIUIIIIIIIIWIUIII',
+        'P = 130': 'UUI0IIIIIIIIIIIIIIIUIIIIIIIIWIUIII',
+        'P = 2052': 'UUI0IIIIIIIIIIIIIIIUIIIIIIIIWIUIII',
+        'P = 100': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+        'no prm': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII',
+        'prm.p = 3': 'UUIUIUIIIUUUUUUUUUUUUUUUUUUUUIUUUW',
+        'prm.n_tbl = 5': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.bias missing': 'UUIIIIIIIIIIIIIIIIIIIIIIIIIIIIUIII',
+        'prm.p = 9': 'UUI0IIIIIIIIIIIIWWWUIIWWWIIIWIUIIW',
+    },
+    'ss_gather_links': {
+        'base call': 'I',
+        'n < 0': 'I00IIII',
+        'n = 0': 'I000000',
+        'n = 0, no pointers': 'I000000',
+        'no links': 'I00IIII',
+        'no order': 'I00IIII',
+        'no out_links': 'I00IIII',
+        'out_links unaligned too': 'I00IIII',
+    },
+    'ss_scatter_feature_rows': {
+        'base call': '0',
+        'n < 0': 'IIIIIII',
+        'width = 0': 'IIIIIII',
+        'width < 0': 'IIIIIII',
+        'n = 0, no pointers': 'III0III',
+        'n = 4, no rows': 'IIIIIII',
+        'n = 4, no order': 'IIIIIII',
+        'n = 4, no out': 'IIIIIII',
+    },
+}
+
+
+@pytest.mark.parametrize('entry', sorted(_link_query_entries()))
+def test_link_query_return_codes_are_pinned(entry):
+    """every bad-argument class of the link-query entry points, alone and in pairs, and their early SS_OK exits: the codes of the
+    library before the host side of these units was refactored (a '?' would be a code outside the four: a launch was reached)"""
+    import subgraph_sketching_amd as ssa
+    nat = ssa._native
+    state, order, _ = _link_query_entries()[entry]
+    base = _return_code(nat.lib(), nat, entry, state, order, [])
+    assert _LETTER.get(base) == _LINK_PINNED[entry]['base call'], base
+    got = _return_code_rows(entry, _link_query_entries())
+    assert [name for name, _ in got] == [name for name in _LINK_PINNED[entry] if name != 'base call']
+    for name, row in got:
+        assert row == _LINK_PINNED[entry][name], (entry, name, row, _LINK_PINNED[entry][name])
 
 
 def test_missing_library_fails_loudly(monkeypatch):

@@ -2,7 +2,8 @@
 topk_scan_kernel and masked_pairs_kernel give the same bits for the same pair (csrc/ss_pair_math.hpp).  Every assertion compares one
 entry point of the library with ANOTHER one (or with float32 torch), never a code path with itself, on a graph small enough for
 seconds: 300 nodes, three of them given degree 0, 2 000 links with negative ids, u == v and two ids out of range, for h = 1 .. 3 on the
-compile-time shape (P = 128, p = 8) and on a run-time shape with fewer MinHash chunks than lanes (P = 36, p = 6)."""
+four compile-time shapes (P = 64, 128, 192, 256 at p = 8) and on a run-time shape with fewer MinHash chunks than lanes (P = 36,
+p = 6): every branch of the one shape dispatcher (dispatch_pair_shape), through every entry point."""
 from argparse import Namespace
 from ctypes import byref, c_void_p
 
@@ -15,7 +16,8 @@ from score_restatement import raw_head
 pytestmark = pytest.mark.gpu
 
 N, L = 300, 2000
-SHAPES = [(128, 8), (36, 6)]
+SHAPES = [(128, 8), (36, 6), (64, 8), (192, 8), (256, 8)]
+FAST = [(P, p) for P, p in SHAPES if p == 8 and P in (64, 128, 192, 256)]  # the shapes with compile-time kernels (run-aware: these only)
 
 
 @pytest.fixture(scope='module')
@@ -93,7 +95,7 @@ def test_grouped_kernels_and_the_normalised_half(ssa, dev, world, h, shape):
     mh_ptrs = (c_void_p * h)(*[table[k].mh_u32.data_ptr() for k in range(1, h + 1)])
     hl_ptrs = (c_void_p * h)(*[table[k].hll_u8.data_ptr() for k in range(1, h + 1)])
     order = H.group_links_by_source(links, N, dev).to(torch.int32).contiguous()
-    for which in ((0, 1) if shape == (128, 8) else (0,)):
+    for which in ((0, 1) if shape in FAST else (0,)):
         for o in (order, None):
             for dg, ref in ((None, plain), (deg, normed)):
                 out = torch.full_like(ref, 7.0)

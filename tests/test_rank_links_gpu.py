@@ -260,9 +260,10 @@ def test_sketch_shapes(ssa, dev, P, p):
 
 
 @pytest.mark.parametrize('h', [1, 2, 3])
-@pytest.mark.parametrize('P', [64, 192, 256])
+@pytest.mark.parametrize('P', [64, 192, 256, 36])
 def test_fast_shapes_at_the_other_hop_counts(ssa, dev, h, P):
-    """every (h, P) instantiation stages another number of links per workgroup: 45 links cross a block boundary in each"""
+    """every (h, P) instantiation stages another number of links per workgroup: 45 links cross a block boundary in each
+    (P = 36: the run-time-size instantiation of every hop count, fewer MinHash chunks than lanes)"""
     N, ei = _graph('ba40')
     eh = _eh(ssa, h=h, P=P)
     table, cards = eh.build_hash_tables(N, torch.from_numpy(ei).to(dev))
