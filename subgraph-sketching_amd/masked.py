@@ -17,6 +17,12 @@ def _is_int_tensor(t):
     return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
 
 
+def _check_row_chunks(num_perm, p):
+    if (num_perm >> 2) + ((1 << p) >> 4) > 256:
+        raise NotImplementedError(f'the masked query walks a sketch row with one 16-byte chunk per thread: num_perm / 4 + 2^hll_p / 16 must '
+                                  f'not exceed 256, got {num_perm} and {p}')
+
+
 def check_arguments(eh, links, mask_target, batch_size, degrees=None, lazy=False, out=None):
     """-> (links [L, 2], edge_index [2, E], batch_size) after every check that needs no device"""
     for name, given in (('degrees', degrees is not None), ('lazy', bool(lazy)), ('out', out is not None)):
@@ -24,6 +30,7 @@ def check_arguments(eh, links, mask_target, batch_size, degrees=None, lazy=False
             raise ValueError(f'mask_target cannot be combined with {name}: the masked query returns plain feature rows in a tensor of its own')
     if eh.max_hops not in (1, 2, 3):
         raise NotImplementedError('Only 1, 2 and 3 hop hashes are implemented')
+    _check_row_chunks(eh.num_perm, eh.p)
     lk = torch.as_tensor(links)
     if lk.dim() == 1:
         lk = lk.unsqueeze(0)
@@ -55,9 +62,7 @@ def masked_subgraph_features(eh, links, hash_table, cards, mask_target, batch_si
     mh, hll, N, P = eh._resolve_tables(hash_table, device)
     if N >= (1 << 31):
         raise NotImplementedError(f'the masked query does not support {N} nodes')
-    if (P >> 2) + (eh.m >> 4) > 256:
-        raise NotImplementedError(f'the masked query walks a sketch row with one 16-byte chunk per thread: num_perm / 4 + 2^hll_p / 16 must '
-                                  f'not exceed 256, got {P} and {eh.p}')
+    _check_row_chunks(P, eh.p)  # (the tables' own width: check_arguments has seen the engine's)
     cd = cards if (cards.device == device and cards.dtype == torch.float32) else cards.to(device=device, dtype=torch.float32)
     if cd.dim() != 2 or cd.size(0) != N or cd.size(1) < h:
         raise ValueError(f'cards must have shape [{N}, >= {h}], got {tuple(cd.shape)}')
