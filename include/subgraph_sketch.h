@@ -726,6 +726,55 @@ int ss_link_grad_hub_finish(const int64_t *nodes, int64_t M, const int32_t *hub_
                             int64_t n_chunks, int64_t N, const void *workspace, size_t workspace_bytes, int32_t F, float *grad_x,
                             void *stream);
 
+/* Node features pooled over a list of weighted entries per link, forward and backward (csrc/ss_cn_rows.hip): the trainable form of
+ * ss_common_neighbour_pool -- the sum of learned embeddings over every link's common neighbours (Neural Common Neighbour) -- which
+ * torch writes as `coef[:, None] * x[ids]` and an index_add_, a [T, F] tensor and float atomics in both directions.
+ * A list is rowptr (device int64 [L + 1], non-decreasing, inside [0, T]), ids (device int64 [T]) and coef (device fp32 [T]): entry k
+ * belongs to link owner[k], the q with rowptr[q] <= k < rowptr[q + 1] (ss_common_neighbour_count / _fill make such a list; ids need
+ * not ascend or be distinct inside a row).  T, L, N < 2^31; x: device fp32 [N, F], out: device fp32 [L, F], row-major; every offset
+ * is 64-bit (N * F and L * F may pass 2^31); float4 accesses when F % 4 == 0 and the float bases are 16-byte aligned, scalar ones
+ * otherwise -- the bits are the same either way.  The accumulation order is the contract, the one ss_aggr_rows is pinned to.  A row
+ * with the entries k_0 < k_1 < ... in chunks of C = ss_cn_rows_chunk() = 256:
+ *   p_c = the sequential fp32 sum from +0 of the terms t_k of chunk c, in that order;  s = ((0 + p_0) + p_1) + ...
+ *   forward   row q of out, its entries rowptr[q] .. rowptr[q + 1] - 1 in list order,        t_k = fl(coef[k] * x[ids[k], :])
+ *   backward  row nodes[r] of grad_x, its entries order[rowptr[r] .. rowptr[r + 1]),          t_k = fl(coef[k] * g[owner[k], :])
+ * products and sums rounded separately, one lane per output element and chunk, no float atomics, no inter-workgroup waits; an empty
+ * row is +0.  A list position outside [0, T), an id outside [0, N) and an owner outside [0, L) are not followed.  Up to 256 entries
+ * a forward row is the sequential sum of ss_common_neighbour_pool bit for bit; longer rows follow the chunk rule.  A row's bits
+ * depend on its own entries and their order, not on the tier, on hub_entries or on the other rows.
+ * The backward runs on a grouping of the T entries by id: nodes (device int64 [M], the distinct named nodes ascending), rowptr
+ * (device int64 [M + 1]), order (device int32 [T], the list positions of every node ascending: a STABLE grouping), owner (device
+ * int64 [T]); g: device fp32 [L, F].  Only the M listed rows of grad_x (device fp32 [N, F]) are written; the caller clears the others.
+ *   ss_cn_rows_forward / ss_cn_rows_grad    the regular tier: one row group per link / per listed node; rows of more than
+ *                              hub_entries (>= 1) entries are left untouched
+ *   ss_cn_rows_forward_hub_partials / ss_cn_rows_grad_hub_partials    one row group per (hub row, chunk): p_c of chunk t goes to row t
+ *                              of the workspace [n_chunks, F].  hub_rows (int32 [n_hubs]) lists the rows of more than hub_entries
+ *                              entries (forward: links; backward: POSITIONS in nodes), hub_chunk (int32 [n_hubs + 1]) where each
+ *                              hub's chunks start, chunk_hub (int32 [n_chunks]) the hub of every chunk
+ *   ss_cn_rows_forward_hub_finish / ss_cn_rows_grad_hub_finish    per hub row: its partials added in chunk order, the row stored
+ *   ss_cn_rows_workspace_bytes(hub_chunks, F) = hub_chunks * F * 4, 0 for a shape that is refused
+ * SS_ERR_INVALID_ARG before any launch for a null pointer while there is work, negative sizes, T, L or N >= 2^31, M > N or M > T,
+ * hub_entries < 1, n_hubs > n_chunks, a workspace smaller than ss_cn_rows_workspace_bytes; L == 0, M == 0, F == 0 (hub launches:
+ * or no chunks / hubs) return SS_OK without a launch, with null pointers too; T == 0 with L > 0 stores rows of +0. */
+int ss_cn_rows_chunk(void);
+size_t ss_cn_rows_workspace_bytes(int64_t hub_chunks, int32_t F);
+int ss_cn_rows_forward(const int64_t *rowptr, const int64_t *ids, const float *coef, int64_t L, int64_t T, int64_t N, int64_t hub_entries,
+                       const float *x, int32_t F, float *out, void *stream);
+int ss_cn_rows_forward_hub_partials(const int64_t *rowptr, const int64_t *ids, const float *coef, int64_t L, int64_t T, int64_t N,
+                                    const int32_t *hub_rows, const int32_t *hub_chunk, const int32_t *chunk_hub, int64_t n_hubs,
+                                    int64_t n_chunks, const float *x, int32_t F, void *workspace, size_t workspace_bytes, void *stream);
+int ss_cn_rows_forward_hub_finish(int64_t L, const int32_t *hub_rows, const int32_t *hub_chunk, int64_t n_hubs, int64_t n_chunks,
+                                  const void *workspace, size_t workspace_bytes, int32_t F, float *out, void *stream);
+int ss_cn_rows_grad(const int64_t *nodes, const int64_t *rowptr, const int32_t *order, int64_t M, const int64_t *owner, const float *coef,
+                    int64_t T, int64_t L, int64_t N, int64_t hub_entries, const float *g, int32_t F, float *grad_x, void *stream);
+int ss_cn_rows_grad_hub_partials(const int64_t *rowptr, const int32_t *order, int64_t M, const int64_t *owner, const float *coef, int64_t T,
+                                 int64_t L, int64_t N, const int32_t *hub_rows, const int32_t *hub_chunk, const int32_t *chunk_hub,
+                                 int64_t n_hubs, int64_t n_chunks, const float *g, int32_t F, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int ss_cn_rows_grad_hub_finish(const int64_t *nodes, int64_t M, const int32_t *hub_rows, const int32_t *hub_chunk, int64_t n_hubs,
+                               int64_t n_chunks, int64_t N, const void *workspace, size_t workspace_bytes, int32_t F, float *grad_x,
+                               void *stream);
+
 /* Graph readouts over a disjoint-union batch of subgraphs (csrc/ss_pool.hip; reference models/seal.py: global_sort_pool :245,
  * global_add_pool / global_mean_pool :42-45, :101-106, :161, centre pooling :88-95, :149-156) [PyG semantics restated].
  * Shared by every entry: graph q owns the rows rowptr[q] .. rowptr[q + 1] of x (rowptr: device int64 [L + 1], non-decreasing,

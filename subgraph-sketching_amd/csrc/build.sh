@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=../libsubgraph_sketch.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -I ../../include $SS_EXTRA_FLAGS"
-UNITS="ss_init ss_digest ss_csr ss_csr_sort_rows ss_propagate ss_first_hop ss_fused_hop ss_update ss_count ss_pairs ss_masked ss_topk ss_topk_head ss_rank ss_lsh ss_negatives ss_wedge ss_exact ss_exact_nodes ss_sampled_nodes ss_subgraph ss_components ss_coalesce ss_heuristics ss_cn_pool ss_ppr ss_spmm ss_aggr ss_link_decoder ss_pool ss_api ss_debug"
+UNITS="ss_init ss_digest ss_csr ss_csr_sort_rows ss_propagate ss_first_hop ss_fused_hop ss_update ss_count ss_pairs ss_masked ss_topk ss_topk_head ss_rank ss_lsh ss_negatives ss_wedge ss_exact ss_exact_nodes ss_sampled_nodes ss_subgraph ss_components ss_coalesce ss_heuristics ss_cn_pool ss_ppr ss_spmm ss_aggr ss_link_decoder ss_cn_rows ss_pool ss_api ss_debug"
 OBJS=""
 PIDS=""
 mkdir -p build

@@ -324,7 +324,8 @@ def common_neighbour_features(A, edge_index, x, weighting='CN', batch_size=10000
     contiguous); any F >= 0.  weighting: 'CN', 'AA', 'RA' or a 1-D float multiplier of length N.  out: optional contiguous float32
     [L, F] on the compute device, filled and returned.  batch_size: links per launch.  Otherwise the result is on the links' device.
     Inference and precompute only: there is NO gradient with respect to x (it would be a float scatter-add), and NaN or Inf in x is
-    outside the contract (0 * Inf of a stored zero is NaN).  A link id outside [0, N) gives a row of zeros and an IndexError after
+    outside the contract (0 * Inf of a stored zero is NaN).  The trainable form is cn_pool.common_neighbour_pool on a
+    CommonNeighbourBatch: the same rows bit for bit up to 256 common neighbours, the chunked sum beyond.  A link id outside [0, N) gives a row of zeros and an IndexError after
     the launches (ss_common_neighbour_pool: csrc/ss_cn_pool.hip)."""
     links = _check_links(edge_index)
     weighting = _check_weighting(A, weighting, allow_none=False)

@@ -277,6 +277,39 @@ def link_decoder_bytes(N, L, F, product=False, backward=False, M=None, hub_chunk
     return b
 
 
+def cn_rows_bytes(N, L, T, F, backward=False, M=None, hub_chunks=0):
+    """algorithmic bytes of one launch family of cn_pool.common_neighbour_pool (csrc/ss_cn_rows.hip) for a list of T entries
+    in L links over N nodes and F fp32 columns, forward or backward; M = the distinct nodes the list names (default: as many as
+    there can be, min(N, T)); hub_chunks = the 256-entry chunks of the direction's hub rows.
+      forward    'gathered' per entry a row of x (4F); 'written' the L rows of out (4F each); 'entries' per entry its id (8) and
+                 coefficient (4), re-read once per pass over the columns -- ceil(F / 256) passes with float4 pieces, ceil(F / 64) when
+                 F % 4 != 0 -- and per link two row-pointer words (16); 'workspace' hub_chunks * 4F written by the partials launch
+                 and read again by the finish launch
+      backward   'cleared' the zero fill of grad_x, N * 4F; 'gathered' per entry a row of g; 'written' the M named rows; 'entries'
+                 per entry and pass the order word (4), the owner (8) and the coefficient (4), and per named node its id (8) and two
+                 row-pointer words (16); 'workspace' as in the forward
+    The plan's own build (the list, a stable grouping of T ids and a few passes over N counters) is not part of a product and not
+    counted."""
+    zero = {'gathered': 0, 'written': 0, 'cleared': 0, 'entries': 0, 'workspace': 0, 'total': 0}
+    if F == 0 or (L == 0 and not backward) or (N == 0 and backward):
+        return zero
+    row = 4 * F
+    passes = (F + 255) // 256 if F % 4 == 0 else (F + 63) // 64
+    b = dict(zero)
+    b['gathered'] = T * row
+    b['workspace'] = 2 * hub_chunks * row
+    if not backward:
+        b['written'] = L * row
+        b['entries'] = passes * T * 12 + L * 16
+    else:
+        M = min(N, T) if M is None else M
+        b['cleared'] = N * row
+        b['written'] = M * row
+        b['entries'] = passes * T * 16 + M * 24
+    b['total'] = sum(v for k, v in b.items() if k != 'total')
+    return b
+
+
 def segment_pool_bytes(T, L, F):
     """algorithmic bytes of pooling.global_add_pool / global_mean_pool forward (ss_segment_pool, csrc/ss_pool.hip)
     over T node rows in L graphs, F fp32 columns: every row of x read once (T * 4F), the output written (L * 4F), the L + 1 offsets.
